@@ -10,6 +10,7 @@ parameters of every sample, batched Adam + plateau step, ranking.  Workload: SYN
 (SURVEY 8d), V=16 reference views, fp32, synthetic data, random-init weights.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy
     python bench.py --gpus N ...                      # bench.py starts the N ranks itself (launch_ranks below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
@@ -48,8 +49,11 @@ F16_MFMA_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: BF16/FP16 MFMA ~2.5 PF den
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=20, help='timed pose iterations of the headline loop (exactly this many)')
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the headline loop computed in its last timed step as DIR/<name>.npy '
+                         '(float32 / float64; the inputs are seeded, so two builds can be compared output for output)')
     ap.add_argument('--size', type=int, default=128, help='latent volume side S of SYN(S,C)')
     ap.add_argument('--channels', type=int, default=16)
     ap.add_argument('--views', type=int, default=16)
@@ -61,10 +65,10 @@ def parse(argv=None):
                          'the HIP loop from the same start (trace_parity_at_full_size)')
     ap.add_argument('--no-alt', action='store_true', help='skip the secondary f16x3 measurement')
     ap.add_argument('--no-graph', action='store_true', help='(accepted, no effect: the hipGraph block moved to tools/engine_ab.py)')
-    ap.add_argument('--repeats', type=int, default=30,
-                    help='the timed region (exactly --steps iterations between barriers) is run this many times back to back; '
-                         '`value` is steps / MEDIAN block time, every block time is reported (box-to-box and run-to-run '
-                         'spread of a 0.1 s region is a few per cent)')
+    ap.add_argument('--repeats', type=int, default=1,
+                    help='the --steps timed iterations are split into this many back-to-back blocks, each between barriers '
+                         '(sizes as equal as possible, at least one iteration each); `ms_per_step` is the total time of '
+                         'the blocks / steps, every block is reported for the spread')
     ap.add_argument('--no-build-parity', action='store_true',
                     help='skip the CPU oracle reconstruction of the 16-view object (build_parity_at_full_size); the CPU pose '
                          'loop then runs on the GPU-built volume')
@@ -167,6 +171,42 @@ def launcher_selftest(a, rank, world):
     if rank == 0:
         print(json.dumps({'selftest': True, 'n_gpus': world, 'gpus_flag': a.gpus, 'ranks_seen': seen,
                           'allreduce_sum': t.item(), 'spawned_by_bench': os.environ.get('LF_BENCH_SPAWNED') == '1'}))
+
+
+def last_step_outputs(st):
+    """What the pose loop computed in its last iteration on `st` (GradientPoseEstimator.iterate), as host copies for N pose
+    hypotheses: the loss terms and camera-parameter gradients of the parameters it evaluated, the parameters after its
+    optimiser step, and the running top-N ranking that GradientPoseEstimator.estimate returns to its caller."""
+    params = st['params']                          # the engine's (N,10) leaf, or log_q / translation / viewport (modules)
+    out = {'camera_grad': torch.cat([p.grad for p in params], 1),
+           'camera_params_updated': torch.cat([p.detach() for p in params], 1)}
+    if 'pinned' in st:
+        # the engine's read-back of an iteration (losses[:, :6] | the parameters it evaluated), double-buffered by step parity
+        host = st['pinned'][(st['step'] - 1) & 1]
+        out['losses'] = host[:, :6]                # depth, ov_depth, iou, mask, weighted total, latent
+        out['camera_params'] = host[:, 6:]
+    ranked = st['ranking']
+    out['ranking_loss'] = torch.tensor([r[1] for r in ranked], dtype=torch.float64)
+    out['ranking_step'] = torch.tensor([r[2] for r in ranked], dtype=torch.float64)
+    out['ranking_log_quaternion'] = torch.cat([r[0].log_quaternion for r in ranked])
+    out['ranking_translation'] = torch.cat([r[0].translation for r in ranked])
+    return {k: v.detach().to('cpu', copy=True).numpy() for k, v in out.items()}
+
+
+def write_outputs(dirname, arrays, limit=64 << 20):
+    """DIR/<name>.npy for every array: float32 / float64 only, at most `limit` bytes in all."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v) for k, v in arrays.items()}
+    bad = [k for k, v in arrays.items() if v.dtype not in (np.float32, np.float64)]
+    if bad:
+        raise ValueError(f'bench.py: --dump-outputs writes float32 / float64 only: {bad}')
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        raise ValueError(f'bench.py: --dump-outputs: {total} bytes exceed the {limit}-byte limit')
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + '.npy'), v)
+    return sorted(arrays), total
 
 
 def cpu_baseline(cks, z_obj_gpu_cpu, ref_data, target_data, init, cfg, iters, build):
@@ -638,6 +678,8 @@ def main():
     a = parse(argv)
     if a.gpus < 1:
         raise SystemExit('bench.py: --gpus must be >= 1')
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit('bench.py: --steps must be >= 1 and --warmup >= 0')
     if a.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # no launcher: bench.py IS the launcher
         sys.exit(launch_ranks(a, argv))
@@ -724,22 +766,25 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed_loop(est_, st_, events=True):
-        """W warm-up iterations, then `--repeats` blocks of EXACTLY K iterations, each bracketed by barrier + synchronize
-        and reduced with MAX over the ranks.  Returns (median block time, all block times, the kernel events of all blocks)."""
+    def timed_loop(est_, st_, events=True, outputs=None):
+        """W warm-up iterations, then EXACTLY K = --steps timed iterations in `--repeats` back-to-back blocks, each bracketed
+        by barrier + synchronize and reduced with MAX over the ranks.  Returns (total time of the blocks, [(block time,
+        iterations)], the kernel events of all blocks).  `outputs` (a dict) receives what the last timed iteration computed."""
         for _ in range(a.warmup):
             est_.iterate(st_)
+        nb = max(1, min(a.repeats, a.steps))
+        sizes = [a.steps // nb + (1 if i < a.steps % nb else 0) for i in range(nb)]
         blocks, timer_ = [], []
         # HIP events inside the timed region only around the DOMINANT kernel, the one `roofline` reports (an event pair costs
         # ~4.6 us of dispatch gap: seven pairs per iteration were 0.6 % of it); the other heavy kernels of `roofline_iter`
         # are timed in one extra, untimed block of the same K iterations behind the timed blocks
         dominant = {'conv3d_c16_wino', 'conv3d_c16_split', 'conv3d_c16_wino_split', f'conv3x3_3d_{C}x{C}'}
         ops.KERNEL_TIMER_TAGS = dominant
-        for _rep in range(max(1, a.repeats)):
+        for k_ in sizes:
             barrier()
             ops.KERNEL_TIMER = [] if events else None
             t0_ = time.perf_counter()
-            for _ in range(a.steps):
+            for _ in range(k_):
                 est_.iterate(st_)
             barrier()
             el = time.perf_counter() - t0_
@@ -749,9 +794,12 @@ def main():
                 tt = torch.tensor([el], device=dev, dtype=torch.float64)
                 dist.all_reduce(tt, op=dist.ReduceOp.MAX)
                 el = tt.item()
-            blocks.append(el)
+            blocks.append((el, k_))
+        if outputs is not None:
+            outputs.update(last_step_outputs(st_))
+        total = sum(b for b, _ in blocks)
         if not events:
-            return sorted(blocks)[len(blocks) // 2], blocks, timer_
+            return total, blocks, timer_
         ops.KERNEL_TIMER_TAGS = {'conv3d_c16_wino_projfwd', 'conv3d_c16_wino_projbwd', 'resample_fwd', 'resample_bwd_coef',
                                  'factor_project_fwd', 'factor_project_bwd'}
         ops.KERNEL_TIMER = []
@@ -760,13 +808,19 @@ def main():
         torch.cuda.synchronize()
         timer_ += ops.KERNEL_TIMER
         ops.KERNEL_TIMER = None
-        return sorted(blocks)[len(blocks) // 2], blocks, timer_
+        return total, blocks, timer_
 
     def est_for_parity(z_):
         e_ = estimation.load_from_config(cfg, model, converge_patience=10 ** 6, conv_mode=a.conv_mode)
         return e_.start(z_, target, init.zoom(None, model.input_size, model.camera_dist).to(dev))
 
-    elapsed, blocks, timer = timed_loop(est, st)
+    dumped = {} if a.dump_outputs else None
+    elapsed, blocks, timer = timed_loop(est, st, outputs=dumped)
+    dump = None
+    if dumped is not None and rank == 0:                   # rank 0's object, like the line
+        names, nbytes = write_outputs(a.dump_outputs, dumped)
+        dump = {'dir': a.dump_outputs, 'arrays': names, 'bytes': nbytes,
+                'what': f'the headline loop after its last timed iteration (iteration {a.warmup + a.steps - 1} from the seeded start)'}
     alt = None
     if a.conv_mode in ('fp32', 'winograd') and not a.no_alt and C == 16:
         # secondary line (never `value`): the same loop with the split-precision conv3d kernels
@@ -783,7 +837,7 @@ def main():
                             'error vs fp64 within the fp32 kernels\', '
                             'tests/test_engine_gpu.py::test_split_precision_conv_matches_fp32_and_fp64)',
                'value': world * a.steps / el2, 'unit': 'iters/s', 'ms_per_step': el2 / a.steps * 1e3,
-               'ms_per_step_blocks': [b / a.steps * 1e3 for b in blocks2],
+               'ms_per_step_blocks': [b / k * 1e3 for b, k in blocks2],
                'conv_avg_launch_ms': sum(d2) / max(len(d2), 1)}
         if d2:
             ms2 = alt['conv_avg_launch_ms']
@@ -986,11 +1040,12 @@ def main():
         'metric': f'pose-optim iters/sec (reconstruct+render+backward), {V} views, {S}^3 voxels',
         'value': value, 'unit': 'iters/s', 'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup,
         'ms_per_step': elapsed / a.steps * 1e3, 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
-        'timing': {'what': f'{len(blocks)} back-to-back blocks of exactly {a.steps} iterations, each between barrier + '
-                           'synchronize, max over ranks; value = steps / MEDIAN block time',
-                   'ms_per_step_blocks': [b / a.steps * 1e3 for b in blocks],
-                   'gpu_timed_total_s': sum(blocks),
-                   'spread_pct': (max(blocks) - min(blocks)) / elapsed * 100.0},
+        'timing': {'what': f'exactly {a.steps} timed iterations in {len(blocks)} back-to-back block(s) of '
+                           f'{[k for _, k in blocks]} iterations, each between barrier + synchronize, max over ranks; '
+                           'value = steps / total block time',
+                   'ms_per_step_blocks': [b / k * 1e3 for b, k in blocks],
+                   'gpu_timed_total_s': elapsed,
+                   'spread_pct': (max(b / k for b, k in blocks) - min(b / k for b, k in blocks)) / (elapsed / a.steps) * 100.0},
         'rccl': rccl,
         'dtype': 'f32' if a.conv_mode in ('fp32', 'winograd') else 'f32 (conv3d products split into 3 f16 MFMAs, fp32 accumulate)', 'data': 'synthetic (SYN(S,C) random-init weights, synthetic observations)',
         'config': {'workload': f'SYN({S},{C}) latent volume, {V} reference views, adam_quick pose loop, '
@@ -1089,6 +1144,8 @@ def main():
         out['pipelined_gru_build'] = pipelined
     if hyp is not None:
         out['hypothesis_sharded_one_object'] = hyp
+    if dump is not None:
+        out['dump_outputs'] = dump
     # LAST in the line (the driver keeps the line's tail): every secondary claim of DESIGN.md in one compact object
     def dig(d, *ks):
         for k_ in ks:
