@@ -308,6 +308,30 @@ int lf_wino_fused_gemm(const float* V, const float* U2, const float* bias, float
                        int dims, int N, int D, int H, int W, int Cin, int Cout, float he, unsigned flags, float slope,
                        void* stream);
 
+/* Split-precision ("f16x3") form of the 3-D wide Winograd convolution: the per-frequency products on
+ * v_mfma_f32_16x16x32_f16, each fp32 product formed from three f16 products of hi / lo halves
+ * (a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi, fp32 accumulation); otherwise the contract of lf_wino_fused_gemm for dims = 3.
+ * Replaces Equalized.forward + LeakyReLU of modules/equalized.py:57-64, blocks.py:152-158 for >= 64-channel 3-D layers.
+ * Split operands are stored as records of 32 channels, [32 hi halfs][32 lo halfs] (128 B), CinP = lf_wino_f16x3_cin_padded(Cin)
+ * channels per row (zero padded).
+ *   lf_wino3d_input_transform_f16x3: x channels-last [N][D][H][W][C] -> V [64][T][CinP/32][2][32] halfs (T = lf_wino3d_tiles),
+ *     the fp32 transform of lf_wino3d_input_transform scaled by 2^eV, then split.  eV: 8 * amax * 2^eV in [2^11, 2^12) with
+ *     amax = the maximum over the slots of amax_in (an LF_AMAX_FLOATS buffer holding a bound of max|x|, read on the device);
+ *     amax_in = NULL: eV = 0.
+ *   lf_wino_fused_f16x3_gemm: U2 [64][CoutP][CinP/32][2][32] halfs = the Winograd weights times 2^eU, split (host-packed,
+ *     CoutP = lf_wino_fused_cout_padded(Cout)); amax_in: the buffer the transform read.  y = epilogue(he 2^-(eU+eV) M) with
+ *     flags LF_EPI_LRELU | LF_OUT_DEPTH_INNER as for lf_wino_fused_gemm; data gradient with transposed / flipped packs,
+ *     flags = 0, bias = NULL.  amax_out (may be NULL, zero-initialised by the caller): receives max|y|.  Small problems are
+ *     split over the frequencies into `scratch` (lf_wino_fused_f16x3_scratch_bytes(...) bytes, 0 = no split) and summed in a
+ *     fixed order.  Returns LF_EINVAL for a NULL operand, Cin / Cout not multiples of 4 or bad flags, LF_ENOSPC for missing
+ *     or short scratch; nothing is launched then. */
+int lf_wino_f16x3_cin_padded(int Cin);
+int lf_wino3d_input_transform_f16x3(const float* x, const float* amax_in, void* V, int N, int D, int H, int W, int C, void* stream);
+size_t lf_wino_fused_f16x3_scratch_bytes(int N, int D, int H, int W, int Cout);
+int lf_wino_fused_f16x3_gemm(const void* V, const void* U2, int eU, const float* amax_in, const float* bias, float* y,
+                             float* amax_out, void* scratch, size_t scratch_bytes, int N, int D, int H, int W, int Cin, int Cout,
+                             float he, unsigned flags, float slope, void* stream);
+
 /* 2-D counterpart, F(2x2,3x3): V [16][T][Cin], T = lf_wino2d_tiles(N, H, W), f = b*4 + c (y, x). */
 long lf_wino2d_tiles(int N, int H, int W);
 int lf_wino2d_input_transform(const float* x, float* V, int N, int H, int W, int C, void* stream);
@@ -554,6 +578,10 @@ int lf_pixelnorm_fwd(const float* x, float* y, float* norm_out, long rows, int C
  * rows x C, channels-last; in place (gp == gy) allowed. */
 int lf_epilogue_bwd(const float* gy, const float* y, const float* norm, float* gp,
                     long rows, int C, unsigned flags, float slope, void* stream);
+/* The same, also publishing max|gp| into amax_out (zero-initialised LF_AMAX_FLOATS buffer; order-independent atomic max):
+ * the input bound of a lf_wino3d_input_transform_f16x3 data-gradient launch.  y, gy, gp, amax_out must not be NULL. */
+int lf_epilogue_bwd_amax(const float* gy, const float* y, const float* norm, float* gp,
+                         long rows, int C, unsigned flags, float slope, float* amax_out, void* stream);
 
 /* Block-end rescale by exactly x2 (up = 1) or x0.5 (up = 0): nearest (linear = 0) or bi-/tri-linear
  * with align_corners=False (linear = 1) = Interpolate / F.interpolate(scale_factor=...) of

@@ -67,6 +67,11 @@ SIGNATURES = {
     'lf_wino_fused_cout_padded': (c_int, [c_int]),
     'lf_wino_fused_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'lf_wino_fused_gemm': (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_uint, c_float, P]),
+    'lf_wino_f16x3_cin_padded': (c_int, [c_int]),
+    'lf_wino3d_input_transform_f16x3': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_wino_fused_f16x3_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'lf_wino_fused_f16x3_gemm': (c_int, [P, P, c_int, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
+                                         c_float, c_uint, c_float, P]),
     'lf_wino2d_tiles': (c_long, [c_int, c_int, c_int]),
     'lf_wino2d_input_transform': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     'lf_gru_stage_a': (c_int, [P, P, c_int, P, P, P, c_long, c_int, c_int, c_int, P]),
@@ -116,6 +121,7 @@ SIGNATURES = {
     'lf_conv_bwd_weight_bf16_io': (c_int, [P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P]),
     'lf_pixelnorm_fwd': (c_int, [P, P, P, c_long, c_int, c_float, P]),
     'lf_epilogue_bwd': (c_int, [P, P, P, P, c_long, c_int, c_uint, c_float, P]),
+    'lf_epilogue_bwd_amax': (c_int, [P, P, P, P, c_long, c_int, c_uint, c_float, P, P]),
     'lf_epilogue_bwd_c16_scratch_bytes': (c_size_t, [c_long]),
     'lf_epilogue_bwd_c16': (c_int, [P, P, P, P, P, P, c_size_t, c_long, c_uint, c_float, c_int, P]),
     'lf_resample3d_fwd_io': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),

@@ -19,8 +19,9 @@ template <int MODE>
 __global__ void __launch_bounds__(256) rows_vec4_kernel(
     const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ nrm_in,
     float* __restrict__ out, float* __restrict__ nrm_out, long rows, int C, int lpr,
-    unsigned flags, float slope, float eps) {
+    unsigned flags, float slope, float eps, float* __restrict__ amax_out) {
   const int rpb = 256 / lpr;                              // rows per block-iteration
+  float am = 0.f;                                         // MODE 1: max |gp| of this lane (amax_out)
   const int q = threadIdx.x % lpr, slot = threadIdx.x / lpr;
   const long iters = (rows + (long)gridDim.x * rpb - 1) / ((long)gridDim.x * rpb);
   for (long it = 0; it < iters; ++it) {
@@ -53,8 +54,17 @@ __global__ void __launch_bounds__(256) rows_vec4_kernel(
 #pragma unroll
         for (int e = 0; e < 4; ++e) g[e] = vb[e] > 0.f ? g[e] : g[e] * slope;
       }
-      if (live) *(f32x4*)(out + row * C + q * 4) = g;
+      if (live) {
+        *(f32x4*)(out + row * C + q * 4) = g;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) am = fmaxf(am, fabsf(g[e]));
+      }
     }
+  }
+  if (MODE == 1 && amax_out != nullptr) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o, 64));
+    lf_amax_publish(amax_out, am, threadIdx.x & 63);
   }
 }
 
@@ -63,8 +73,9 @@ template <int MODE>
 __global__ void __launch_bounds__(256) rows_wave_kernel(
     const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ nrm_in,
     float* __restrict__ out, float* __restrict__ nrm_out, long rows, int C,
-    unsigned flags, float slope, float eps) {
+    unsigned flags, float slope, float eps, float* __restrict__ amax_out) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float am = 0.f;
   for (long row = (long)blockIdx.x * 4 + wave; row < rows; row += (long)gridDim.x * 4) {
     const float* pa = a + row * C;
     const float* pb = (MODE == 1) ? b + row * C : nullptr;
@@ -88,8 +99,14 @@ __global__ void __launch_bounds__(256) rows_wave_kernel(
         if (flags & LF_EPI_PIXELNORM) g = (g - yv * dot) / r;
         if (flags & LF_EPI_LRELU) g = yv > 0.f ? g : g * slope;
         out[row * C + c] = g;
+        am = fmaxf(am, fabsf(g));
       }
     }
+  }
+  if (MODE == 1 && amax_out != nullptr) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) am = fmaxf(am, __shfl_xor(am, o, 64));
+    lf_amax_publish(amax_out, am, lane);
   }
 }
 
@@ -180,7 +197,7 @@ bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 // (the fused lift kernels below use ld4 / bf16x4p, declared with the 16-channel epilogue kernel further down)
 template <int MODE>
 int launch_rows(const float* a, const float* b, const float* nrm_in, float* out, float* nrm_out,
-                long rows, int C, unsigned flags, float slope, float eps, hipStream_t s) {
+                long rows, int C, unsigned flags, float slope, float eps, hipStream_t s, float* amax_out = nullptr) {
   if (rows <= 0 || C <= 0) return LF_EINVAL;
   const bool vec = (C % 4 == 0) && pow2(C / 4) && (C / 4) <= 64 && lf_aligned16(a) && lf_aligned16(out) &&
                    (MODE == 0 || lf_aligned16(b));
@@ -189,12 +206,12 @@ int launch_rows(const float* a, const float* b, const float* nrm_in, float* out,
     const long blocks = (rows + rpb - 1) / rpb;
     const unsigned grid = (unsigned)(blocks < 16384 ? blocks : 16384);
     hipLaunchKernelGGL((rows_vec4_kernel<MODE>), dim3(grid), dim3(256), 0, s, a, b, nrm_in, out, nrm_out, rows, C, lpr,
-                       flags, slope, eps);
+                       flags, slope, eps, amax_out);
   } else {
     const long blocks = (rows + 3) / 4;
     const unsigned grid = (unsigned)(blocks < 16384 ? blocks : 16384);
     hipLaunchKernelGGL((rows_wave_kernel<MODE>), dim3(grid), dim3(256), 0, s, a, b, nrm_in, out, nrm_out, rows, C,
-                       flags, slope, eps);
+                       flags, slope, eps, amax_out);
   }
   return lf_launch_status();
 }
@@ -398,6 +415,15 @@ extern "C" int lf_epilogue_bwd(const float* gy, const float* y, const float* nor
   lf_clear_error();
   if ((flags & LF_EPI_PIXELNORM) && norm == nullptr) return LF_EINVAL;
   return launch_rows<1>(gy, y, norm, gp, nullptr, rows, C, flags, slope, 0.f, (hipStream_t)stream);
+}
+
+// lf_epilogue_bwd that also publishes max|gp| into amax_out (the input bound of a split-precision data-gradient launch)
+extern "C" int lf_epilogue_bwd_amax(const float* gy, const float* y, const float* norm, float* gp, long rows, int C,
+                                    unsigned flags, float slope, float* amax_out, void* stream) {
+  lf_clear_error();
+  if (gy == nullptr || y == nullptr || gp == nullptr || amax_out == nullptr) return LF_EINVAL;
+  if ((flags & LF_EPI_PIXELNORM) && norm == nullptr) return LF_EINVAL;
+  return launch_rows<1>(gy, y, norm, gp, nullptr, rows, C, flags, slope, 0.f, (hipStream_t)stream, amax_out);
 }
 
 extern "C" size_t lf_epilogue_bwd_c16_scratch_bytes(long rows) {

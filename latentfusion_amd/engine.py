@@ -18,6 +18,8 @@ Numerically it is the same computation as Photographer.decode + default_pose_los
 (reference recon/models.py:397-505, pose/estimation.py:70-118); tests/test_engine_gpu.py checks it
 against the module path and against the reference's golden loop trace.
 """
+import math
+
 import torch
 
 from . import _lib, ops
@@ -141,7 +143,9 @@ class RenderLoopEngine:
         """conv_mode selects the kernels of the 16->16 camera-block convolutions:
         'fp32'     direct implicit-GEMM on the fp32 MFMA (works for every channel count);
         'winograd' F(2x2x2,3x3x3) minimal filtering, all-fp32 arithmetic (fp32 MFMA + fp32 transforms);
-        'f16x3'    direct, each fp32 product from three f16 MFMAs with fp32 accumulation (documented preset: bench `alt`);
+        'f16x3'    each fp32 product from three f16 MFMAs with fp32 accumulation: on 16->16 blocks the direct kernel
+                   (documented preset: bench `alt`), on wide (>= 64-channel) blocks the F(2x2x2,3x3x3) Winograd GEMM
+                   lf_wino_fused_f16x3_gemm for every camera-block convolution and data gradient;
         'auto'     (default) 'winograd' when the blocks are 16->16 or >= 64 channels wide, else 'fp32'.
         All stay within the fp32 kernel's distance of an fp64 reference (tests/test_engine_gpu.py).
         fuse_projection: None = the default (factor projection forward fused into the last block's Winograd launch where the
@@ -180,24 +184,35 @@ class RenderLoopEngine:
                                            and w.shape[1] % 4 == 0 for w, *_ in self.convs)
         if conv_mode == 'auto':
             conv_mode = 'winograd' if (c16 or wide) else 'fp32'
-        if conv_mode not in ('fp32', 'winograd') and not c16:
-            raise NotImplementedError(f'{conv_mode} mode is implemented for 16->16 camera blocks')
+        if conv_mode == 'f16x3' and not (c16 or wide):
+            raise NotImplementedError('f16x3 mode is implemented for 16->16 and wide (>= 64 channel) camera blocks')
         if conv_mode == 'winograd' and not (c16 or wide):
             raise NotImplementedError('winograd mode needs 16->16 or wide (>= 64 channel) camera blocks')
         self.conv_mode = conv_mode
-        self.split = self.wino = self.wgemm = None
+        self.split = self.wino = self.wgemm = self.wgemm_x = None
         if conv_mode == 'winograd' and not c16:
             # wide blocks (released model: 256 -> 256 on 16^3): Winograd input transform + the fused fp32-MFMA GEMM /
             # output transform / epilogue kernel (lf_wino_fused_gemm)
             self.wgemm = [w for w, *_ in self.convs]            # packs are cached on the parameters (ops.wide_conv)
-        if conv_mode == 'f16x3':
+        if conv_mode == 'f16x3' and not c16:
+            # wide blocks on the split-precision Winograd GEMM (ops.wide_conv_f16x3): the weights' scale is chosen at packing,
+            # the inputs' from a bound held in a device buffer -- the first block reads the resampled volume, a convex
+            # combination of z (|x| <= max|z|), every later one a PixelNorm output (|x| <= sqrt(Cin)); gradients' bounds
+            # are measured where they are produced (ops.epilogue_bwd_amax)
+            self.wgemm_x = [w for w, *_ in self.convs]
+            self.wgemm_x_amax = [ops.amax_buffer(self.z.abs().amax(), dev)] + [
+                ops.amax_buffer(torch.tensor(math.sqrt(w.shape[1])), dev) for w, *_ in self.convs[1:]]
+            for w, *_ in self.convs:                            # packed now (cached on the parameter), not inside the first call
+                ops._pk(w, 'wxf', lambda w_: ops.pack_conv_wino_fused_f16x3(w_))
+                ops._pk(w, 'wxb', lambda w_: ops.pack_conv_wino_fused_f16x3(w_, transpose=True))
+        elif conv_mode == 'f16x3':
             self.split = [(ops.pack_conv3d_c16_split(w), ops.pack_conv3d_c16_split(w, transpose=True)) for w, *_ in self.convs]
         elif conv_mode == 'winograd' and c16:
             self.wino = [(ops.pack_conv3d_c16_wino(w), ops.pack_conv3d_c16_wino(w, transpose=True)) for w, *_ in self.convs]
         # 'sum' projection / occlusion module: the tail between the camera blocks and the 2-D decoder runs through the
         # depth-column ops (autograd functions over lf_column_*), the rest of the iteration stays explicit
         self.generic_tail = photographer.projection_type != 'factor' or photographer.occlusion_module is not None
-        if self.generic_tail and self.split is not None:
+        if self.generic_tail and (self.split is not None or self.wgemm_x is not None):
             raise NotImplementedError("the split-precision conv modes drive the plain 'factor' renderer only")
         C, D = (self.convs[-1][0].shape[0] if self.convs else self.C), self.S
         # the occlusion module on this library's kernels, sequenced here like the camera blocks (round 5); None: its
@@ -322,6 +337,8 @@ class RenderLoopEngine:
     def _conv_fwd(self, li, x, flags, depth_inner=False):
         """Forward of camera-block convolution `li`: (y, norm, (zp, pnorm) when the factor projection rode along, else None)."""
         w, b, he, wp, _wt = self.convs[li]
+        if self.wgemm_x is not None:
+            return ops.wide_conv_f16x3(x, self.wgemm_x[li], b, he, flags, depth_inner=depth_inner, amax_in=self.wgemm_x_amax[li]) + (None,)
         if depth_inner:
             return ops.wide_conv(x, self.wgemm[li], b, he, flags, depth_inner=True) + (None,)
         if self.split is not None:
@@ -345,6 +362,19 @@ class RenderLoopEngine:
         if self.wino is not None:
             return ops.conv3d_c16_wino(g, self.wino[i][1], None, he, 0, prev=prev)[0]
         return ops.conv3x3_bwd_data(g, wt, w.shape[1], he, prev)
+
+    def _wide_bwd(self, i, g, acts, norms, flags):
+        """Data gradient of wide camera-block convolution `i` from d/d(its output) `g`: the LeakyReLU' / PixelNorm' pass, then the
+        transposed convolution (fp32 Winograd GEMM, or the split-precision one with the pass measuring the gradient's bound)."""
+        w, _b, he, _wp, wt = self.convs[i]
+        if self.wgemm_x is not None:
+            amax = ops.amax_buffer(None, self.dev)
+            gpre = ops.epilogue_bwd_amax(g, acts[i + 1], norms[i], flags, amax)
+            return ops.wide_conv_f16x3(gpre, self.wgemm_x[i], None, he, 0, transpose=True, amax_in=amax)[0]
+        gpre = ops._epilogue_bwd(g, acts[i + 1], norms[i], flags)
+        if self.wgemm is not None:
+            return ops.wide_conv(gpre, self.wgemm[i], None, he, 0, transpose=True)[0]
+        return ops._conv3x3_raw(gpre, wt, None, w.shape[1], he, 0, False)[0]
 
     def _tail_leaf(self, act_leaf, zs_leaf, zp_leaf):
         """The tensor autograd differentiates the 2-D tail back to: the projected latent (factor projection), the scaled volume
@@ -524,7 +554,7 @@ class RenderLoopEngine:
         # wide blocks, ranking only (the released architecture under the cross-entropy search): the last block writes its output
         # depth-innermost, so that the factor projection K = D * C -> C2 below is ONE row-major GEMM for the library
         # (128 renders: 32768 x 4096 x 256, 0.5 ms on hipBLASLt's fp32 MFMA kernel against 1.27 ms of lf_conv1x1_fwd's K slices)
-        proj_gemm = (self.PROJ_GEMM and self.wgemm is not None and not need_grad and self.occ is None and not self.generic_tail
+        proj_gemm = (self.PROJ_GEMM and (self.wgemm is not None or self.wgemm_x is not None) and not need_grad and self.occ is None and not self.generic_tail
                      and self.proj is not None and 'fwd' not in self.fuse_projection)
         for li_ in range(len(self.convs)):
             y, nrm, rode = self._conv_fwd(li_, acts[-1], flags, depth_inner=proj_gemm and li_ == len(self.convs) - 1)
@@ -727,12 +757,7 @@ class RenderLoopEngine:
                     g = self._conv_bwd(i, g, prev, None)
             else:
                 for i in range(nconv - 1, -1, -1):
-                    w, b, he, _wp, wt = self.convs[i]
-                    gpre = ops._epilogue_bwd(g, acts[i + 1], norms[i], flags)
-                    if self.wgemm is not None:
-                        g, _ = ops.wide_conv(gpre, self.wgemm[i], None, he, 0, transpose=True)
-                    else:
-                        g, _ = ops._conv3x3_raw(gpre, wt, None, w.shape[1], he, 0, False)
+                    g = self._wide_bwd(i, g, acts, norms, flags)
             return self._finish_backward(g, g_cf, cf20, jac, n, grad_scale, losses)
         gp = gp_explicit if (explicit and gp_explicit is not None) else ops._epilogue_bwd(ops.cl(g_zp), zp, pnorm, flags)
         fused_pb = self._proj_bwd_fused(gp, acts, norms, flags) if (fuse and nconv) else None
@@ -758,12 +783,7 @@ class RenderLoopEngine:
             ops._conv1x1_raw(gp, ppack_t, None, n, S * S, cout, 1, S * S * cout, 0, S * Cl, g, phe, 0,
                              yaddr=(S * S * S * Cl, Cl, Cl, S * S * Cl))
             for i in range(nconv - 1, -1, -1):
-                w, b, he, _wp, wt = self.convs[i]
-                gpre = ops._epilogue_bwd(g, acts[i + 1], norms[i], flags)
-                if self.wgemm is not None:
-                    g, _ = ops.wide_conv(gpre, self.wgemm[i], None, he, 0, transpose=True)
-                else:
-                    g, _ = ops._conv3x3_raw(gpre, wt, None, w.shape[1], he, 0, False)
+                g = self._wide_bwd(i, g, acts, norms, flags)
         return self._finish_backward(g, g_cf, cf20, jac, n, grad_scale, losses)
 
     def _finish_backward(self, g, g_cf, cf20, jac, n, grad_scale, losses):

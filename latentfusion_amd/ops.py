@@ -470,6 +470,77 @@ def wide_conv(x, weight, bias, he, flags, transpose=False, depth_inner=False):
     return experimental.conv3d_wino_gemm(x, U, bias, he, flags)
 
 
+def pack_conv_wino_fused_f16x3(weight, transpose=False):
+    """[Cout,Cin,3,3,3] -> (U2s, eU) for lf_wino_fused_f16x3_gemm: U2s [64][CoutP][CinP/32][2][32] f16, the Winograd weights
+    of pack_conv_wino_fused (fp64) times 2^eU, split into hi = f16(u) and lo = f16(u - hi) per 32-channel record
+    (CoutP = lf_wino_fused_cout_padded(Cout), CinP = lf_wino_f16x3_cin_padded(Cin), zero padded); eU puts max|U| 2^eU in
+    [2^11, 2^12)."""
+    w = weight.detach()
+    if transpose:
+        w = w.transpose(0, 1).flip(dims=(2, 3, 4))
+    assert w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3)
+    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
+    cout, cin = w.shape[0], w.shape[1]
+    U = torch.einsum('ai,bj,ck,omijk->abcom', G, G, G, w.double()).reshape(64, cout, cin)
+    amax = U.abs().max().item()
+    eU = 12 - math.frexp(amax)[1] if amax > 0 else 0
+    coutp, cinp = (cout + 63) // 64 * 64, (cin + 31) // 32 * 32          # lf_wino_fused_cout_padded / lf_wino_f16x3_cin_padded
+    Us = torch.zeros(64, coutp, cinp, dtype=torch.float64, device=w.device)
+    Us[:, :cout, :cin] = torch.ldexp(U, torch.tensor(float(eU), dtype=torch.float64, device=w.device))
+    hi = Us.half()
+    lo = (Us - hi.double()).half()
+    out = torch.stack((hi.reshape(64, coutp, cinp // 32, 32), lo.reshape(64, coutp, cinp // 32, 32)), dim=3)
+    return out.contiguous(), eU
+
+
+def wide_conv_f16x3(x, weight, bias, he, flags, transpose=False, depth_inner=False, amax_in=None, amax_out=None):
+    """Wide 3-D 3x3x3 convolution (or its data gradient, transpose=True) with three-term f16 products
+    (lf_wino3d_input_transform_f16x3 + lf_wino_fused_f16x3_gemm); PixelNorm as a pass over the output, as conv_wino_fused.
+    amax_in: max-abs buffer (amax_buffer) holding a bound of max|x| -- the input's power-of-two scale is derived from it on the
+    device; None: measured here from x.  amax_out (zeroed amax_buffer, optional): receives max|y| before any PixelNorm.
+    Returns (y, norm or None); depth_inner: y as a plain (N, H, W, D, cout) tensor (LF_OUT_DEPTH_INNER)."""
+    L = _lib.lib()
+    assert x.dim() == 5
+    cout = weight.shape[1] if transpose else weight.shape[0]
+    U2, eU = _pk(weight, 'wxb' if transpose else 'wxf', lambda w: pack_conv_wino_fused_f16x3(w, transpose=transpose))
+    N, cin, D, H, W = x.shape
+    if amax_in is None:
+        amax_in = amax_buffer(x.detach().abs().amax(), x.device)
+    T = L.lf_wino3d_tiles(N, D, H, W)
+    V = torch.empty(64, T, L.lf_wino_f16x3_cin_padded(cin) * 2, device=x.device, dtype=torch.float16)
+    with _timed('wino3d_input_f16x3'):
+        check(L.lf_wino3d_input_transform_f16x3(_ptr(x), _ptr(amax_in), _ptr(V), N, D, H, W, cin, _stream()),
+              'lf_wino3d_input_transform_f16x3')
+    if depth_inner:
+        y = torch.empty((N, H, W, D, cout), device=x.device, dtype=torch.float32)
+    else:
+        y = empty_cl((N, cout, D, H, W), x.device)
+    nscr = L.lf_wino_fused_f16x3_scratch_bytes(N, D, H, W, cout)
+    scr = torch.empty(nscr // 4, device=x.device, dtype=torch.float32) if nscr else None
+    with _timed('wino3d_fused_f16x3'):
+        check(L.lf_wino_fused_f16x3_gemm(_ptr(V), _ptr(U2), eU, _ptr(amax_in), _ptr(bias) if bias is not None else None, _ptr(y),
+                                         _ptr(amax_out) if amax_out is not None else None,
+                                         _ptr(scr, True) if scr is not None else None, nscr, N, D, H, W, cin, cout, he,
+                                         (flags & LF_EPI_LRELU) | (_lib.LF_OUT_DEPTH_INNER if depth_inner else 0), SLOPE,
+                                         _stream()), 'lf_wino_fused_f16x3_gemm')
+    del V
+    norm = None
+    if flags & LF_EPI_PIXELNORM:
+        norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32)
+        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * D * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+    return y, norm
+
+
+def epilogue_bwd_amax(gy, y, norm, flags, amax_out):
+    """_epilogue_bwd (LeakyReLU' / PixelNorm' of a layer) that also publishes max|gp| into amax_out (lf_epilogue_bwd_amax)."""
+    L = _lib.lib()
+    rows = gy.numel() // gy.shape[1]
+    gp = torch.empty_like(gy, memory_format=torch.preserve_format)
+    check(L.lf_epilogue_bwd_amax(_ptr(gy), _ptr(y), _ptr(norm) if norm is not None else None, _ptr(gp), rows, gy.shape[1], flags,
+                                 SLOPE, _ptr(amax_out), _stream()), 'lf_epilogue_bwd_amax')
+    return gp
+
+
 def _wino_gemm_ok(x, weight):
     """Wide 2-D / 3-D 3x3 convolutions where the transforms amortise over the channels."""
     return (x.dim() == weight.dim() and x.dim() in (4, 5) and weight.shape[0] >= 64 and weight.shape[1] >= 64
