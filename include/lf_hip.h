@@ -336,6 +336,26 @@ int lf_wino_fused_f16x3_gemm(const void* V, const void* U2, int eU, const float*
 long lf_wino2d_tiles(int N, int H, int W);
 int lf_wino2d_input_transform(const float* x, float* V, int N, int H, int W, int C, void* stream);
 
+/* Split-precision ("f16x3") form of the 2-D wide Winograd convolution, F(2x2,3x3): the 2-D decoder's >= 64-channel layers
+ * (Equalized.forward + LeakyReLU of modules/equalized.py:57-64, blocks.py:152-158, 2-D).  Products and records as for
+ * lf_wino_fused_f16x3_gemm; the input scale is chosen PER TILE by the transform, not from a bound held on the device.
+ *   lf_wino2d_input_transform_f16x3: x channels-last [N][H][W][C] -> V [16][T][CinP/32][2][32] halfs (T = lf_wino2d_tiles,
+ *     CinP = lf_wino_f16x3_cin_padded(C), zero padded) and eV [T] ints: the fp32 transform of lf_wino2d_input_transform times
+ *     2^eV[t], eV[t] such that the tile's largest finite |V| times 2^eV[t] lies in [2^11, 2^12) (0 for an all-zero tile).
+ *     Non-finite inputs stay non-finite in exactly the frequencies they reach.  x, V 16-byte, eV 4-byte aligned.
+ *   lf_wino_fused2d_f16x3_gemm: U2 [16][CoutP][CinP/32][2][32] halfs = the Winograd weights times 2^eU, split (host-packed,
+ *     CoutP = lf_wino_fused_cout_padded(Cout)); V, eV from the transform.  y [N][H][W][Cout] = epilogue(2^-eV[t] he 2^-eU M)
+ *     with flags 0 or LF_EPI_LRELU (PixelNorm: lf_pixelnorm_fwd afterwards); data gradient with transposed / flipped packs,
+ *     flags = 0, bias = NULL.  Small problems are split over the frequencies into `scratch`
+ *     (lf_wino_fused2d_f16x3_scratch_bytes(...) bytes, 0 = no split) and summed in a fixed order.
+ *   Both return LF_EINVAL for a NULL operand, a size < 1, Cin / Cout not multiples of 4 or bad flags, LF_EALIGN for a
+ *   misaligned buffer, LF_ENOSPC for missing or short scratch; nothing is launched then. */
+int lf_wino2d_input_transform_f16x3(const float* x, void* V, int* eV, int N, int H, int W, int C, void* stream);
+size_t lf_wino_fused2d_f16x3_scratch_bytes(int N, int H, int W, int Cout);
+int lf_wino_fused2d_f16x3_gemm(const void* V, const int* eV, const void* U2, int eU, const float* bias, float* y, void* scratch,
+                               size_t scratch_bytes, int N, int H, int W, int Cin, int Cout, float he, unsigned flags, float slope,
+                               void* stream);
+
 /* Gate arithmetic of the convolutional GRU fuser, inference path (modules/gru.py:30-43; no tanh on the
  * candidate).  `rec` is the channels-last record [x | state] (rec_stride floats per voxel, state at
  * rec_off) that the gate convolutions read; upre / rpre = update / reset pre-activations, pre_stride floats

@@ -74,6 +74,10 @@ SIGNATURES = {
                                          c_float, c_uint, c_float, P]),
     'lf_wino2d_tiles': (c_long, [c_int, c_int, c_int]),
     'lf_wino2d_input_transform': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
+    'lf_wino2d_input_transform_f16x3': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    'lf_wino_fused2d_f16x3_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'lf_wino_fused2d_f16x3_gemm': (c_int, [P, P, P, c_int, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_float, c_uint,
+                                           c_float, P]),
     'lf_gru_stage_a': (c_int, [P, P, c_int, P, P, P, c_long, c_int, c_int, c_int, P]),
     'lf_gru_stage_b': (c_int, [P, P, P, P, P, c_long, c_int, c_int, c_int, P]),
     'lf_lstm_cell_fwd': (c_int, [P, P, P, P, c_long, c_int, P]),

@@ -118,19 +118,112 @@ __global__ void __launch_bounds__(256) wino3d_input_f16x3_kernel(const float* __
   }
 }
 
-// Workgroup shape: WM x WN waves, each owning BA x BB blocks of 16 couts x 16 tiles -- the 128 x 64 shape that the fp32 kernel
-// uses for the 128-render 256 -> 256 launch (8 waves, one workgroup per CU); smaller problems are split over the frequencies.
-// (One shape, and not a template: hipcc 7.2 emitted no host stub for the template form of this kernel.)
+// F(2x2,3x3) input transform of channels c .. c+3 of the 4 x 4 patch at (y0, x0): v[b*4 + c'] (the arithmetic of
+// wino2d_input_kernel, wino_gemm.hip, in fp32); live = false: zeros (channel padding of the record)
+__device__ __forceinline__ void wino2d_xform4(const float* __restrict__ xs, int y0, int x0, int H, int W, int C, int c, bool live,
+                                              f32x4 v[16]) {
+  f32x4 vx[4][4];
+#pragma unroll
+  for (int dy = 0; dy < 4; ++dy) {
+    const int yy = y0 + dy;
+    f32x4 d[4];
+#pragma unroll
+    for (int dx = 0; dx < 4; ++dx) {
+      const int xx = x0 + dx;
+      d[dx] = (live && (unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) ? *(const f32x4*)(xs + ((long)yy * W + xx) * C + c)
+                                                                                  : (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    vx[dy][0] = d[0] - d[2];
+    vx[dy][1] = d[1] + d[2];
+    vx[dy][2] = d[2] - d[1];
+    vx[dy][3] = d[1] - d[3];
+  }
+#pragma unroll
+  for (int b = 0; b < 4; ++b)
+#pragma unroll
+    for (int cc = 0; cc < 4; ++cc)
+      v[b * 4 + cc] = (b == 0) ? (vx[0][cc] - vx[2][cc]) : (b == 1) ? (vx[1][cc] + vx[2][cc])
+                    : (b == 2) ? (vx[2][cc] - vx[1][cc]) : (vx[1][cc] - vx[3][cc]);
+}
+
+// 2-D: one wave per tile.  The tile's input scale is its own: pass 1 takes the largest FINITE |V| of the tile over all
+// channels and frequencies (eV: that maximum times 2^eV in [2^11, 2^12); 0 for an all-zero tile) -- no bound has to be handed
+// over by a producer, and a tile of small values keeps its precision next to one of large values.  Non-finite values are
+// left out of the maximum and pass through as inf / NaN, so exactly the frequencies they reach become non-finite, as in the
+// fp32 kernel.  Pass 2 recomputes the transform (the patch is cache-hot), scales, splits and stores 8 channels per lane:
+// one 16-byte store of hi and one of lo.
+__global__ void __launch_bounds__(256) wino2d_input_f16x3_kernel(const float* __restrict__ x, _Float16* __restrict__ V,
+                                                                int* __restrict__ eVt, int H, int W, int C, int CP, int ty, int tx,
+                                                                long T) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long tile = (long)blockIdx.x * 4 + wave;
+  if (tile >= T) return;                                         // wave-uniform
+  long r = tile;
+  const int bx = (int)(r % tx); r /= tx;
+  const int by = (int)(r % ty);
+  const long n = r / ty;
+  const int y0 = 2 * by - 1, x0 = 2 * bx - 1;
+  const float* xs = x + n * H * W * C;
+  float m = 0.f;
+  for (int q = lane; q * 4 < C; q += 64) {
+    f32x4 v[16];
+    wino2d_xform4(xs, y0, x0, H, W, C, q * 4, true, v);
+#pragma unroll
+    for (int i = 0; i < 16; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float a = fabsf(v[i][e]);
+        m = a < __builtin_inff() ? fmaxf(m, a) : m;
+      }
+  }
+  m = wave_max(m);
+  int eV = 0;
+  if (m > 0.f) {
+    int ex;
+    frexpf(m, &ex);                                              // m = f 2^ex, f in [0.5, 1)
+    eV = 12 - ex;
+  }
+  if (lane == 0) eVt[tile] = eV;
+  for (int g = lane; g * 8 < CP; g += 64) {
+    f32x4 v0[16], v1[16];
+    wino2d_xform4(xs, y0, x0, H, W, C, g * 8, g * 8 < C, v0);
+    wino2d_xform4(xs, y0, x0, H, W, C, g * 8 + 4, g * 8 + 4 < C, v1);
+    _Float16* p = V + tile * CP * 2 + (g >> 2) * 64 + (g & 3) * 8;
+#pragma unroll
+    for (int f = 0; f < 16; ++f) {
+      h16x8 hi, lo;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float s = ldexpf(e < 4 ? v0[f][e] : v1[f][e - 4], eV);
+        hi[e] = (_Float16)s;
+        lo[e] = (_Float16)(s - (float)hi[e]);
+      }
+      *(h16x8*)(p + (long)f * T * CP * 2) = hi;
+      *(h16x8*)(p + (long)f * T * CP * 2 + 32) = lo;
+    }
+  }
+}
+
+// Workgroup shape: WM x WN waves, each owning BA x BB blocks of 16 couts x 16 tiles.  3-D: the 128 x 64 shape that the fp32
+// kernel uses for the 128-render 256 -> 256 launch (8 waves, one workgroup per CU); smaller problems are split over the
+// frequencies.  2-D (F(2x2,3x3), 4 output accumulators per block instead of 8): 128 x 128, or 64 x 128 when CoutP = 64.
+// The body is a template; every shape has its own NON-template __global__ entry point (hipcc 7.2 emitted no host stub for
+// a __global__ template of this kernel).
+//   eVt == nullptr (3-D): one input scale 2^eV from amax_in, osc = he 2^-(eU+eV).
+//   eVt != nullptr (2-D): per-tile input scale 2^eVt[tile] chosen by lf_wino2d_input_transform_f16x3; y = 2^-eVt[tile] (he 2^-eU M).
 constexpr int WM = 4, WN = 2, BA = 2, BB = 2;
 constexpr int NT = WM * BA * 16, MT = WN * BB * 16, NTHR = WM * WN * 64;
 constexpr int LDS_BYTES = NSTAGE * (NT + MT) * 128;
+constexpr int NT2 = 128, MT2 = 128, NT2S = 64, MT2S = 128;      // 2-D shapes: <2,4,2,2,4> and <2,2,4,2,2>
+constexpr int LDS2_BYTES = NSTAGE * (NT2 + MT2) * 128, LDS2S_BYTES = NSTAGE * (NT2S + MT2S) * 128;
 
-__global__ void __launch_bounds__(NTHR, 1) wino_fused_f16x3_kernel(
+template <int DIMS, int WM, int WN, int BA, int BB>
+__device__ __forceinline__ void f16x3_gemm_body(
     const _Float16* __restrict__ V, const _Float16* __restrict__ U2, const float* __restrict__ bias, float* __restrict__ y,
     long T, int tz, int ty, int tx, int D, int H, int W, int CinP, int Cout, int CoutP, float he, int eU,
-    const float* __restrict__ amax_in, unsigned flags, float slope, float* __restrict__ partial, long ysize,
-    float* __restrict__ amax_out) {
-  constexpr int F = 64, NO = 8;
+    const float* __restrict__ amax_in, const int* __restrict__ eVt, unsigned flags, float slope, float* __restrict__ partial,
+    long ysize, float* __restrict__ amax_out) {
+  constexpr int F = DIMS == 3 ? 64 : 16, NO = DIMS == 3 ? 8 : 4;
   constexpr int NTc = WM * BA * 16, MTc = WN * BB * 16, NW = WM * WN;
   constexpr int A_BYTES = NTc * 128, STAGE_BYTES = (NTc + MTc) * 128;
   constexpr int PA = NTc / 8, PB = MTc / 8;
@@ -265,7 +358,8 @@ __global__ void __launch_bounds__(NTHR, 1) wino_fused_f16x3_kernel(
       const int fc = f & 3, fb_ = (f >> 2) & 3, fa_ = (f >> 4) & 3;
 #pragma unroll
       for (int o = 0; o < NO; ++o) {
-        const float cf = at_coef(o & 1, fc) * at_coef((o >> 1) & 1, fb_) * at_coef((o >> 2) & 1, fa_);
+        float cf = at_coef(o & 1, fc) * at_coef((o >> 1) & 1, fb_);
+        if (DIMS == 3) cf *= at_coef((o >> 2) & 1, fa_);
         if (cf != 0.f) {
 #pragma unroll
           for (int a = 0; a < BA; ++a)
@@ -282,7 +376,7 @@ __global__ void __launch_bounds__(NTHR, 1) wino_fused_f16x3_kernel(
   }
 
   // ---- epilogue: he * 2^-(eU + eV), bias, LeakyReLU ----
-  const float osc = ldexpf(he, -(eU + v_scale_exp(amax_in, lane)));
+  const float osc = DIMS == 3 ? ldexpf(he, -(eU + v_scale_exp(amax_in, lane))) : ldexpf(he, -eU);
   float m = 0.f;
 #pragma unroll
   for (int b = 0; b < BB; ++b) {
@@ -291,8 +385,9 @@ __global__ void __launch_bounds__(NTHR, 1) wino_fused_f16x3_kernel(
     long r = tile;
     const int bx = (int)(r % tx); r /= tx;
     const int by = (int)(r % ty); r /= ty;
-    const int bz = (int)(r % tz);
-    const long n = r / tz;
+    const int bz = DIMS == 3 ? (int)(r % tz) : 0;
+    const long n = DIMS == 3 ? r / tz : r;
+    const int etile = DIMS == 3 ? 0 : eVt[tile];
 #pragma unroll
     for (int a = 0; a < BA; ++a) {
       const int co = n0 + wr * (BA * 16) + a * 16 + kg * 4;
@@ -301,25 +396,57 @@ __global__ void __launch_bounds__(NTHR, 1) wino_fused_f16x3_kernel(
       if (bias != nullptr) bv = *(const f32x4*)(bias + co);
 #pragma unroll
       for (int o = 0; o < NO; ++o) {
-        const int gx = 2 * bx + (o & 1), gy = 2 * by + ((o >> 1) & 1), gz = 2 * bz + ((o >> 2) & 1);
+        const int gx = 2 * bx + (o & 1), gy = 2 * by + ((o >> 1) & 1), gz = 2 * bz + (DIMS == 3 ? ((o >> 2) & 1) : 0);
         if (gx >= W || gy >= H || gz >= D) continue;
         const long vox = (flags & LF_OUT_DEPTH_INNER) ? ((n * H + gy) * W + gx) * D + gz : ((n * D + gz) * H + gy) * W + gx;
         if (partial != nullptr) {
           *(f32x4*)(partial + (long)blockIdx.z * ysize + vox * Cout + co) = Y[o][a][b];
           continue;
         }
-        f32x4 v = Y[o][a][b] * osc + bv;
+        f32x4 v = Y[o][a][b] * osc;
+        if (DIMS == 2) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] = ldexpf(v[e], -etile);              // exact (a power of two)
+        }
+        v += bv;
         if (flags & LF_EPI_LRELU) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], v[e] * slope);
         }
+        if (DIMS == 3) {
 #pragma unroll
-        for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(v[e]));
+          for (int e = 0; e < 4; ++e) m = fmaxf(m, fabsf(v[e]));
+        }
         *(f32x4*)(y + vox * Cout + co) = v;
       }
     }
   }
-  if (amax_out != nullptr) lf_amax_publish(amax_out, wave_max(m), lane);
+  if (DIMS == 3 && amax_out != nullptr) lf_amax_publish(amax_out, wave_max(m), lane);
+}
+
+__global__ void __launch_bounds__(NTHR, 1) wino_fused_f16x3_kernel(
+    const _Float16* __restrict__ V, const _Float16* __restrict__ U2, const float* __restrict__ bias, float* __restrict__ y,
+    long T, int tz, int ty, int tx, int D, int H, int W, int CinP, int Cout, int CoutP, float he, int eU,
+    const float* __restrict__ amax_in, unsigned flags, float slope, float* __restrict__ partial, long ysize,
+    float* __restrict__ amax_out) {
+  f16x3_gemm_body<3, WM, WN, BA, BB>(V, U2, bias, y, T, tz, ty, tx, D, H, W, CinP, Cout, CoutP, he, eU, amax_in, nullptr, flags, slope,
+                                     partial, ysize, amax_out);
+}
+
+__global__ void __launch_bounds__(512, 1) wino_fused2d_f16x3_kernel(
+    const _Float16* __restrict__ V, const _Float16* __restrict__ U2, const float* __restrict__ bias, float* __restrict__ y,
+    long T, int ty, int tx, int H, int W, int CinP, int Cout, int CoutP, float he, int eU, const int* __restrict__ eVt,
+    unsigned flags, float slope, float* __restrict__ partial, long ysize) {
+  f16x3_gemm_body<2, 4, 2, 2, 4>(V, U2, bias, y, T, 1, ty, tx, 1, H, W, CinP, Cout, CoutP, he, eU, nullptr, eVt, flags, slope, partial,
+                                 ysize, nullptr);
+}
+
+__global__ void __launch_bounds__(512, 1) wino_fused2d_f16x3_c64_kernel(
+    const _Float16* __restrict__ V, const _Float16* __restrict__ U2, const float* __restrict__ bias, float* __restrict__ y,
+    long T, int ty, int tx, int H, int W, int CinP, int Cout, int CoutP, float he, int eU, const int* __restrict__ eVt,
+    unsigned flags, float slope, float* __restrict__ partial, long ysize) {
+  f16x3_gemm_body<2, 2, 4, 2, 2>(V, U2, bias, y, T, 1, ty, tx, 1, H, W, CinP, Cout, CoutP, he, eU, nullptr, eVt, flags, slope, partial,
+                                 ysize, nullptr);
 }
 
 // y = epilogue(he 2^-(eU+eV) * sum_z partial[z] + bias), partials added in a fixed order
@@ -348,11 +475,40 @@ __global__ void __launch_bounds__(256) wino_fused_f16x3_finish_kernel(const f32x
   if (amax_out != nullptr) lf_amax_publish(amax_out, wave_max(m), lane);
 }
 
-int zsplit(long gx, int gy) {                                     // enough workgroups for one per CU
+// 2-D: y = epilogue(2^-eVt[tile] (he 2^-eU sum_z partial[z]) + bias), partials added in a fixed order
+__global__ void __launch_bounds__(256) wino_fused2d_f16x3_finish_kernel(const f32x4* __restrict__ partial, const float* __restrict__ bias,
+                                                                       f32x4* __restrict__ y, long n4, int zs, int c4, int H, int W,
+                                                                       int ty, int tx, float heU, const int* __restrict__ eVt,
+                                                                       unsigned flags, float slope) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  f32x4 acc = partial[i];
+  for (int z = 1; z < zs; ++z) acc += partial[i + z * n4];
+  const long p = i / c4;
+  const int gx = (int)(p % W), gy = (int)((p / W) % H);
+  const long n = p / ((long)W * H);
+  const int e = eVt[(n * ty + gy / 2) * tx + gx / 2];
+  f32x4 bv = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if (bias != nullptr) bv = *(const f32x4*)(bias + (i % c4) * 4);
+  f32x4 v = acc * heU;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) v[k] = ldexpf(v[k], -e);
+  v += bv;
+  if (flags & LF_EPI_LRELU) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], v[k] * slope);
+  }
+  y[i] = v;
+}
+
+int zsplit(long gx, int gy, int F = 64) {                        // enough workgroups for one per CU
   int zs = 1;
-  while (zs < 64 && gx * gy * zs < 256) zs <<= 1;
+  while (zs < F && gx * gy * zs < 256) zs <<= 1;
   return zs;
 }
+
+// 2-D workgroup shape: 64 x 128 for 64-channel outputs (no half-empty A blocks), else 128 x 128
+int nt2d(int CoutP) { return CoutP == 64 ? NT2S : NT2; }
 
 void tiles_of(int D, int H, int W, int& tz, int& ty, int& tx) { tz = (D + 1) / 2, ty = (H + 1) / 2, tx = (W + 1) / 2; }
 
@@ -418,5 +574,68 @@ extern "C" int lf_wino_fused_f16x3_gemm(const void* V, const void* U2, int eU, c
   const long n4 = ysize / 4;
   hipLaunchKernelGGL(wino_fused_f16x3_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const f32x4*)partial, bias,
                      (f32x4*)y, n4, zs, Cout / 4, he, eU, amax_in, flags & LF_EPI_LRELU, slope, amax_out);
+  return lf_launch_status();
+}
+
+// ---- 2-D, F(2x2,3x3): decoder layers (modules/blocks.py:152-158 with modules/equalized.py:57-64, 2-D) ----
+extern "C" int lf_wino2d_input_transform_f16x3(const float* x, void* V, int* eV, int N, int H, int W, int C, void* stream) {
+  lf_clear_error();
+  if (x == nullptr || V == nullptr || eV == nullptr || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 3)) return LF_EINVAL;
+  if (!lf_aligned16(x) || !lf_aligned16(V) || ((uintptr_t)eV & 3)) return LF_EALIGN;
+  const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
+  if (T >= 0x7fffffffL || (long)N * H * W * C >= (1L << 40)) return LF_EINVAL;
+  hipLaunchKernelGGL(wino2d_input_f16x3_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, (_Float16*)V, eV,
+                     H, W, C, lf_wino_f16x3_cin_padded(C), (H + 1) / 2, (W + 1) / 2, T);
+  return lf_launch_status();
+}
+
+extern "C" size_t lf_wino_fused2d_f16x3_scratch_bytes(int N, int H, int W, int Cout) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
+  const long T = (long)N * ((H + 1) / 2) * ((W + 1) / 2);
+  const int CoutP = lf_wino_fused_cout_padded(Cout), nt = nt2d(CoutP);
+  const int zs = zsplit((T + MT2 - 1) / MT2, (CoutP + nt - 1) / nt, 16);
+  return zs > 1 ? (size_t)zs * N * H * W * Cout * sizeof(float) : 0;
+}
+
+extern "C" int lf_wino_fused2d_f16x3_gemm(const void* V, const int* eV, const void* U2, int eU, const float* bias, float* y,
+                                          void* scratch, size_t scratch_bytes, int N, int H, int W, int Cin, int Cout, float he,
+                                          unsigned flags, float slope, void* stream) {
+  lf_clear_error();
+  if (V == nullptr || eV == nullptr || U2 == nullptr || y == nullptr) return LF_EINVAL;
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 3) || (Cout & 3)) return LF_EINVAL;
+  if ((flags & ~LF_EPI_LRELU) || eU < -100 || eU > 100) return LF_EINVAL;
+  if (!lf_aligned16(V) || !lf_aligned16(U2) || !lf_aligned16(y) || (bias && !lf_aligned16(bias)) || ((uintptr_t)eV & 3)) return LF_EALIGN;
+  const int ty = (H + 1) / 2, tx = (W + 1) / 2;
+  const long T = (long)N * ty * tx;
+  const int CoutP = lf_wino_fused_cout_padded(Cout), CinP = lf_wino_f16x3_cin_padded(Cin);
+  if (T * CinP * 4 > 0xffffffffL || (long)CoutP * CinP * 4 > 0xffffffffL) return LF_EINVAL;
+  const int nt = nt2d(CoutP);
+  const long gx = (T + MT2 - 1) / MT2;
+  const int gy = (CoutP + nt - 1) / nt;
+  if (gx > 0x7fffffffL || gy > 65535) return LF_EINVAL;
+  const int zs = zsplit(gx, gy, 16);
+  const long ysize = (long)N * H * W * Cout;
+  if (zs > 1 && (scratch == nullptr || scratch_bytes < (size_t)zs * ysize * sizeof(float) || !lf_aligned16(scratch))) return LF_ENOSPC;
+  float* partial = zs > 1 ? (float*)scratch : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const void* kern = nt == NT2 ? (const void*)wino_fused2d_f16x3_kernel : (const void*)wino_fused2d_f16x3_c64_kernel;
+  const int lds = nt == NT2 ? LDS2_BYTES : LDS2S_BYTES;
+  static lf_devmask_t attr_big, attr_c64;
+  {
+    hipError_t e = lf_ensure_dyn_lds(nt == NT2 ? attr_big : attr_c64, kern, lds);
+    if (e != hipSuccess) return (int)e;
+  }
+  const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)zs);
+  if (nt == NT2)
+    hipLaunchKernelGGL(wino_fused2d_f16x3_kernel, grid, dim3(512), lds, s, (const _Float16*)V, (const _Float16*)U2, bias, y, T, ty, tx,
+                       H, W, CinP, Cout, CoutP, he, eU, eV, flags, slope, partial, ysize);
+  else
+    hipLaunchKernelGGL(wino_fused2d_f16x3_c64_kernel, grid, dim3(512), lds, s, (const _Float16*)V, (const _Float16*)U2, bias, y, T, ty,
+                       tx, H, W, CinP, Cout, CoutP, he, eU, eV, flags, slope, partial, ysize);
+  const int st = lf_launch_status();
+  if (st || zs == 1) return st;
+  const long n4 = ysize / 4;
+  hipLaunchKernelGGL(wino_fused2d_f16x3_finish_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const f32x4*)partial, bias,
+                     (f32x4*)y, n4, zs, Cout / 4, H, W, ty, tx, ldexpf(he, -eU), eV, flags, slope);
   return lf_launch_status();
 }

@@ -145,7 +145,8 @@ class RenderLoopEngine:
         'winograd' F(2x2x2,3x3x3) minimal filtering, all-fp32 arithmetic (fp32 MFMA + fp32 transforms);
         'f16x3'    each fp32 product from three f16 MFMAs with fp32 accumulation: on 16->16 blocks the direct kernel
                    (documented preset: bench `alt`), on wide (>= 64-channel) blocks the F(2x2x2,3x3x3) Winograd GEMM
-                   lf_wino_fused_f16x3_gemm for every camera-block convolution and data gradient;
+                   lf_wino_fused_f16x3_gemm for every camera-block convolution and data gradient; the 2-D decoder's wide
+                   layers of the shapes and batches in ops.WIDE2D_F16X3_ROUTE on lf_wino_fused2d_f16x3_gemm (forward and data gradient);
         'auto'     (default) 'winograd' when the blocks are 16->16 or >= 64 channels wide, else 'fp32'.
         All stay within the fp32 kernel's distance of an fp64 reference (tests/test_engine_gpu.py).
         fuse_projection: None = the default (factor projection forward fused into the last block's Winograd launch where the
@@ -635,7 +636,10 @@ class RenderLoopEngine:
             logits = ops.empty_cl((n, hw.shape[0], hh, ww), dev)
             ops._conv1x1_raw(dacts[-1], hpk, hb, n, hh * ww, hw.shape[1], 1, hh * ww * hw.shape[1], 0, hw.shape[0], logits, hhe, 0)
         else:
-            with torch.set_grad_enabled(need_grad):
+            # conv_mode 'f16x3': the decoder's wide 2-D convolutions on the split-precision Winograd GEMM where that was measured
+            # faster (ops.WIDE2D_F16X3_ROUTE); each records its form for its own backward, so the autograd backward below
+            # follows it without the scope
+            with torch.set_grad_enabled(need_grad), ops.wide2d_f16x3(self.conv_mode == 'f16x3'):
                 yimg, rescale = self.ph.decode_features(zp_leaf)      # (a final nearest up-sampling is owed to the logits)
                 if self.heads is not None:
                     logits = ops.conv1x1(yimg, self.heads[0], self.heads[1])

@@ -471,35 +471,44 @@ def wide_conv(x, weight, bias, he, flags, transpose=False, depth_inner=False):
 
 
 def pack_conv_wino_fused_f16x3(weight, transpose=False):
-    """[Cout,Cin,3,3,3] -> (U2s, eU) for lf_wino_fused_f16x3_gemm: U2s [64][CoutP][CinP/32][2][32] f16, the Winograd weights
-    of pack_conv_wino_fused (fp64) times 2^eU, split into hi = f16(u) and lo = f16(u - hi) per 32-channel record
-    (CoutP = lf_wino_fused_cout_padded(Cout), CinP = lf_wino_f16x3_cin_padded(Cin), zero padded); eU puts max|U| 2^eU in
-    [2^11, 2^12)."""
+    """[Cout,Cin,3,3,3] or [Cout,Cin,3,3] -> (U2s, eU) for lf_wino_fused_f16x3_gemm / lf_wino_fused2d_f16x3_gemm:
+    U2s [F][CoutP][CinP/32][2][32] f16 (F = 64 frequencies in 3-D, 16 in 2-D), the Winograd weights of pack_conv_wino_fused
+    (fp64) times 2^eU, split into hi = f16(u) and lo = f16(u - hi) per 32-channel record (CoutP = lf_wino_fused_cout_padded(Cout),
+    CinP = lf_wino_f16x3_cin_padded(Cin), zero padded); eU puts max|U| 2^eU in [2^11, 2^12)."""
     w = weight.detach()
     if transpose:
-        w = w.transpose(0, 1).flip(dims=(2, 3, 4))
-    assert w.dim() == 5 and tuple(w.shape[2:]) == (3, 3, 3)
+        w = w.transpose(0, 1).flip(dims=tuple(range(2, w.dim())))
+    assert w.dim() in (4, 5) and tuple(w.shape[2:]) == (3,) * (w.dim() - 2)
     G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
     cout, cin = w.shape[0], w.shape[1]
-    U = torch.einsum('ai,bj,ck,omijk->abcom', G, G, G, w.double()).reshape(64, cout, cin)
+    if w.dim() == 5:
+        U = torch.einsum('ai,bj,ck,omijk->abcom', G, G, G, w.double()).reshape(64, cout, cin)
+    else:
+        U = torch.einsum('bj,ck,omjk->bcom', G, G, w.double()).reshape(16, cout, cin)
+    F = U.shape[0]
     amax = U.abs().max().item()
     eU = 12 - math.frexp(amax)[1] if amax > 0 else 0
     coutp, cinp = (cout + 63) // 64 * 64, (cin + 31) // 32 * 32          # lf_wino_fused_cout_padded / lf_wino_f16x3_cin_padded
-    Us = torch.zeros(64, coutp, cinp, dtype=torch.float64, device=w.device)
+    Us = torch.zeros(F, coutp, cinp, dtype=torch.float64, device=w.device)
     Us[:, :cout, :cin] = torch.ldexp(U, torch.tensor(float(eU), dtype=torch.float64, device=w.device))
     hi = Us.half()
     lo = (Us - hi.double()).half()
-    out = torch.stack((hi.reshape(64, coutp, cinp // 32, 32), lo.reshape(64, coutp, cinp // 32, 32)), dim=3)
+    out = torch.stack((hi.reshape(F, coutp, cinp // 32, 32), lo.reshape(F, coutp, cinp // 32, 32)), dim=3)
     return out.contiguous(), eU
 
 
 def wide_conv_f16x3(x, weight, bias, he, flags, transpose=False, depth_inner=False, amax_in=None, amax_out=None):
     """Wide 3-D 3x3x3 convolution (or its data gradient, transpose=True) with three-term f16 products
     (lf_wino3d_input_transform_f16x3 + lf_wino_fused_f16x3_gemm); PixelNorm as a pass over the output, as conv_wino_fused.
+    A 4-D x: the 2-D 3x3 form (lf_wino2d_input_transform_f16x3 + lf_wino_fused2d_f16x3_gemm), whose input scale is chosen per
+    Winograd tile by the transform itself (amax_in / amax_out / depth_inner do not apply).
     amax_in: max-abs buffer (amax_buffer) holding a bound of max|x| -- the input's power-of-two scale is derived from it on the
     device; None: measured here from x.  amax_out (zeroed amax_buffer, optional): receives max|y| before any PixelNorm.
     Returns (y, norm or None); depth_inner: y as a plain (N, H, W, D, cout) tensor (LF_OUT_DEPTH_INNER)."""
     L = _lib.lib()
+    if x.dim() == 4:
+        assert amax_in is None and amax_out is None and not depth_inner
+        return _wide_conv2d_f16x3(x, weight, bias, he, flags, transpose)
     assert x.dim() == 5
     cout = weight.shape[1] if transpose else weight.shape[0]
     U2, eU = _pk(weight, 'wxb' if transpose else 'wxf', lambda w: pack_conv_wino_fused_f16x3(w, transpose=transpose))
@@ -529,6 +538,71 @@ def wide_conv_f16x3(x, weight, bias, he, flags, transpose=False, depth_inner=Fal
         norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32)
         check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * D * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
     return y, norm
+
+
+def _wide_conv2d_f16x3(x, weight, bias, he, flags, transpose=False):
+    L = _lib.lib()
+    cout = weight.shape[1] if transpose else weight.shape[0]
+    U2, eU = _pk(weight, 'wxb' if transpose else 'wxf', lambda w: pack_conv_wino_fused_f16x3(w, transpose=transpose))
+    N, cin, H, W = x.shape
+    T = L.lf_wino2d_tiles(N, H, W)
+    V = torch.empty(16, T, L.lf_wino_f16x3_cin_padded(cin) * 2, device=x.device, dtype=torch.float16)
+    eV = torch.empty(T, device=x.device, dtype=torch.int32)
+    with _timed('wino2d_input_f16x3'):
+        check(L.lf_wino2d_input_transform_f16x3(_ptr(x), _ptr(V), _ptr(eV), N, H, W, cin, _stream()), 'lf_wino2d_input_transform_f16x3')
+    y = empty_cl((N, cout, H, W), x.device)
+    nscr = L.lf_wino_fused2d_f16x3_scratch_bytes(N, H, W, cout)
+    scr = torch.empty(nscr // 4, device=x.device, dtype=torch.float32) if nscr else None
+    with _timed('wino2d_fused_f16x3'):
+        check(L.lf_wino_fused2d_f16x3_gemm(_ptr(V), _ptr(eV), _ptr(U2), eU, _ptr(bias) if bias is not None else None, _ptr(y),
+                                           _ptr(scr, True) if scr is not None else None, nscr, N, H, W, cin, cout, he,
+                                           flags & LF_EPI_LRELU, SLOPE, _stream()), 'lf_wino_fused2d_f16x3_gemm')
+    del V
+    norm = None
+    if flags & LF_EPI_PIXELNORM:
+        norm = torch.empty(N * H * W, device=x.device, dtype=torch.float32)
+        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+    return y, norm
+
+
+# Scope of the split-precision 2-D decoder (RenderLoopEngine conv_mode='f16x3'): inside `with ops.wide2d_f16x3():` the wide 2-D
+# convolutions of _Conv3x3 that WIDE2D_F16X3_ROUTE lists for their shape and batch run on lf_wino_fused2d_f16x3_gemm instead of
+# the fp32 pair (lf_wino2d_input_transform + lf_wino_fused_gemm); the forward records the forms it chose, so the backward does
+# not depend on the scope.  Autocast and the 3-D dispatch are not affected, and with WIDE_CONV_MODE = 'bmm' (the library-GEMM
+# A/B form) nothing is routed: every wide convolution then keeps that form.
+WIDE2D_F16X3 = False
+# (Cin, Cout, H, W) of a convolution -- a layer's forward, or the data gradient of a layer (Cout, Cin, H, W) -- -> N_min: the
+# smallest batch from which on f16x3 measured faster than the fp32 pair at every measured batch (N = 8, 16, 32, 128;
+# tools/wide2d_f16x3_ab.py, profiles/r08_wide2d_f16x3_ab.jsonl).  Routed: the released architecture's decoder layers with
+# >= 196 channels, 1.15-2.1x at N = 128.  Not routed: the 128 -> 128 / 128 -> 64 / 64 -> 64 layers on 64^2 and 128^2 (0.58-0.96x:
+# the f16x3 GEMM is faster, but its input transform is 2.3-2.5x slower than the fp32 one -- one wave per tile leaves 48-56 of 64
+# lanes idle at 64-128 channels, and it reads the patch twice) and the released-width model's 64-96-channel layers at N = 4
+# (0.70-0.83x: launch-bound).
+WIDE2D_F16X3_ROUTE = {
+    (128, 196, 64, 64): 8, (196, 128, 64, 64): 8, (196, 196, 32, 32): 8, (196, 256, 32, 32): 8, (256, 196, 32, 32): 8,
+    (256, 256, 16, 16): 16, (256, 512, 16, 16): 16, (512, 256, 16, 16): 8, (512, 512, 16, 16): 8, (512, 512, 8, 8): 16,
+    (512, 1024, 8, 8): 8, (1024, 512, 8, 8): 16, (512, 512, 4, 4): 128}
+
+
+class wide2d_f16x3:
+    def __init__(self, enabled=True):
+        self.enabled = enabled
+
+    def __enter__(self):
+        global WIDE2D_F16X3
+        self.prev = WIDE2D_F16X3
+        WIDE2D_F16X3 = bool(self.enabled)
+        return self
+
+    def __exit__(self, *exc):
+        global WIDE2D_F16X3
+        WIDE2D_F16X3 = self.prev
+        return False
+
+
+def _wide2d_f16x3_routed(cin, cout, H, W, N):
+    n_min = WIDE2D_F16X3_ROUTE.get((cin, cout, H, W))
+    return n_min is not None and N >= n_min
 
 
 def epilogue_bwd_amax(gy, y, norm, flags, amax_out):
@@ -700,6 +774,8 @@ class _Conv3x3(torch.autograd.Function):
         he = he_constant(weight)
         b = bias.detach() if bias is not None else None
         ctx.ac = AUTOCAST is not None
+        split2d = WIDE2D_F16X3 and not ctx.ac and WIDE_CONV_MODE == 'fused'
+        ctx.f16x3 = (False, False)                            # (forward, data gradient) on the split-precision 2-D kernel
         if ctx.ac and _wino_ok(x, weight):                    # autocast, 3-D 16 -> 16: direct conv on the bf16 MFMA
             y, norm = conv3d_c16_ring_bf16(x, _pk(weight, 'r3f', pack_conv3d_c16_ring_bf16), b, he, flags, 1)
             # (the input is saved un-rounded: the bf16 weight-gradient kernel rounds it while staging, like this one)
@@ -710,7 +786,13 @@ class _Conv3x3(torch.autograd.Function):
             if _wino_ok(x, weight):                           # 3-D 16 -> 16: the all-fp32 Winograd kernel
                 y, norm = conv3d_c16_wino(x, _pk(weight, 'w3f', pack_conv3d_c16_wino), b, he, flags)
             elif _wino_gemm_ok(x, weight):                    # wide 2-D / 3-D: Winograd with the fused fp32-MFMA GEMM
-                y, norm = wide_conv(x, weight, b, he, flags)
+                if x.dim() == 4 and split2d:
+                    N, cin, H, W = x.shape
+                    ctx.f16x3 = (_wide2d_f16x3_routed(cin, weight.shape[0], H, W, N), _wide2d_f16x3_routed(weight.shape[0], cin, H, W, N))
+                if ctx.f16x3[0]:                              # ... or its split-precision form (ops.wide2d_f16x3 scope)
+                    y, norm = wide_conv_f16x3(x, weight, b, he, flags)
+                else:
+                    y, norm = wide_conv(x, weight, b, he, flags)
             else:
                 wpack = _pk(weight, 'c3f', pack_conv3x3)
                 y, norm = _conv3x3_raw(x, wpack, b, weight.shape[0], he, flags, True)
@@ -734,6 +816,8 @@ class _Conv3x3(torch.autograd.Function):
                     gpc = _ac_in(gp)
                     if _wino_ok(gpc, w):
                         gx, _ = conv3d_c16_wino(gpc, _pk(w, 'w3b', lambda t: pack_conv3d_c16_wino(t, transpose=True)), None, ctx.he, 0)
+                    elif ctx.f16x3[1]:
+                        gx, _ = wide_conv_f16x3(gpc, w, None, ctx.he, 0, transpose=True)
                     elif _wino_gemm_ok(gpc, w):
                         gx, _ = wide_conv(gpc, w, None, ctx.he, 0, transpose=True)
                     else:
