@@ -241,6 +241,50 @@ def epilogue_bwd_c16(gy, y, norm, flags, want_bias, out_bf16=True):
     return gp, gb
 
 
+def _ex_prev_scratch_floats(device, _cache={}):
+    """Size of LF_RING_EX_PREV's partial-sum buffer, 16 * (1 + 2 * #CUs) floats (include/lf_hip.h)."""
+    n = _cache.get(device)
+    if n is None:
+        n = _cache[device] = 16 * (1 + 2 * torch.cuda.get_device_properties(device).multi_processor_count)
+    return n
+
+
+# The chained epilogue's hand-off (CHAIN_EPILOGUE).  A consumer that applied the producer's epilogue backward ARMS the
+# producer's box with the data gradient `gx` it returned -- the producer's pre-activation gradient -- and the bias sums of
+# that launch.  The producer takes the fused result only if the box was armed in the SAME backward pass, and it disarms the
+# box.  Its incoming gradient is then either exactly `gx` (the usual case: nothing else consumed the activation), or `gx`
+# plus post-activation gradients of other consumers, which still need the epilogue backward.  The box holds `gx` itself,
+# not a copy: a tensor referenced elsewhere is never the target of autograd's in-place gradient accumulation, so `gx` keeps
+# its values and the incoming gradient can be told apart from it (storage, version, shape).
+def _chain_box():
+    return {'gx': None, 'gb': None, 'task': None}
+
+
+def _chain_take(box):
+    """The box's (gx, gb) when it was armed in the running backward pass, else None."""
+    if box['gx'] is None or box['task'] != torch._C._current_graph_task_id():
+        return None
+    return box['gx'], box['gb']
+
+
+def _chain_arm(box, gx, gb):
+    box['gx'], box['gb'], box['task'] = gx, gb, torch._C._current_graph_task_id()
+
+
+def _chain_epilogue_bwd(ctx, gy, y, norm, want_b):
+    """The producer's side of an armed box: (pre-activation gradient in bf16, bias gradient or None); disarms the box."""
+    gx, gb = _chain_take(ctx.box)
+    ctx.box.update(gx=None, gb=None, task=None)
+    if (gy.data_ptr() == gx.data_ptr() and gy._version == gx._version and gy.shape == gx.shape
+            and gy.stride() == gx.stride() and gy.dtype == gx.dtype):
+        return gx, (gb if want_b else None)
+    # other consumers added post-activation gradients into gy: their share still goes through this layer's epilogue backward
+    rest = gy.float() - gx.float()
+    gp_rest, gb_rest = epilogue_bwd_c16(cl(rest), y, norm, ctx.flags, want_b, out_bf16=False)
+    gp = cl((gp_rest + gx.float()).to(torch.bfloat16))
+    return gp, (gb + gb_rest if want_b else None)
+
+
 class _Conv16AC(torch.autograd.Function):
     """A 3-D 16 -> 16 layer (3x3x3, or 1x1x1 on the centre tap) of the training step under the bf16 autocast + storage policy:
     x (fp32 or bf16 storage) -> epilogue(conv(x, W) * he + b) in bf16 storage on lf_conv3d_c16_ring_bf16_io.  Backward: one
@@ -289,7 +333,7 @@ class _Conv16AC(torch.autograd.Function):
         # the consumer as that layer's input), and the box through which the consumer reports having done so
         ctx.box = None
         if CHAIN_EPILOGUE and flags == (LF_EPI_LRELU | LF_EPI_PIXELNORM) and not one:
-            ctx.box = {'done': False, 'gb': None}
+            ctx.box = _chain_box()
             y._lf_link = (norm, ctx.box)
         ctx.link = None
         if link is not None and x.dtype == torch.bfloat16 and need_w and not one and x.shape[2] * x.shape[3] * x.shape[4] * 64 < 2 ** 31:
@@ -304,10 +348,8 @@ class _Conv16AC(torch.autograd.Function):
         pw_bwd = ctx.pw and ctx.flags == 0 and gy.dtype == torch.bfloat16 and ctx.needs_input_grad[0]
         if pw_bwd:
             gp, gb = gy, None                                     # no activation: the pre-activation gradient IS gy; the bias sums ride in lf_pw16_bwd
-        elif ctx.box is not None and ctx.box['done']:
-            gp, gb = gy, ctx.box['gb']                            # the consumer's data gradient already applied this layer's epilogue backward
-            if gp.dtype != torch.bfloat16:
-                gp = gp.to(torch.bfloat16)
+        elif ctx.box is not None and _chain_take(ctx.box) is not None:
+            gp, gb = _chain_epilogue_bwd(ctx, gy, y, norm, want_b)
         elif ctx.flags == 0 and not want_b and gy.dtype == torch.bfloat16:
             gp, gb = gy, None
         else:
@@ -354,15 +396,15 @@ class _Conv16AC(torch.autograd.Function):
                                         _ptr(scr, True) if need_gb else None, scr.numel() * 4 if need_gb else 0, rows, _stream()), 'lf_pw16_bwd')
             elif ctx.needs_input_grad[0]:
                 pack_t = _pk(w, 'a3b', lambda t: pack_conv3d_c16_ring_bf16(w3(t), transpose=True))
-                if ctx.link is not None and gp.dtype == torch.bfloat16:
+                if ctx.link is not None and gp.dtype == torch.bfloat16 and _chain_take(ctx.link[1]) is None:
                     # this layer's data gradient + the PRODUCER's epilogue backward and bias sums in one launch: x_saved is the
                     # producer's activation
                     pnorm, pbox = ctx.link
                     gx = torch.empty_like(gp)
-                    gbuf = torch.zeros(16 * 1025, device=gp.device, dtype=torch.float32)
+                    gbuf = torch.zeros(_ex_prev_scratch_floats(gp.device), device=gp.device, dtype=torch.float32)
                     ring_multi(gp, pack_t.reshape(1, 14, 16, 32), ctx.he, [(gx, None, True)], extra=_lib.LF_RING_EX_PREV, e0=x_saved, e1=pnorm,
                                o2=gbuf)
-                    pbox['done'], pbox['gb'] = True, gbuf[:16]
+                    _chain_arm(pbox, gx, gbuf[:16])
                 elif RING_DGRAD and gp.dtype == torch.bfloat16 and ctx.xdtype == torch.bfloat16:
                     # the same sums and roundings on the one-group ring kernel with a compile-time epilogue (csrc/conv_gru.hip):
                     # bit-identical, 32 instead of 53 us per 128^3 volume
@@ -380,7 +422,7 @@ class _Conv16AC(torch.autograd.Function):
                     gw = round_bf16(gwt[13].reshape(w.shape).contiguous())
                 else:
                     gw = round_bf16(gwt.reshape(3, 3, 3, 16, 16).permute(3, 4, 0, 1, 2).contiguous())
-        return gx, gw, gb, None, None
+        return gx, gw, gb if want_b else None, None, None
 
 
 def _conv16_ac_ok(x, weight):
