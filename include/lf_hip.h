@@ -535,6 +535,16 @@ int lf_conv_bwd_weight_bf16(const float* x, const float* gpre, float* gw, void* 
 /* ... with x (io & 1) and / or gpre (io & 2) stored as bf16 channels-last records (see lf_conv3d_c16_ring_bf16_io). */
 int lf_conv_bwd_weight_bf16_io(const void* x, const void* gpre, float* gw, void* scratch, size_t scratch_bytes,
                                int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, int io, void* stream);
+/* The same weight gradient (lf_conv_bwd_weight's math, layouts and output; autograd of equalized.py:57-64 /
+ * modules/blocks.py:152-158 in train_reconstruct.py:421-535) for WIDE layers: any Cin, Cout >= 16 (ragged allowed), dims
+ * 0 / 2 / 3, x != NULL (the bias gradient stays on lf_conv_bwd_weight).  LDS-staged fp32 MFMA over 64 x 64 channel tiles;
+ * fp32 products are exact, so it also serves bf16-valued (autocast) operands.  Deterministic: per-run partials in
+ * `scratch` (lf_conv_bwd_weight_wide_scratch_bytes; 0 for an unsupported shape), fixed-order fp64 sum.  Returns LF_EINVAL
+ * for a NULL operand or an unsupported shape, LF_EALIGN for x / gpre / gw / scratch not 16-byte aligned, LF_ENOSPC for a
+ * short scratch; nothing is launched and gw is not written then. */
+size_t lf_conv_bwd_weight_wide_scratch_bytes(int dims, int N, int D, int H, int W, int Cin, int Cout);
+int lf_conv_bwd_weight_wide(const float* x, const float* gpre, float* gw, void* scratch, size_t scratch_bytes,
+                            int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, void* stream);
 
 /* Epilogue backward of a 16-CHANNEL layer for the training step: gp = LeakyReLU'(y) PixelNorm'(gy; y, norm) (flags says
  * which; flags = 0: gp = gy) with the bias gradient gbias[16] = column sums of the un-rounded gp folded into the same pass

@@ -41,6 +41,7 @@ RING_DGRAD = _env('RING_DGRAD', True)                  # data gradients of the 1
 CHAIN_EPILOGUE = _env('CHAIN_EPILOGUE', True)          # a Block's conv2 data gradient applies conv1's epilogue backward (LF_RING_EX_PREV)
 LIFT_MFMA = _env('LIFT_MFMA', True)                    # the 16-channel lift as one MFMA kernel each way (csrc/lift_mfma.hip)
 PW16 = _env('PW16', True)                              # 1x1x1 16 -> 16 layers on the pointwise MFMA kernels (csrc/pw16.hip), not on the centre tap of the ring kernels
+WIDE_WGRAD = _env('WIDE_WGRAD', True)                  # weight gradients with Cin, Cout >= 64 on the LDS-staged MFMA kernel (csrc/wgrad_wide.hip)
 
 
 _SIDE = {}
@@ -166,6 +167,12 @@ def _wgrad_bf16_ok(gp, dims, cin, cout):
     return D * H * W * 64 < 2 ** 31 and (D + 3) * H * W * 64 <= 0xffffffff
 
 
+def _wide_wgrad_ok(x, gp, dims, cin, cout):
+    """Shapes routed to lf_conv_bwd_weight_wide (WIDE_WGRAD): Cin, Cout >= 64, 16-byte aligned channels-last operands."""
+    return (WIDE_WGRAD and dims in (0, 2, 3) and cin >= 64 and cout >= 64 and x is not None
+            and x.data_ptr() % 16 == 0 and gp.data_ptr() % 16 == 0)
+
+
 def conv_bwd_weight(x, gp, dims, cin, he, want_bias=True, bf16=None):
     """Weight and bias gradients of y = conv(x, W) * he + b from the pre-activation gradient `gp`
     (lf_conv_bwd_weight).  x, gp: channels-last (N,C,[D,]H,W), or plain [rows][C] matrices for dims = 0.
@@ -201,10 +208,17 @@ def conv_bwd_weight(x, gp, dims, cin, he, want_bias=True, bf16=None):
     taps = {0: 1, 2: 9, 3: 27}[dims]
     gw = torch.empty(taps, cout, cin, device=gp.device, dtype=torch.float32)
     gb = torch.empty(1, cout, 1, device=gp.device, dtype=torch.float32) if want_bias else None
-    nbytes = max(L.lf_conv_bwd_weight_scratch_bytes(dims, N, D, H, W, cin, cout),
+    wide = _wide_wgrad_ok(x, gp, dims, cin, cout)
+    nbytes = max(L.lf_conv_bwd_weight_wide_scratch_bytes(dims, N, D, H, W, cin, cout) if wide else
+                 L.lf_conv_bwd_weight_scratch_bytes(dims, N, D, H, W, cin, cout),
                  L.lf_conv_bwd_weight_scratch_bytes(0, N, D, H, W, 0, cout))
-    scratch = torch.empty(nbytes // 4 + 1, device=gp.device, dtype=torch.float32)
-    if bf16 and _wgrad_bf16_ok(gp, dims, cin, cout):
+    scratch = torch.empty(nbytes // 4 + 4, device=gp.device, dtype=torch.float32)
+    if wide:
+        # wide layers: 64 x 64 channel tiles staged in LDS (products exact, so the autocast policy's operands too)
+        with _timed('wgrad_wide', f'{dims}:{cin}:{cout}'):
+            check(L.lf_conv_bwd_weight_wide(_ptr(x), _ptr(gp), _ptr(gw), _ptr(scratch, True), scratch.numel() * 4, dims, N, D, H, W,
+                                            cin, cout, he, _stream()), 'lf_conv_bwd_weight_wide')
+    elif bf16 and _wgrad_bf16_ok(gp, dims, cin, cout):
         # autocast: both operands are bf16 values -- the bf16 MFMA forms the same exact products 8x faster
         check(L.lf_conv_bwd_weight_bf16(_ptr(x), _ptr(gp), _ptr(gw), _ptr(scratch, True), scratch.numel() * 4, dims, N, D, H, W, cin, cout,
                                         he, _stream()), 'lf_conv_bwd_weight_bf16')
