@@ -11,8 +11,16 @@ parameters of every sample, batched Adam + plateau step, ranking.  Workload: SYN
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                 # + every secondary measurement and check
     python bench.py --gpus N ...                      # bench.py starts the N ranks itself (launch_ranks below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set up (model, two builds of the object, the loop state), warm up, time the
+--steps iterations, write --dump-outputs, print the line (`value`, `ms_per_step`, the timing blocks, `roofline` of the
+dominant kernel from the HIP events of the timed blocks).  `--full` adds everything else, each part still switched off by its
+own `--no-...` flag: the CPU baseline with its parity checks, the f16x3 `alt` line, the cfg 3 / cfg 5 / renderer-variant
+blocks, the comparison with the reference's own trace, the live PMC traffic, the per-kernel block behind `roofline_iter`,
+the RCCL probe, the sharding sections at N > 1 and the closing `summary`.
 
 `--gpus N` IS the number of ranks: without a launcher environment bench.py spawns N processes (one per GPU, RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* set, RCCL process group); under a launcher it checks WORLD_SIZE == N and fails
@@ -54,6 +62,10 @@ def parse(argv=None):
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the headline loop computed in its last timed step as DIR/<name>.npy '
                          '(float32 / float64; the inputs are seeded, so two builds can be compared output for output)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, run every secondary measurement and check as well (CPU baseline and parity, alt, '
+                         'cfg3, cfg5, renderer variants, reference trace, live PMC, per-kernel block, RCCL probe, sharding at '
+                         'N > 1, summary); the --no-... flags below switch single parts of it off.  Off: the headline alone')
     ap.add_argument('--size', type=int, default=128, help='latent volume side S of SYN(S,C)')
     ap.add_argument('--channels', type=int, default=16)
     ap.add_argument('--views', type=int, default=16)
@@ -75,7 +87,8 @@ def parse(argv=None):
     ap.add_argument('--sharded-build', action='store_true',
                     help='reconstruct ONE pool:mean object with its reference views sharded over the ranks and fused by the '
                          'RCCL all-reduce of the latent volume (parallel.build_latent_object_sharded); reported as '
-                         '`sharded_build`.  ON by default when N > 1 (the north-star collective); this flag forces it at N = 1')
+                         '`sharded_build`.  ON by default under --full when N > 1 (the north-star collective); this flag forces '
+                         'it, also at N = 1 and without --full')
     ap.add_argument('--no-sharded-build', action='store_true', help='skip the view-sharded build at N > 1')
     ap.add_argument('--fuse-projection', default='default', choices=['default', 'none', 'fwd'],
                     help="factor projection fused into the last camera block's Winograd kernels (engine.py): 'default' = forward form")
@@ -755,7 +768,8 @@ def main():
     init = pu.sample_cameras_with_estimate(N, target.camera.to('cpu'))
     init_rec = {'K': init.intrinsic.clone(), 'log_q': init.log_quaternion.clone(), 't': init.translation.clone()}
     st = est.start(z_obj, target, init.zoom(None, model.input_size, model.camera_dist).to(dev))
-    # losses and camera gradients of iteration 0 (before any optimiser step), for the parity line below
+    # losses and camera gradients of iteration 0 (before any optimiser step), for the parity line of --full; a plain run makes
+    # this call too, so that the warm-up and timed iterations always follow the engine's first call (its allocations)
     with torch.no_grad():
         l0, g0 = st['engine'].forward_backward(st['cam'], need_grad=True)
     hip0 = {'rank_loss': l0[:, 4].cpu(), 'grad': g0.cpu()}
@@ -766,10 +780,11 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    def timed_loop(est_, st_, events=True, outputs=None):
+    def timed_loop(est_, st_, events=True, outputs=None, kernel_block=True):
         """W warm-up iterations, then EXACTLY K = --steps timed iterations in `--repeats` back-to-back blocks, each bracketed
         by barrier + synchronize and reduced with MAX over the ranks.  Returns (total time of the blocks, [(block time,
-        iterations)], the kernel events of all blocks).  `outputs` (a dict) receives what the last timed iteration computed."""
+        iterations)], the kernel events of all blocks).  `outputs` (a dict) receives what the last timed iteration computed.
+        `kernel_block`: one more, untimed block of K iterations behind them with events around the other heavy kernels."""
         for _ in range(a.warmup):
             est_.iterate(st_)
         nb = max(1, min(a.repeats, a.steps))
@@ -798,7 +813,7 @@ def main():
         if outputs is not None:
             outputs.update(last_step_outputs(st_))
         total = sum(b for b, _ in blocks)
-        if not events:
+        if not (events and kernel_block):
             return total, blocks, timer_
         ops.KERNEL_TIMER_TAGS = {'conv3d_c16_wino_projfwd', 'conv3d_c16_wino_projbwd', 'resample_fwd', 'resample_bwd_coef',
                                  'factor_project_fwd', 'factor_project_bwd'}
@@ -815,14 +830,14 @@ def main():
         return e_.start(z_, target, init.zoom(None, model.input_size, model.camera_dist).to(dev))
 
     dumped = {} if a.dump_outputs else None
-    elapsed, blocks, timer = timed_loop(est, st, outputs=dumped)
+    elapsed, blocks, timer = timed_loop(est, st, outputs=dumped, kernel_block=a.full)
     dump = None
     if dumped is not None and rank == 0:                   # rank 0's object, like the line
         names, nbytes = write_outputs(a.dump_outputs, dumped)
         dump = {'dir': a.dump_outputs, 'arrays': names, 'bytes': nbytes,
                 'what': f'the headline loop after its last timed iteration (iteration {a.warmup + a.steps - 1} from the seeded start)'}
     alt = None
-    if a.conv_mode in ('fp32', 'winograd') and not a.no_alt and C == 16:
+    if a.full and a.conv_mode in ('fp32', 'winograd') and not a.no_alt and C == 16:
         # secondary line (never `value`): the same loop with the split-precision conv3d kernels
         st = est = None
         torch.cuda.empty_cache()
@@ -890,7 +905,7 @@ def main():
         return None, None
     traffic, traffic_src = pmc_traffic(kname)
     traffic_live = None
-    if world == 1 and not a.no_live_pmc and wino and S == 128 and C == 16 and N == 8:
+    if a.full and world == 1 and not a.no_live_pmc and wino and S == 128 and C == 16 and N == 8:
         # measured now, on this box: two counter passes over the same kernel at the same shape in a child process (the bench is idle
         # meanwhile); the committed file is the fallback
         try:
@@ -943,7 +958,7 @@ def main():
     iter_floor_ms = iter_bytes / (HBM_PEAK_GBS * 1e9) * 1e3
 
     sharded = None
-    if a.sharded_build or (world > 1 and not a.no_sharded_build):
+    if a.sharded_build or (a.full and world > 1 and not a.no_sharded_build):
         # auxiliary measurement: whatever happens here must not lose the headline line of an N-GPU run
         try:
             sharded = sharded_build_report(a, S, C, V, dev, world, barrier)
@@ -952,7 +967,7 @@ def main():
 
     # N > 1: the other two sharding axes of SURVEY 8(e), on ONE object (auxiliary: never allowed to lose the headline line)
     pipelined, hyp = None, None
-    if world > 1 and not (a.no_pipelined_build and a.no_hypothesis_sharding):
+    if a.full and world > 1 and not (a.no_pipelined_build and a.no_hypothesis_sharding):
         try:
             st = est = st2 = est2 = None                             # release the per-rank loop states
             torch.cuda.empty_cache()
@@ -968,7 +983,7 @@ def main():
             pipelined = {'error': f'{type(e).__name__}: {e}'[:300]}
 
     cfg3 = None
-    if world == 1 and not a.no_cfg3:
+    if a.full and world == 1 and not a.no_cfg3:
         try:
             st = est = st2 = est2 = None
             torch.cuda.empty_cache()
@@ -980,7 +995,7 @@ def main():
     # build container by oracle/make_golden_headline.py from the imported reference): volume, iteration-0 renders and the whole
     # 100-iteration adam_quick trace (GPU only, ~1 s; the fixture is data, the reference never runs here)
     ref_trace = None
-    if world == 1 and (S, C, V, N, a.fuser) == (128, 16, 16, 8, 'gru'):
+    if a.full and world == 1 and (S, C, V, N, a.fuser) == (128, 16, 16, 8, 'gru'):
         try:
             import importlib.util
             spec = importlib.util.spec_from_file_location('headline_trace_probe', os.path.join(ROOT, 'tools', 'headline_trace_probe.py'))
@@ -995,7 +1010,7 @@ def main():
             ref_trace = {'error': f'{type(e).__name__}: {e}'[:300]}
 
     cfg5 = None
-    if world == 1 and not a.no_cfg5 and C == 16:
+    if a.full and world == 1 and not a.no_cfg5 and C == 16:
         try:
             st = est = st2 = est2 = None
             torch.cuda.empty_cache()
@@ -1004,32 +1019,34 @@ def main():
             cfg5 = {'error': f'{type(e).__name__}: {e}'[:300]}
 
     variants = None
-    if world == 1 and not a.no_variants:
+    if a.full and world == 1 and not a.no_variants:
         try:
             variants = variants_report(a, dev)
         except Exception as e:                                       # noqa: BLE001  (auxiliary: never loses the headline)
             variants = {'error': f'{type(e).__name__}: {e}'[:300]}
 
-    # RCCL on this box: under a launcher the process group above IS an RCCL communicator; a plain `python bench.py` run
+    # RCCL (--full): under a launcher the process group above IS an RCCL communicator; a single `python bench.py` run
     # initialises a world-size-1 group here (after the timed regions, so it cannot touch the number) and runs one
     # all-reduce of a latent-volume-sized tensor through it
-    rccl = {'backend': None, 'ranks_seen': dist.get_world_size() if dist.is_initialized() else 1}
-    try:
-        if not dist.is_initialized():
-            os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
-            os.environ.setdefault('MASTER_PORT', str(29400 + os.getpid() % 500))
-            dist.init_process_group('nccl', rank=0, world_size=1)
-        rccl['backend'] = dist.get_backend()
-        rccl['ranks_seen'] = dist.get_world_size()
-        if rccl['backend'] == 'nccl':
-            rccl['rccl_version'] = '.'.join(str(v) for v in torch.cuda.nccl.version())
-        probe = torch.ones(C * S ** 3, device=dev)
-        dist.all_reduce(probe)
-        torch.cuda.synchronize()
-        rccl['allreduce_ok'] = bool(probe[0].item() == dist.get_world_size() and probe[-1].item() == dist.get_world_size())
-        del probe
-    except Exception as e:                                           # noqa: BLE001  (reported, never fatal for the bench line)
-        rccl['error'] = f'{type(e).__name__}: {e}'[:300]
+    rccl = None
+    if a.full:
+        rccl = {'backend': None, 'ranks_seen': dist.get_world_size() if dist.is_initialized() else 1}
+        try:
+            if not dist.is_initialized():
+                os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
+                os.environ.setdefault('MASTER_PORT', str(29400 + os.getpid() % 500))
+                dist.init_process_group('nccl', rank=0, world_size=1)
+            rccl['backend'] = dist.get_backend()
+            rccl['ranks_seen'] = dist.get_world_size()
+            if rccl['backend'] == 'nccl':
+                rccl['rccl_version'] = '.'.join(str(v) for v in torch.cuda.nccl.version())
+            probe = torch.ones(C * S ** 3, device=dev)
+            dist.all_reduce(probe)
+            torch.cuda.synchronize()
+            rccl['allreduce_ok'] = bool(probe[0].item() == dist.get_world_size() and probe[-1].item() == dist.get_world_size())
+            del probe
+        except Exception as e:                                       # noqa: BLE001  (reported, never fatal for the bench line)
+            rccl['error'] = f'{type(e).__name__}: {e}'[:300]
     if dist.is_initialized():
         barrier()
         dist.destroy_process_group()
@@ -1046,7 +1063,6 @@ def main():
                    'ms_per_step_blocks': [b / k * 1e3 for b, k in blocks],
                    'gpu_timed_total_s': elapsed,
                    'spread_pct': (max(b / k for b, k in blocks) - min(b / k for b, k in blocks)) / (elapsed / a.steps) * 100.0},
-        'rccl': rccl,
         'dtype': 'f32' if a.conv_mode in ('fp32', 'winograd') else 'f32 (conv3d products split into 3 f16 MFMAs, fp32 accumulate)', 'data': 'synthetic (SYN(S,C) random-init weights, synthetic observations)',
         'config': {'workload': f'SYN({S},{C}) latent volume, {V} reference views, adam_quick pose loop, '
                                f'{N} pose samples per iteration, one object per GPU',
@@ -1056,9 +1072,13 @@ def main():
         'e2e_100_iters_per_s': 100.0 / (t_build_warm + 100.0 * elapsed / a.steps),
         'roofline': roofline,
         'roofline_iter': {'hbm_floor_ms': iter_floor_ms, 'algorithmic_bytes_per_iteration': iter_bytes,
-                          'frac': iter_floor_ms / (elapsed / a.steps * 1e3), 'kernels': others},
+                          'frac': iter_floor_ms / (elapsed / a.steps * 1e3)},
     }
-    if world == 1 and not a.no_cpu_baseline:
+    if rccl is not None:
+        out['rccl'] = rccl
+    if a.full:                                                       # measured in the untimed block behind the timed ones
+        out['roofline_iter']['kernels'] = others
+    if a.full and world == 1 and not a.no_cpu_baseline:
         v, cores, ref0, cpu_dt, build_info, z_ora = cpu_baseline(cks[:3] + (cks[3],), z_obj.cpu(), rdata, tdata, init_rec, cfg,
                                                                   a.cpu_iters, build=not a.no_build_parity)
         # the HIP render + loss + camera gradients on the ORACLE-built volume (iteration 0): render parity that does not
@@ -1146,28 +1166,29 @@ def main():
         out['hypothesis_sharded_one_object'] = hyp
     if dump is not None:
         out['dump_outputs'] = dump
-    # LAST in the line (the driver keeps the line's tail): every secondary claim of DESIGN.md in one compact object
+    # LAST in the line (the driver keeps the line's tail), --full: every secondary claim of DESIGN.md in one compact object
     def dig(d, *ks):
         for k_ in ks:
             if not isinstance(d, dict) or k_ not in d:
                 return None
             d = d[k_]
         return d
-    tr = dig(ref_trace, 'trace') or {}
-    out['summary'] = {
-        'headline_iters_per_s': out.get('value'), 'headline_roofline_frac': dig(out, 'roofline', 'frac'),
-        'cpu_baseline_iters_per_s': dig(out, 'cpu_baseline', 'value'),
-        'cfg3_iters_per_s': dig(cfg3, 'value'), 'cfg3_roofline_frac': dig(cfg3, 'roofline', 'frac'),
-        'cfg3_scored_on_fused_engine': dig(cfg3, 'scored_on_fused_engine'),
-        'cfg5_ms_per_step': dig(cfg5, 'ms_per_step'), 'cfg5_peak_mem_GB': dig(cfg5, 'peak_mem_GB'), 'cfg5_peak_mem_step_GB': dig(cfg5, 'peak_mem_step_GB'),
-        'cfg5_roofline_step_frac': dig(cfg5, 'roofline_step', 'frac'), 'cfg5_step_GB': (dig(cfg5, 'roofline_step', 'algorithmic_bytes_per_step') or 0) / 1e9 or None,
-        'cfg5_run_to_run_identical': dig(cfg5, 'run_to_run_identical'),
-        'renderer_variants_iters_per_s': {k: dig(variants, k, 'iters_per_s') for k in ('sum', 'occlusion')} if variants else None,
-        'reference_trace': {k: tr.get(k) for k in ('first_iteration_argmin_differs', 'max_rel_diff_all', 'final_top1_equal',
-                                                     'argmin_mismatch_at_clear_gap')} if tr else None,
-        'reference_self_deviation': {k: dig(tr, 'reference_self_deviation', k) for k in (
-            'control_threads', 'first_iteration_references_disagree_on_argmin', 'hip_argmin_mismatch_where_references_agree',
-            'max_hip_dev_over_windowed_ref_dev', 'hip_dev_over_ref_dev_at_9')} if dig(tr, 'reference_self_deviation') else None}
+    if a.full:
+        tr = dig(ref_trace, 'trace') or {}
+        out['summary'] = {
+            'headline_iters_per_s': out.get('value'), 'headline_roofline_frac': dig(out, 'roofline', 'frac'),
+            'cpu_baseline_iters_per_s': dig(out, 'cpu_baseline', 'value'),
+            'cfg3_iters_per_s': dig(cfg3, 'value'), 'cfg3_roofline_frac': dig(cfg3, 'roofline', 'frac'),
+            'cfg3_scored_on_fused_engine': dig(cfg3, 'scored_on_fused_engine'),
+            'cfg5_ms_per_step': dig(cfg5, 'ms_per_step'), 'cfg5_peak_mem_GB': dig(cfg5, 'peak_mem_GB'), 'cfg5_peak_mem_step_GB': dig(cfg5, 'peak_mem_step_GB'),
+            'cfg5_roofline_step_frac': dig(cfg5, 'roofline_step', 'frac'), 'cfg5_step_GB': (dig(cfg5, 'roofline_step', 'algorithmic_bytes_per_step') or 0) / 1e9 or None,
+            'cfg5_run_to_run_identical': dig(cfg5, 'run_to_run_identical'),
+            'renderer_variants_iters_per_s': {k: dig(variants, k, 'iters_per_s') for k in ('sum', 'occlusion')} if variants else None,
+            'reference_trace': {k: tr.get(k) for k in ('first_iteration_argmin_differs', 'max_rel_diff_all', 'final_top1_equal',
+                                                         'argmin_mismatch_at_clear_gap')} if tr else None,
+            'reference_self_deviation': {k: dig(tr, 'reference_self_deviation', k) for k in (
+                'control_threads', 'first_iteration_references_disagree_on_argmin', 'hip_argmin_mismatch_where_references_agree',
+                'max_hip_dev_over_windowed_ref_dev', 'hip_dev_over_ref_dev_at_9')} if dig(tr, 'reference_self_deviation') else None}
     print(json.dumps(out), flush=True)
 
 

@@ -88,3 +88,23 @@ def test_bench_dumps_the_same_outputs_and_times_exactly_steps(tmp_path):
         assert x.dtype in (np.float32, np.float64) and x.shape == y.shape and np.isfinite(x).all(), n
         assert x.shape[0] == 4, n
         np.testing.assert_allclose(x, y, rtol=1e-5, atol=1e-6, err_msg=n)
+
+
+def test_full_is_off_by_default():
+    """A plain bench.py run is the headline alone; `--full` adds the secondary measurements and checks."""
+    import bench
+    assert bench.parse([]).full is False
+    assert bench.parse(['--full']).full is True
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_alone():
+    """Without --full the line carries the headline and its timing, and none of the secondary blocks: they are not run."""
+    d = _bench(['--gpus', '1', '--warmup', '1', '--steps', '2', '--size', '32', '--views', '2', '--samples', '4'])
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'timing', 'roofline'):
+        assert k in d, k
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['roofline']['launches_timed'] > 0
+    for k in ('cpu_baseline', 'alt', 'cfg3', 'cfg5', 'renderer_variants', 'reference_trace_parity', 'sharded_build', 'rccl',
+              'summary'):
+        assert k not in d, k
+    assert 'kernels' not in d['roofline_iter'] and d['roofline']['traffic_live'] is None

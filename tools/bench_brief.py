@@ -1,4 +1,5 @@
-"""Prints the few numbers of a bench.py JSON line that are looked at between runs: `python bench.py ... | python tools/bench_brief.py`."""
+"""Prints the few numbers of a bench.py JSON line that are looked at between runs: `python bench.py --full ... | python tools/bench_brief.py`
+(the per-kernel table `roofline_iter.kernels` comes with --full)."""
 import sys, json
 for l in sys.stdin:
     if l.startswith("{"):
