@@ -73,6 +73,14 @@ size_t lf_resample3d_bwd_coef_scratch_bytes(int N, int D, int H, int W);
 int lf_resample3d_bwd_coef(const float* gout, const float* vol, int vol_n, const float* coef,
                            float* gcoef, void* scratch, size_t scratch_bytes,
                            int N, int D, int H, int W, int C, void* stream);
+/* The same over N samples whose per-block voxel partition is the one a launch of part_n samples uses: every sample's 18
+ * sums are bit-identical to lf_resample3d_bwd_coef called with N = part_n on a group containing it, whatever N is (the
+ * multi-target pose loop launches T targets x part_n hypotheses and reproduces T single-target loops).  part_n >= 1;
+ * NULL pointers -> LF_EINVAL.  scratch: lf_resample3d_bwd_coef_part_scratch_bytes(N, part_n, D, H, W) bytes. */
+size_t lf_resample3d_bwd_coef_part_scratch_bytes(int N, int part_n, int D, int H, int W);
+int lf_resample3d_bwd_coef_part(const float* gout, const float* vol, int vol_n, const float* coef,
+                                float* gcoef, void* scratch, size_t scratch_bytes,
+                                int N, int D, int H, int W, int C, int part_n, void* stream);
 
 /* d(loss)/d(vol) (trilinear splat, fp32 atomics; training / encoder backward only).
  * gvol must be zero-initialised by the caller; with vol_n == 1 all samples accumulate into one
@@ -678,6 +686,23 @@ int lf_pose_loss_fwd_depth(const float* depth_and_logits, const float* coefs, co
 int lf_pose_loss_bwd_depth(const float* depth_and_logits, const float* coefs, const float* target_depth,
                            const float* target_mask, const float* gsums, float* gcrop, float* gcoefs,
                            void* scratch, size_t scratch_bytes, int N, int h, int w, int H, int W, void* stream);
+/* Several target frames in one launch: N = T * n samples grouped by target, sample i scored against frame i / n of
+ * target_depth / target_mask [T][H*W]; gsums is d(mean over the n samples OF THE SAME TARGET)/d(sums).  Otherwise as
+ * lf_pose_loss_fwd / _fwd_masked / _bwd, and per target the outputs (sums, losses, gsums, glogits, gcoefs 18..23) are
+ * bit-identical to the single-target entry point called on that target's n rows alone.  Scratch:
+ * lf_pose_loss_scratch_bytes(N, h, w, H, W).  NULL pointers, T < 1, n < 1 or N != T * n -> LF_EINVAL. */
+int lf_pose_loss_fwd_mt(const float* logits, const float* coefs, const float* target_depth,
+                        const float* target_mask, const float* weights, float* sums, float* losses,
+                        float* gsums, void* scratch, size_t scratch_bytes,
+                        int N, int T, int n, int h, int w, int H, int W, void* stream);
+int lf_pose_loss_fwd_masked_mt(const float* logits, const float* coefs, const float* target_depth,
+                               const float* target_mask, const float* weights, float* sums, float* losses,
+                               void* scratch, size_t scratch_bytes, int N, int T, int n, int h, int w, int H, int W,
+                               void* stream);
+int lf_pose_loss_bwd_mt(const float* logits, const float* coefs, const float* target_depth,
+                        const float* target_mask, const float* gsums, float* glogits, float* gcoefs,
+                        void* scratch, size_t scratch_bytes, int N, int T, int n, int h, int w, int H, int W,
+                        void* stream);
 
 /* Batched Adam / AdamW step over N independent rows of P parameters (pose/estimation.py:579-594,
  * 664-666).  step_size[n] = lr[n] / (1 - beta1^t) and bias_correction2_sqrt = sqrt(1 - beta2^t)

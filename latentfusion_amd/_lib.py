@@ -32,6 +32,8 @@ SIGNATURES = {
     'lf_resample3d_fwd': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_resample3d_bwd_coef_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
     'lf_resample3d_bwd_coef': (c_int, [P, P, c_int, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_resample3d_bwd_coef_part_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'lf_resample3d_bwd_coef_part': (c_int, [P, P, c_int, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_resample3d_bwd_vol_det_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     'lf_resample3d_bwd_vol_det': (c_int, [P, P, c_int, P, c_int, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_conv3x3_cout_padded': (c_int, [c_int]),
@@ -143,6 +145,10 @@ SIGNATURES = {
     'lf_pose_loss_fwd_depth': (c_int, [P, P, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_pose_loss_bwd_depth': (c_int, [P, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_pose_loss_fwd_masked': (c_int, [P, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_pose_loss_fwd_mt': (c_int, [P, P, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_pose_loss_fwd_masked_mt': (c_int, [P, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           P]),
+    'lf_pose_loss_bwd_mt': (c_int, [P, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_adam_step': (c_int, [P, P, P, P, P, P, c_float, c_float, c_float, c_float, c_float, c_int, c_int, P]),
     'lf_nchw_to_nhwc': (c_int, [P, P, c_int, c_int, c_long, P]),
     'lf_nhwc_to_nchw': (c_int, [P, P, c_int, c_int, c_long, P]),

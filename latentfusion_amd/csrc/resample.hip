@@ -1517,25 +1517,35 @@ static long staged_bwd_blocks(int D, int H, int W) {
   return (nt + STAGED_TPW - 1) / STAGED_TPW;
 }
 
-extern "C" size_t lf_resample3d_bwd_coef_scratch_bytes(int N, int D, int H, int W) {
+// part_n: the sample count the voxels per block are chosen for (N for lf_resample3d_bwd_coef; the caller's group size for
+// lf_resample3d_bwd_coef_part, whose samples then sum exactly as a launch of part_n samples would)
+static size_t bwd_coef_scratch_bytes(int N, int part_n, int D, int H, int W) {
   const long nvox = (long)D * H * W;
-  const int vpb = bwd_vox_per_block(nvox, N);
+  const int vpb = bwd_vox_per_block(nvox, part_n);
   const BwdTile bt = bwd_tile(vpb, D, H, W);
   const long nblk = (long)bt.ntx * bt.nty * bt.ntz;
   const long nblk_staged = staged_bwd_blocks(D, H, W);             // whichever form runs (lf_set_tuning) must fit
   return (size_t)N * (nblk > nblk_staged ? nblk : nblk_staged) * 18 * sizeof(float);
 }
 
-extern "C" int lf_resample3d_bwd_coef(const float* gout, const float* vol, int vol_n, const float* coef,
-                                      float* gcoef, void* scratch, size_t scratch_bytes,
-                                      int N, int D, int H, int W, int C, void* stream) {
-  lf_clear_error();
+extern "C" size_t lf_resample3d_bwd_coef_scratch_bytes(int N, int D, int H, int W) {
+  return bwd_coef_scratch_bytes(N, N, D, H, W);
+}
+
+extern "C" size_t lf_resample3d_bwd_coef_part_scratch_bytes(int N, int part_n, int D, int H, int W) {
+  if (N <= 0 || part_n <= 0) return 0;
+  return bwd_coef_scratch_bytes(N, part_n, D, H, W);
+}
+
+static int bwd_coef_launch(const float* gout, const float* vol, int vol_n, const float* coef,
+                           float* gcoef, void* scratch, size_t scratch_bytes,
+                           int N, int part_n, int D, int H, int W, int C, void* stream) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return LF_EINVAL;
   if (vol_n != 1 && vol_n != N) return LF_EINVAL;
-  if (scratch_bytes < lf_resample3d_bwd_coef_scratch_bytes(N, D, H, W)) return LF_ENOSPC;
+  if (scratch_bytes < bwd_coef_scratch_bytes(N, part_n, D, H, W)) return LF_ENOSPC;
   if ((long)D * H * W >= 0x7fffffffL) return LF_EINVAL;
   const long nvox = (long)D * H * W;
-  const int vpb = bwd_vox_per_block(nvox, N);
+  const int vpb = bwd_vox_per_block(nvox, part_n);
   const BwdTile bt = bwd_tile(vpb, D, H, W);
   const long nblk_l = (long)bt.ntx * bt.nty * bt.ntz;
   if (nblk_l * N > 0x7fffffffL) return LF_EINVAL;
@@ -1598,6 +1608,22 @@ extern "C" int lf_resample3d_bwd_coef(const float* gout, const float* vol, int v
   if (st) return st;
   hipLaunchKernelGGL(resample_bwd_coef_reduce, dim3(N), dim3(256), 0, s, partial, nblk, gcoef);
   return lf_launch_status();
+}
+
+extern "C" int lf_resample3d_bwd_coef(const float* gout, const float* vol, int vol_n, const float* coef,
+                                      float* gcoef, void* scratch, size_t scratch_bytes,
+                                      int N, int D, int H, int W, int C, void* stream) {
+  lf_clear_error();
+  return bwd_coef_launch(gout, vol, vol_n, coef, gcoef, scratch, scratch_bytes, N, N, D, H, W, C, stream);
+}
+
+extern "C" int lf_resample3d_bwd_coef_part(const float* gout, const float* vol, int vol_n, const float* coef,
+                                           float* gcoef, void* scratch, size_t scratch_bytes,
+                                           int N, int D, int H, int W, int C, int part_n, void* stream) {
+  lf_clear_error();
+  if (!gout || !vol || !coef || !gcoef || !scratch) return LF_EINVAL;
+  if (part_n <= 0 || N <= 0) return LF_EINVAL;
+  return bwd_coef_launch(gout, vol, vol_n, coef, gcoef, scratch, scratch_bytes, N, part_n, D, H, W, C, stream);
 }
 
 extern "C" int lf_resample3d_bwd_vol(const float* gout, const float* coef, int kind, float* gvol, int vol_n,

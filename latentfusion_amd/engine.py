@@ -658,27 +658,18 @@ class RenderLoopEngine:
             sums = torch.empty(n, 8, device=dev, dtype=torch.float32)
             losses = torch.empty(n, 8, device=dev, dtype=torch.float32)
             gsums = torch.empty(n, 8, device=dev, dtype=torch.float32)
-            if masked_depth:
-                check(L.lf_pose_loss_fwd_masked(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(),
-                                                self.weights.data_ptr(), sums.data_ptr(), losses.data_ptr(), scratch_l.data_ptr(),
-                                                scratch_l.numel() * 4, n, h_, w_, self.H, self.W, s), 'lf_pose_loss_fwd_masked')
-            else:
-                check(L.lf_pose_loss_fwd(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(),
-                                         self.weights.data_ptr(), sums.data_ptr(), losses.data_ptr(), gsums.data_ptr(),
-                                         scratch_l.data_ptr(), scratch_l.numel() * 4, n, h_, w_, self.H, self.W, s), 'lf_pose_loss_fwd')
+            self._loss_fwd(lg, coefs, sums, losses, gsums, scratch_l, masked_depth)
             if not need_grad:
                 if zt is not None:
                     # latent term of a ranking-only evaluation: cosine distance of the projected latent (estimation.py:112-116)
-                    lat = 1.0 - torch.cosine_similarity(zp.reshape(n, -1), zt.reshape(n, -1).to(zp.dtype), 1, 1e-8)
+                    lat = self._latent_distance(zp, zt, n)
                     losses[:, 5] = lat
                     losses[:, 4] += self.w_latent * lat
                 return losses, None
             glogits = torch.empty_like(lg)
             # (lf_pose_loss_bwd writes entries 18..23; 0..17 come from the resampler's coefficient gradient below)
             g_cf = torch.empty(n, NCOEF, device=dev, dtype=torch.float32)
-            check(L.lf_pose_loss_bwd(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(), gsums.data_ptr(),
-                                     glogits.data_ptr(), g_cf.data_ptr(), scratch_l.data_ptr(), scratch_l.numel() * 4,
-                                     n, h_, w_, self.H, self.W, s), 'lf_pose_loss_bwd')
+            self._loss_bwd(lg, coefs, gsums, glogits, g_cf, scratch_l)
             gp_explicit = None
             if explicit:
                 # heads, then the decoder's data gradients in reverse; each launch folds in the LeakyReLU' / PixelNorm' of the
@@ -709,14 +700,14 @@ class RenderLoopEngine:
         else:
             cf_leaf = coefs.detach().requires_grad_(need_grad)
             with torch.set_grad_enabled(need_grad):
-                total, losses = pose_loss(logits, cf_leaf, self.tdepth, self.tmask, self.weights, self.H, self.W)
+                total, losses = self._loss_autograd(logits, cf_leaf)
                 # latent term: cosine distance of the projected latent (what Photographer.forward returns as its latent)
-                lat = 1.0 - torch.cosine_similarity(zp_leaf.reshape(n, -1), zt.reshape(n, -1).to(zp_leaf.dtype), 1, 1e-8)
+                lat = self._latent_distance(zp_leaf, zt, n)
                 total = total + self.w_latent * lat
                 losses = losses.clone()
                 losses[:, 5] = lat.detach()
                 losses[:, 4] += self.w_latent * lat.detach()
-                objective = total.mean()                     # the optimised quantity (estimation.py:616-617)
+                objective = self._objective(total)           # the optimised quantity (estimation.py:616-617)
             if not need_grad:
                 return losses, None
             g_zp, g_cf = torch.autograd.grad(objective, [self._tail_leaf(act_leaf, zs_leaf, zp_leaf), cf_leaf])
@@ -790,16 +781,56 @@ class RenderLoopEngine:
                 g = self._wide_bwd(i, g, acts, norms, flags)
         return self._finish_backward(g, g_cf, cf20, jac, n, grad_scale, losses)
 
+    # ---- the pieces that see the target frame or partition a per-sample reduction by the batch
+    #      (engine_multi.MultiTargetEngine replaces them with their several-target forms) ----
+    def _loss_fwd(self, lg, coefs, sums, losses, gsums, scratch, masked_depth):
+        """Fused pose loss of the logits lg [n][h*w][2] against the target frame (lf_pose_loss_fwd / _fwd_masked)."""
+        L = _lib.lib()
+        n, _, h, w = lg.shape
+        if masked_depth:
+            check(L.lf_pose_loss_fwd_masked(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(),
+                                            self.weights.data_ptr(), sums.data_ptr(), losses.data_ptr(), scratch.data_ptr(),
+                                            scratch.numel() * 4, n, h, w, self.H, self.W, _s()), 'lf_pose_loss_fwd_masked')
+        else:
+            check(L.lf_pose_loss_fwd(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(),
+                                     self.weights.data_ptr(), sums.data_ptr(), losses.data_ptr(), gsums.data_ptr(),
+                                     scratch.data_ptr(), scratch.numel() * 4, n, h, w, self.H, self.W, _s()), 'lf_pose_loss_fwd')
+
+    def _loss_bwd(self, lg, coefs, gsums, glogits, g_cf, scratch):
+        """d/d(logits) and coefficient entries 18..23 of the loss formed by _loss_fwd (lf_pose_loss_bwd)."""
+        L = _lib.lib()
+        n, _, h, w = lg.shape
+        check(L.lf_pose_loss_bwd(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(), gsums.data_ptr(),
+                                 glogits.data_ptr(), g_cf.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
+                                 n, h, w, self.H, self.W, _s()), 'lf_pose_loss_bwd')
+
+    def _loss_autograd(self, logits, coefs):
+        """The fused loss as an autograd node (the latent-term path): (total (n,), components (n,8))."""
+        return pose_loss(logits, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W)
+
+    def _objective(self, total):
+        return total.mean()
+
+    def _latent_distance(self, zp, zt, n):
+        """Cosine distance of every hypothesis's projected latent to the target's latent code (estimation.py:112-116)."""
+        return 1.0 - torch.cosine_similarity(zp.reshape(n, -1), zt.reshape(n, -1).to(zp.dtype), 1, 1e-8)
+
+    def _bwd_coef(self, g, cf20, gcoef18, n):
+        """d/d(O2C output) -> gcoef18 [n][18] (lf_resample3d_bwd_coef)."""
+        L = _lib.lib()
+        S = self.S
+        nbytes = L.lf_resample3d_bwd_coef_scratch_bytes(n, S, S, S)
+        scratch = torch.empty(nbytes // 4 + 1, device=self.dev, dtype=torch.float32)
+        with ops._timed('resample_bwd_coef'):
+            check(L.lf_resample3d_bwd_coef(g.data_ptr(), self.z.data_ptr(), 1, cf20.data_ptr(), gcoef18.data_ptr(),
+                                           scratch.data_ptr(), scratch.numel() * 4, n, S, S, S, self.C, _s()), 'lf_resample3d_bwd_coef')
+
     def _finish_backward(self, g, g_cf, cf20, jac, n, grad_scale, losses):
         """d/d(O2C output) -> coefficient gradient -> camera parameters (lf_resample3d_bwd_coef, lf_camera_coefs_bwd)."""
         L = _lib.lib()
-        dev, S, s = self.dev, self.S, _s()
+        dev, s = self.dev, _s()
         gcoef18 = torch.empty(n, 18, device=dev, dtype=torch.float32)
-        nbytes = L.lf_resample3d_bwd_coef_scratch_bytes(n, S, S, S)
-        scratch = torch.empty(nbytes // 4 + 1, device=dev, dtype=torch.float32)
-        with ops._timed('resample_bwd_coef'):
-            check(L.lf_resample3d_bwd_coef(g.data_ptr(), self.z.data_ptr(), 1, cf20.data_ptr(), gcoef18.data_ptr(),
-                                           scratch.data_ptr(), scratch.numel() * 4, n, S, S, S, self.C, s), 'lf_resample3d_bwd_coef')
+        self._bwd_coef(g, cf20, gcoef18, n)
         gcoefs = g_cf.contiguous()
         gcoefs[:, :18] = gcoef18
         gparams = torch.empty(n, NPAR, device=dev, dtype=torch.float32)

@@ -717,6 +717,176 @@ class GradientPoseEstimator(PoseEstimator):
                 break
         return st['stat_history'], st['camera_history']
 
+    # ---- several target frames of one object in one render loop ----
+    def estimate_batch(self, z_obj, targets, cameras=None):
+        """Refines T single-frame targets of one object in ONE batched loop on engine_multi.MultiTargetEngine.  Entry t of
+        the returned list is what estimate(z_obj, targets[t], camera=cameras[t]) returns (the best cameras, plus stat_history /
+        camera_history per the flags) -- bit for bit on the kernels whose per-hypothesis arithmetic does not depend on the
+        batch size (tests/test_multi_target_estimator_gpu.py): the 16-channel renderers (SYN, occlusion) in conv_mode
+        'winograd' / 'fp32'.  NOT on renderers with wide (>= 64-channel) layers, the released architecture included, nor in
+        conv_mode 'f16x3': lf_wino_fused_gemm chooses its workgroup configuration and frequency split from the batch's tile
+        count, and the f16x3 gradient scales come from a batch-wide max, so a row's rounding follows its batch mates; Adam
+        amplifies such last-bit differences to percent-level loss differences within a few iterations.  `cameras`: T Camera
+        batches of equal length; None draws initial_pose + sample_cameras_with_estimate per target, in target order.
+
+        Every target keeps its own ranking, plateau state and convergence counter and runs at most num_iters iterations; a
+        converged target is frozen (its ranking and histories stop growing) while its rows keep running with the others.
+        All rows start together, so the one step counter of BatchedOptimizer (Adam's bias correction) is right for each.
+        More than MultiTargetEngine.MAX_ROWS rows run as successive groups of whole targets (`last_batch_groups` records
+        the group sizes).  Without an applicable engine (use_engine=False, a renderer the engine does not sequence, a
+        custom loss_func) the targets run one estimate() after another."""
+        targets = list(targets)
+        if not targets:
+            raise ValueError('estimate_batch needs at least one target')
+        for i, t in enumerate(targets):
+            if len(t) != 1:
+                raise ValueError(f'target {i} holds {len(t)} observations: the pose is estimated for one frame per target')
+        sizes = {tuple(t.depth.shape[-2:]) for t in targets}
+        if len(sizes) != 1:
+            raise ValueError(f'the targets differ in frame size: {sorted(sizes)}')
+        if cameras is not None:
+            cameras = list(cameras)
+            if len(cameras) != len(targets):
+                raise ValueError(f'{len(cameras)} camera batches for {len(targets)} targets')
+            counts = {len(c) for c in cameras}
+            if len(counts) != 1:
+                raise ValueError(f'every target needs the same number of hypotheses, got {sorted(counts)}')
+        if self.shard_hypotheses:
+            raise NotImplementedError('estimate_batch does not shard hypotheses over ranks')
+        if cameras is None:
+            cameras = [pu.sample_cameras_with_estimate(n=self.num_samples, camera_est=self.initial_pose(t)) for t in targets]
+        if not self._multi_engine_applies(z_obj):
+            self.last_batch_groups = [1] * len(targets)
+            return [self.estimate(z_obj, t, camera=c) for t, c in zip(targets, cameras)]
+        if self.engine_streams > 1 or self.engine_graph:
+            raise NotImplementedError('engine_streams / engine_graph are experimental.RenderLoopEngineX options')
+        from ..engine_multi import MultiTargetEngine
+        groups = self._batch_groups(len(targets), len(cameras[0]))
+        try:
+            with self._frozen_model():
+                zoomed = [c.zoom(None, self.model.input_size, self.model.camera_dist).to(self.device) for c in cameras]
+                if len({float(c.z_span) for c in zoomed}) != 1:
+                    raise ValueError("the targets' cameras differ in z_span")
+                dev_targets = [t.to(self.device) for t in targets]
+                self.last_batch_groups = [e - b for b, e in groups]
+                out = []
+                for b, e in groups:                                  # (whole targets per group)
+                    eng = MultiTargetEngine(self.model.photographer, z_obj, dev_targets[b:e], self.loss_weights,
+                                            conv_mode=self.conv_mode, fuse_projection=self.fuse_projection)
+                    out += self._run_batch(eng, dev_targets[b:e], zoomed[b:e])
+                    del eng
+                return out
+        finally:
+            self._engine_cache = None
+
+    @staticmethod
+    def _batch_groups(T, n):
+        """[(first, end)) target ranges of the batched loops: as many whole targets per loop as MultiTargetEngine.MAX_ROWS
+        rows allow (one loop unless T x n exceeds it)."""
+        from ..engine_multi import MultiTargetEngine
+        per = min(T, MultiTargetEngine.MAX_ROWS // n)
+        if per < 1:
+            raise ValueError(f'{n} hypotheses per target exceed the {MultiTargetEngine.MAX_ROWS} rows one render loop can carry')
+        return [(b, min(T, b + per)) for b in range(0, T, per)]
+
+    def _multi_engine_applies(self, z_obj):
+        """The conditions of PoseEstimator._engine_for, without building an engine."""
+        if not self.use_engine or self.loss_func is not default_pose_loss or not z_obj.is_cuda:
+            return False
+        from ..engine import RenderLoopEngine
+        ph = getattr(self.model, 'photographer', None)
+        if ph is None or not RenderLoopEngine.supports(ph, self.loss_weights):
+            return False
+        return all(k in RenderLoopEngine.LOSS_KEYS + ('latent',) for k in self.loss_schedules)
+
+    def _batch_launch(self, st, step):
+        """_engine_launch for the batched loop: forward + backward of all targets' rows of iteration `step` and the
+        asynchronous read-back of their losses and parameters."""
+        eng, P, n = st['engine'], st['P'], st['n']
+        optim_weights = self._engine_weights(st, step)
+        with torch.no_grad():
+            zt = None
+            if optim_weights.get('latent', 0.0) != 0.0 or self.loss_weights.get('latent', 0.0) != 0.0:
+                # each target's latent code under its own hypotheses (the single-target loop's call, per target)
+                codes = [self.model.compute_latent_code(tg, c) for tg, c in zip(st['targets'], st['cam_t'])]
+                zt = torch.cat([z.expand(n, *z.shape[1:]) if z.shape[0] == 1 else z for z in codes])
+            losses, gparams = eng.forward_backward(st['cam'], n, need_grad=True, z_target_latent=zt, params=P)
+            dev = torch.cat((losses[:, :6], P.detach()), dim=1)
+        slot = st.setdefault('pinned', {})
+        key = step & 1
+        if key not in slot or slot[key].shape != dev.shape:
+            slot[key] = torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True)
+        slot[key].copy_(dev, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        return {'step': step, 'gparams': gparams, 'host': slot[key], 'event': ev, 'weights': optim_weights}
+
+    def _run_batch(self, eng, targets, zoomed):
+        """The loop of _optimize_camera / _iterate_engine over T targets at once (one D2H transfer per iteration, the next
+        iteration enqueued before the host ranks this one); returns the per-target results of estimate()."""
+        from ..engine import camera_params
+        T, n = len(targets), len(zoomed[0])
+        P = torch.cat([camera_params(c) for c in zoomed]).detach().clone().contiguous()
+        P.requires_grad_(True)
+        cam = Camera.cat(zoomed)._like(log_quaternion=P[:, 0:3], translation=P[:, 3:6], viewport=P[:, 6:10])
+        st = {'engine': eng, 'P': P, 'n': n, 'cam': cam, 'targets': targets,
+              'cam_t': [cam[t * n:(t + 1) * n] for t in range(T)]}
+        opt = BatchedOptimizer(self.optimizer, [P])
+        sched = _PlateauLR(T * n, self.learning_rate, self.lr_reduce_patience, self.lr_reduce_threshold, self.lr_reduce_factor)
+        per = [{'ranking': [], 'converge_count': 0, 'stat_history': {}, 'camera_history': [], 'done': False,
+                'template_cpu': zoomed[t].to('cpu'), 'target_q': targets[t].camera.quaternion} for t in range(T)]
+        inflight = None
+        for step in range(self.num_iters):
+            cur = inflight if inflight is not None else self._batch_launch(st, step)
+            P.grad = cur['gparams']
+            opt.step(sched.lr)                                        # lr after scheduler.step(loss[t-1])
+            inflight = self._batch_launch(st, step + 1) if step + 1 < self.num_iters else None
+            cur['event'].synchronize()                                # the one D2H sync per iteration, all targets
+            host = cur['host'].clone()
+            optim_weights = cur['weights']
+            comp = {k: host[:, i] for i, k in enumerate(eng.LOSS_KEYS)}
+            if self.loss_weights.get('latent', 0.0) != 0.0 or 'latent' in self.loss_schedules:
+                comp['latent'] = host[:, 5]
+            rank = sum(self.loss_weights.get(k, 0.0) * v for k, v in comp.items())
+            for t, pt in enumerate(per):
+                if pt['done']:
+                    continue
+                r = slice(t * n, (t + 1) * n)
+                rank_t = rank[r]
+                detached = pt['template_cpu']._like(log_quaternion=host[r, 6:9].clone(), translation=host[r, 9:12].clone(),
+                                                    viewport=None)
+                if self.return_camera_history:
+                    pt['camera_history'].append((rank_t.clone(), detached))
+                delta = self._track_best_items(pt['ranking'], step, list(detached), rank_t.tolist())
+                if self.track_stats:
+                    angle = three.quaternion.angular_distance(detached.quaternion, pt['target_q'].cpu()).squeeze()
+                    trans = torch.norm(detached.translation - targets[t].camera.translation.cpu(), dim=1).squeeze()
+                    self._record_stat_dict(pt['stat_history'], {
+                        **{f'{k}_loss': v[r] for k, v in comp.items()}, **{f'{k}_weight': v for k, v in optim_weights.items()},
+                        'delta': delta, 'converge_count': pt['converge_count'], 'angle_dist': angle, 'trans_dist': trans,
+                        'optim_loss': host[r, 4].clone(), 'rank_loss': rank_t.clone()})
+                if delta < self.converge_threshold:
+                    pt['converge_count'] += 1
+                elif delta > self.converge_threshold:
+                    pt['converge_count'] = 0
+                pt['done'] = pt['converge_count'] >= self.converge_patience
+            # (a frozen target's rows keep their own plateau state and parameters: nothing it returns reads them again)
+            sched.step(rank.tolist())
+            if all(pt['done'] for pt in per):
+                break
+        out = []
+        for pt in per:
+            best = Camera.cat([c for c, _, _ in pt['ranking']])
+            if self.track_stats and self.return_camera_history:
+                out.append((best, pt['stat_history'], pt['camera_history']))
+            elif self.track_stats:
+                out.append((best, pt['stat_history']))
+            elif self.return_camera_history:
+                out.append((best, pt['camera_history']))
+            else:
+                out.append(best)
+        return out
+
     @classmethod
     def _record_stat(cls, history, key, value):
         value = value.detach().cpu() if torch.is_tensor(value) else torch.tensor(value)
