@@ -489,7 +489,8 @@ int lf_column_scale_bwd(const float* gout, const float* z, const float* w, float
  * element order -- the output uses the same one).
  *   lf_fuse_views_fwd  kind = LF_FUSE_MEAN | MAX | ABSMAX (signed value of largest magnitude) | MEDIAN (lower median,
  *                      torch.median; V <= 64): PoolFuser / pool_tensor, recon/fusion.py:45-57, functional.py:47-49.
- *                      idx (may be NULL; unused for MEAN) receives the selected view per element.
+ *                      idx (may be NULL; unused for MEAN) receives the selected view per element.  A NaN in any view is
+ *                      the result of every kind, as in torch (selections pick the first NaN view).
  *   lf_fuse_views_bwd  gz[v][i] = g[i] / V (MEAN) or g[i] * (v == idx[i]).
  *   lf_fuse_blend_fwd  BlendFuser.forward, recon/fusion.py:139-148: weights[v][row] = softmax_v(logits[v][row]),
  *                      out[row][:] = sum_v z[v][row][:] * weights[v][row]  (rows voxels, C % 4 == 0 channels-last;

@@ -184,7 +184,8 @@ __device__ __forceinline__ PixelFwd pixel_forward(const float* __restrict__ lg, 
     r.dhat = dl;
   } else {
     r.mask_on = sigmoidf_(ml) > 0.5f;
-    r.dn = r.mask_on ? tanhf(dl) : -1.f;                             // (tanh+1)*(mask>0.5)-1
+    // (tanh+1)*(mask>0.5)-1: -1 under a closed mask, except that NaN * 0 stays NaN there (tanh(+-inf) = +-1 is finite)
+    r.dn = r.mask_on ? tanhf(dl) : (dl != dl ? dl : -1.f);
     r.dhat = r.dn * cf[4] + cf[5];
     if constexpr (MODE == 1) r.dhat *= sigmoidf_(ml);
   }
@@ -263,10 +264,12 @@ __global__ void pose_loss_finish_kernel(const float* __restrict__ partial, int n
     const float w_depth = weights[0], w_ov = weights[1], w_iou = weights[2], w_mask = weights[3];
     const float inv_hw = 1.f / (float)HW;
     const float depth = S0 * inv_hw;
-    const float num = fmaxf(S1, 1e-5f), den = fmaxf(S2, 1e-4f);
+    // torch.clamp(min=): a NaN sum stays NaN (fmaxf would return the floor and report a finite term for a NaN render)
+    auto clamp_min = [](float v, float lo) { return v < lo ? lo : v; };
+    const float num = clamp_min(S1, 1e-5f), den = clamp_min(S2, 1e-4f);
     const float ov = num / den;
     const float uni = S3 + S5 - S4;
-    const float iou = logf(fmaxf(uni, 1e-4f)) - logf(fmaxf(S4, 1e-4f));
+    const float iou = logf(clamp_min(uni, 1e-4f)) - logf(clamp_min(S4, 1e-4f));
     const float mask = S6 * inv_hw;
     losses[n * 8 + 0] = depth; losses[n * 8 + 1] = ov; losses[n * 8 + 2] = iou; losses[n * 8 + 3] = mask;
     losses[n * 8 + 4] = w_depth * depth + w_ov * ov + w_iou * iou + w_mask * mask;      // rank / optim loss
@@ -392,7 +395,11 @@ __global__ void __launch_bounds__(256) pose_loss_bwd_cols_kernel(
     const float dl = logits[o], ml = logits[o + 1];
     const float th = tanhf(dl);
     const bool on = sigmoidf_(ml) > 0.5f;
-    glogits[o] = on ? sd * a_depth * (1.f - th * th) : 0.f;     // d dhat/d dn = a_depth; (mask>0.5) gate has no gradient
+    // d dhat/d dn = a_depth; the (mask>0.5) gate has no gradient: 0 under a closed mask, where a NaN logit keeps its NaN
+    // as in the forward ((1 - tanh^2) * 0 of the reference's autograd).  Two statements on purpose: with the NaN select folded
+    // into the first expression the compiler contracts the product differently and finite gradients change in the last bit.
+    const float g = on ? sd * a_depth * (1.f - th * th) : 0.f;
+    glogits[o] = (!on && dl != dl) ? dl : g;
   }
   glogits[o + 1] = sm;
 }

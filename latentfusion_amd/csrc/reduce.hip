@@ -309,9 +309,13 @@ __global__ void __launch_bounds__(256) fuse_views_fwd_kernel(const T* __restrict
     for (; v < V; ++v) consider(__builtin_nontemporal_load(z + i + (long)v * vstride_vec), v);
   } else {
     // lower median = element of rank (V-1)/2 (torch.median); rank by counting, ties by view index
+    // A NaN orders with nothing (every comparison below is false for it, so ranks would collide on a finite value):
+    // the first NaN view is the result and the selected view, as torch.median, the host path and the sharded form
+    // of the same pool return it, and as the max / abs_max branch above does.
     const int want = (V - 1) / 2;
+    bool has_nan[O::W];
 #pragma unroll
-    for (int e = 0; e < O::W; ++e) sel[e] = 0;
+    for (int e = 0; e < O::W; ++e) { sel[e] = 0; has_nan[e] = false; }
     r = z[i];
     for (int v = 0; v < V; ++v) {
       const T c = z[i + v * vstride_vec];
@@ -327,8 +331,12 @@ __global__ void __launch_bounds__(256) fuse_views_fwd_kernel(const T* __restrict
         }
       }
 #pragma unroll
-      for (int e = 0; e < O::W; ++e)
-        if (rank[e] == want) { O::set(r, e, O::get(c, e)); sel[e] = v; }
+      for (int e = 0; e < O::W; ++e) {
+        const float b = O::get(c, e);
+        const bool first_nan = b != b && !has_nan[e];
+        if (first_nan || (!has_nan[e] && rank[e] == want)) { O::set(r, e, b); sel[e] = v; }
+        has_nan[e] = has_nan[e] || first_nan;
+      }
     }
   }
   out[i] = r;

@@ -47,6 +47,70 @@ def test_cabi_exports_every_declared_symbol():
     assert L.lf_resample3d_bwd_coef_scratch_bytes(8, 128, 128, 128) == 8 * 512 * 18 * 4
 
 
+_C_SCALARS = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'unsigned': ctypes.c_uint,
+              'unsigned int': ctypes.c_uint, 'size_t': ctypes.c_size_t}
+
+
+def _ctype_of(decl, is_return=False):
+    """C declaration of one parameter (with or without its name) or of a return type -> the ctypes type that binds it."""
+    decl = decl.strip()
+    if '*' in decl:
+        base = decl[:decl.index('*')].replace('const', ' ').split()
+        assert decl.count('*') == 1 and base, decl
+        return ctypes.c_char_p if base == ['char'] else ctypes.c_void_p
+    tokens = [t for t in decl.split() if t != 'const']
+    if not is_return and len(tokens) > 1 and ' '.join(tokens) not in _C_SCALARS:
+        tokens = tokens[:-1]                                       # the parameter's name
+    name = ' '.join(tokens)
+    if is_return and name == 'void':
+        return None
+    assert name in _C_SCALARS, f'no ctypes mapping for {decl!r}'
+    return _C_SCALARS[name]
+
+
+def _header_prototypes(fname):
+    """name -> (restype, [argtypes]) of every prototype in include/<fname>."""
+    text = open(os.path.join(ROOT, 'include', fname)).read()
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*', ' ', text)
+    text = '\n'.join(ln for ln in text.split('\n') if not ln.lstrip().startswith('#'))
+    text = text.replace('extern "C" {', ' ')
+    protos = {}
+    for stmt in text.split(';'):
+        stmt = ' '.join(stmt.replace('}', ' ').split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r'(.+?)\b(lf_[a-z0-9_]+)\s*\((.*)\)', stmt)
+        assert m, f'{fname}: cannot parse {stmt!r}'
+        ret, name, args = m.group(1), m.group(2), m.group(3).strip()
+        assert name not in protos, name
+        argtypes = [] if args in ('', 'void') else [_ctype_of(a) for a in args.split(',')]
+        protos[name] = (_ctype_of(ret, is_return=True), argtypes)
+    return protos
+
+
+def test_ctypes_table_matches_the_header_prototypes():
+    """Arity, order and type of every binding in _lib.SIGNATURES / EXPERIMENTAL_SIGNATURES against the prototype in the
+    header it mirrors (pointer -> c_void_p, char* -> c_char_p, scalars by name).  The name-only comparison above does not
+    notice an `int` bound as c_long or a dropped argument; ctypes then corrupts the call silently."""
+    from latentfusion_amd import _lib
+    assert _ctype_of('const float* x') is ctypes.c_void_p and _ctype_of('char* buf') is ctypes.c_char_p
+    assert _ctype_of('unsigned flags') is ctypes.c_uint and _ctype_of('long') is ctypes.c_long
+    assert _ctype_of('void', is_return=True) is None and _ctype_of('size_t', is_return=True) is ctypes.c_size_t
+    total = 0
+    for fname, table in (('lf_hip.h', _lib.SIGNATURES), ('lf_hip_experimental.h', _lib.EXPERIMENTAL_SIGNATURES)):
+        protos = _header_prototypes(fname)
+        assert set(protos) == set(table), (fname, set(protos) ^ set(table))
+        for name, (res, args) in protos.items():
+            bres, bargs = table[name]
+            assert bres is res, (name, 'return', bres, res)
+            assert len(bargs) == len(args), (name, 'arity', len(bargs), len(args))
+            for i, (b, a) in enumerate(zip(bargs, args)):
+                assert b is a, (name, 'argument', i, b, a)
+        total += len(protos)
+    assert total == len(_lib.SIGNATURES) + len(_lib.EXPERIMENTAL_SIGNATURES) >= 127
+
+
 def test_product_never_imports_the_oracle():
     pkg = os.path.join(ROOT, 'latentfusion_amd')
     for dirpath, _, files in os.walk(pkg):
