@@ -17,45 +17,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
-from .engine import NCOEF, RenderLoopEngine, _s
-
-
-class _PoseLossMT(torch.autograd.Function):
-    """_PoseLoss over [T][H*W] target frames: returns (total (N,), components (N,8)); d(total) is taken per row."""
-
-    @staticmethod
-    def forward(ctx, logits, coefs, tdepth, tmask, weights, H, W, T):
-        L = _lib.lib()
-        lg = ops.cl(logits)
-        N, _, h, w = lg.shape
-        n = N // T
-        nbytes = L.lf_pose_loss_scratch_bytes(N, h, w, H, W)
-        scratch = torch.empty(nbytes // 4 + 1, device=lg.device, dtype=torch.float32)
-        sums = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
-        losses = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
-        gsums = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
-        cf = coefs.detach().contiguous()
-        check(L.lf_pose_loss_fwd_mt(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), weights.data_ptr(),
-                                    sums.data_ptr(), losses.data_ptr(), gsums.data_ptr(), scratch.data_ptr(),
-                                    scratch.numel() * 4, N, T, n, h, w, H, W, _s()), 'lf_pose_loss_fwd_mt')
-        ctx.save_for_backward(lg, cf, tdepth, tmask, gsums, scratch)
-        ctx.dims = (N, T, n, h, w, H, W)
-        ctx.mark_non_differentiable(losses)
-        return losses[:, 4].clone(), losses
-
-    @staticmethod
-    def backward(ctx, g_total, _g_losses):
-        L = _lib.lib()
-        lg, cf, tdepth, tmask, gsums, scratch = ctx.saved_tensors
-        N, T, n, h, w, H, W = ctx.dims
-        # gsums were formed for d(mean over the row's target); rescale to the incoming per-row gradient (as _PoseLoss)
-        gs = (gsums * (g_total * n).unsqueeze(1)).contiguous()
-        glogits = torch.empty_like(lg)
-        gcoefs = torch.zeros(N, NCOEF, device=lg.device, dtype=torch.float32)
-        check(L.lf_pose_loss_bwd_mt(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), gs.data_ptr(),
-                                    glogits.data_ptr(), gcoefs.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
-                                    N, T, n, h, w, H, W, _s()), 'lf_pose_loss_bwd_mt')
-        return glogits, gcoefs, None, None, None, None, None, None
+from .engine import RenderLoopEngine, _PoseLoss, _pose_loss_bwd, _pose_loss_fwd, _s
 
 
 class MultiTargetEngine(RenderLoopEngine):
@@ -120,42 +82,22 @@ class MultiTargetEngine(RenderLoopEngine):
             if z_target_latent.shape[0] != self.T:
                 raise ValueError(f'z_target_latent has {z_target_latent.shape[0]} rows: expected {N} or {self.T}')
             z_target_latent = z_target_latent.repeat_interleave(n, dim=0)
-        # (frozen here, so that the base class's own freeze-and-recurse branch, whose call has no `n`, is never taken)
-        live = [p for p in self._params if p.requires_grad]
-        for p in live:
-            p.requires_grad_(False)
         self._n = n
         try:
             return RenderLoopEngine.forward_backward(self, camera, need_grad, z_target_latent, params, masked_depth)
         finally:
             self._n = None
-            for p in live:
-                p.requires_grad_(True)
 
     # ---- the per-target pieces ----
-    def _loss_fwd(self, lg, coefs, sums, losses, gsums, scratch, masked_depth):
-        L = _lib.lib()
-        N, _, h, w = lg.shape
-        if masked_depth:
-            check(L.lf_pose_loss_fwd_masked_mt(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(),
-                                               self.weights.data_ptr(), sums.data_ptr(), losses.data_ptr(), scratch.data_ptr(),
-                                               scratch.numel() * 4, N, self.T, self._n, h, w, self.H, self.W, _s()),
-                  'lf_pose_loss_fwd_masked_mt')
-        else:
-            check(L.lf_pose_loss_fwd_mt(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(),
-                                        self.weights.data_ptr(), sums.data_ptr(), losses.data_ptr(), gsums.data_ptr(),
-                                        scratch.data_ptr(), scratch.numel() * 4, N, self.T, self._n, h, w, self.H, self.W, _s()),
-                  'lf_pose_loss_fwd_mt')
+    def _loss_fwd(self, lg, coefs, masked_depth):
+        return _pose_loss_fwd(lg, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W, masked_depth, (self.T, self._n))
 
     def _loss_bwd(self, lg, coefs, gsums, glogits, g_cf, scratch):
-        L = _lib.lib()
-        N, _, h, w = lg.shape
-        check(L.lf_pose_loss_bwd_mt(lg.data_ptr(), coefs.data_ptr(), self.tdepth.data_ptr(), self.tmask.data_ptr(),
-                                    gsums.data_ptr(), glogits.data_ptr(), g_cf.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
-                                    N, self.T, self._n, h, w, self.H, self.W, _s()), 'lf_pose_loss_bwd_mt')
+        _pose_loss_bwd(lg, coefs, self.tdepth, self.tmask, gsums, glogits, g_cf, scratch, self.H, self.W, (self.T, self._n))
 
     def _loss_autograd(self, logits, coefs):
-        return _PoseLossMT.apply(logits, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W, self.T)
+        # (_PoseLoss over [T][H*W] target frames: d(total) is taken per row)
+        return _PoseLoss.apply(logits, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W, (self.T, self._n))
 
     def _objective(self, total):
         # sum over the targets of each target's mean: every row's gradient is what its own single-target loop sees

@@ -4,7 +4,10 @@ A/B reference paths, kept for tools/ and the tests that pin them -- nothing on a
   conv3d_c16_bf16          the first bf16 16 -> 16 kernel (the ring form lf_conv3d_c16_ring_bf16 is what the training step runs)
   conv3d_c16_wino_split    Winograd with three-term f16 products (engine conv_mode 'winograd_f16x3')
   conv3d_c16_wino_projbwd  factor projection backward fused into the first data-gradient conv (1.45 vs 0.40 + 0.95 ms)
-  conv3d_wino_gemm         wide Winograd convolution in three stages on the library GEMM (ops.WIDE_CONV_MODE = 'bmm')"""
+  conv3d_wino_gemm         wide Winograd convolution in three stages on the library GEMM (ops.WIDE_CONV_MODE = 'bmm')
+
+The second half holds RenderLoopEngineX, the engine with the measured-and-rejected variants.  Its kernel family for conv_mode
+'winograd_f16x3' joins the engine's camera-block plan through select_camera_blocks here, which the class names in `_select_blocks`."""
 import math  # noqa: F401
 
 import torch
@@ -155,161 +158,140 @@ def _conv2d_wino_gemm(x, U, bias, he, flags):
 # Render-loop engine variants that were built, measured and NOT adopted (evidence under profiles/): kept so that the A/B
 # tools and the tests that pin their correctness keep running.  The estimators select this class when one of its options
 # is asked for (conv_mode='winograd_f16x3', fuse_projection containing 'bwd', engine_streams > 1, engine_graph=True).
+# The experimental kernel family plugs into the engine's camera-block plan: select_camera_blocks below answers for
+# 'winograd_f16x3' and hands every other mode to engine.select_camera_blocks; RenderLoopEngineX names it in `_select_blocks`.
 # ---------------------------------------------------------------------------------------------------------------------------
-def _engine_base():
-    from .engine import RenderLoopEngine
-    return RenderLoopEngine
+from . import engine as _engine  # noqa: E402  (engine.py imports nothing from here)
 
 
-def make_engine_x():
-    Base = _engine_base()
+class _Winograd16F16x3(_engine._Direct16F16x3):
+    """16 -> 16 blocks: Winograd with fp32 transforms and three-term f16 products (lf_conv3d_c16_wino_split); gradient bounds as
+    the direct f16x3 family, plus a bound of the first layer's input."""
+    _pack, _conv = staticmethod(pack_conv3d_c16_wino_split), staticmethod(conv3d_c16_wino_split)
 
-    class RenderLoopEngineX(Base):
-        """RenderLoopEngine plus:
-          conv_mode 'winograd_f16x3'   Winograd with fp32 transforms and three-term f16 products (22-bit operands: narrower
-                                       arithmetic than the reference's fp32 by construction);
-          fuse_projection 'bwd'        projection backward inside the first data-gradient conv (1.45 vs 0.40 + 0.95 ms,
-                                       profiles/r04_proj_fuse_ab.txt);
-          set_streams(k)               hypothesis groups on k HIP streams (no gain, profiles/r03_stream_groups_ab.json);
-          forward_backward_graph       hipGraph replay of one evaluation (186.8 vs 187.0 it/s, profiles/r04_hipgraph_ab.json)."""
-        CONV_MODES = Base.CONV_MODES + ('winograd_f16x3',)
-        FUSE_FORMS = ('fwd', 'bwd')
-
-        def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None):
-            wino_split = conv_mode == 'winograd_f16x3'
-            super().__init__(photographer, z_obj, target_obs, loss_weights, 'f16x3' if wino_split else conv_mode, fuse_projection)
-            if wino_split:
-                if self.generic_tail:
-                    raise NotImplementedError("the split-precision conv modes drive the plain 'factor' renderer only")
-                self.conv_mode = 'winograd_f16x3'
-                self.split = [(pack_conv3d_c16_wino_split(w), pack_conv3d_c16_wino_split(w, transpose=True)) for w, *_ in self.convs]
-                # trilinear resampling is a convex combination: max|x0| <= max|z_obj|
-                self.z_amax = ops.amax_buffer(self.z.abs().max(), self.dev)
-            self.streams, self._side_streams = 1, []
-            self._packs_built = False
-            self._graph = None
-
-        def _conv_fwd(self, li, x, flags, depth_inner=False):
-            if self.conv_mode == 'winograd_f16x3':
-                _w, b, he, _wp, _wt = self.convs[li]
-                return conv3d_c16_wino_split(x, self.split[li][0], b, he, flags, amax_in=self.z_amax if li == 0 else None) + (None,)
-            return super()._conv_fwd(li, x, flags, depth_inner)
-
-        def _conv_bwd(self, i, g, prev, amax):
-            if self.conv_mode == 'winograd_f16x3':
-                he = self.convs[i][2]
-                return conv3d_c16_wino_split(g, self.split[i][1], None, he, 0, prev=prev, amax_in=amax[i + 1], amax_out=amax[i])[0]
-            return super()._conv_bwd(i, g, prev, amax)
-
-        def _proj_bwd_fused(self, gp, acts, norms, flags):
-            if 'bwd' not in self.fuse_projection:
-                return None
-            nconv = len(self.convs)
-            i = nconv - 1
-            prev = (acts[i], norms[i - 1], flags) if i > 0 else None
-            g = conv3d_c16_wino_projbwd(gp, self.proj_fused[1], self.proj[2], acts[nconv], norms[nconv - 1], flags,
-                                        self.wino[i][1], self.convs[i][2], prev=prev)
-            return g, nconv - 2
-
-        def set_streams(self, k):
-            """Number of hypothesis groups evaluated concurrently on separate HIP streams (1 = everything on the current stream)."""
-            self.streams = max(1, int(k))
-            while len(self._side_streams) < self.streams:
-                self._side_streams.append(torch.cuda.Stream(device=self.dev))
-            return self
-
-        def _run(self, params, intr, z_span, need_grad, zt, masked_depth):
-            """With `streams` = k > 1 the N hypotheses are evaluated as k independent groups on k HIP streams: hypotheses do not
-            interact (the reference optimises N separate cameras, estimation.py:580-594); same kernels, same per-hypothesis
-            arithmetic: bit-identical to the single-stream evaluation (tests/test_engine_gpu.py)."""
-            n = params.shape[0]
-            k = min(self.streams, n)
-            if k > 1 and not self._packs_built:
-                # weight packs are memoised on the parameters when the HOST enqueues the packing kernels (ops._cached), with no
-                # stream attached: the first evaluation therefore runs on the current stream alone (ADVICE r03)
-                k = 1
-            self._packs_built = True
-            if k <= 1:
-                return self._forward_backward_group(params, intr, z_span, need_grad, 1.0, zt, masked_depth)
-            main = torch.cuda.current_stream()
-            ready = torch.cuda.Event()
-            ready.record(main)
-            bounds = [(n * i) // k for i in range(k + 1)]
-            outs = []
-            for i in range(k):
-                b, e = bounds[i], bounds[i + 1]
-                st = self._side_streams[i]
-                st.wait_event(ready)
-                params.record_stream(st)                           # (made on the main stream, read on the side streams)
-                intr.record_stream(st)
-                if zt is not None:
-                    zt.record_stream(st)
-                with torch.cuda.stream(st):
-                    # d(mean over all N) = (group size / N) x d(mean over the group)
-                    lo, gp = self._forward_backward_group(params[b:e], intr[b:e], z_span, need_grad, (e - b) / n,
-                                                          zt[b:e] if zt is not None else None, masked_depth)
-                    done = torch.cuda.Event()
-                    done.record(st)
-                outs.append((lo, gp, done))
-            for lo, gp, done in outs:
-                main.wait_event(done)
-                lo.record_stream(main)
-                if gp is not None:
-                    gp.record_stream(main)
-            losses = torch.cat([o[0] for o in outs], dim=0)
-            gparams = torch.cat([o[1] for o in outs], dim=0) if need_grad else None
-            return losses, gparams
-
-        def forward_backward_graph(self, camera, params):
-            """forward_backward(need_grad=True) replayed from a hipGraph (stream capture through torch.cuda.graph of the C-ABI
-            launches).  Conditions: `params` is the SAME (N,10) device tensor on every call, the loss weights have not been
-            re-set, no latent term, one stream, no kernel timer.  Returns the graph's static output tensors (overwritten by the
-            next replay).  A model whose renderer parameters still require grad is frozen for warm-up and capture (replays need
-            no autograd state)."""
-            from .engine import camera_intrinsics
-            if ops.KERNEL_TIMER is not None or self.streams > 1 or self.w_latent != 0.0:
-                return self.forward_backward(camera, need_grad=True, params=params)
-            pc = params.detach()
-            if not pc.is_contiguous():
-                raise ValueError('forward_backward_graph needs a contiguous (N,10) parameter block')
-            K = camera.intrinsic
-            if self._intr is None or self._intr[0] is not K or self._intr[1] != K._version:
-                self._intr = (K, K._version, camera_intrinsics(camera))
-            intr = self._intr[2]
-            # (the captured kernels hold raw pointers: the graph is valid for exactly these tensors -- compared by identity, and
-            # kept alive in the tuple below, so a freed buffer's address cannot come back as a false match)
-            key = (pc.data_ptr(), tuple(pc.shape), intr.data_ptr(), float(camera.z_span))
-            if self._graph is None or self._graph[0] != key or self._graph[6] is not self.weights or self._graph[7] is not params:
-                live = [p for p in self._params if p.requires_grad]
-                for p in live:
-                    p.requires_grad_(False)
-                try:
-                    cur = torch.cuda.current_stream()
-                    side = torch.cuda.Stream(device=self.dev)
-                    side.wait_stream(cur)
-                    with torch.cuda.stream(side), torch.no_grad():        # warm-up: weight packs, allocator pools, code objects
-                        for _ in range(2):
-                            self._forward_backward_group(pc, intr, float(camera.z_span), True, 1.0)
-                    cur.wait_stream(side)
-                    self._packs_built = True
-                    g = torch.cuda.CUDAGraph()
-                    with torch.no_grad(), torch.cuda.graph(g):
-                        lo, gp = self._forward_backward_group(pc, intr, float(camera.z_span), True, 1.0)
-                finally:
-                    for p in live:
-                        p.requires_grad_(True)
-                self._graph = (key, g, lo, gp, pc, intr, self.weights, params)        # (keeps the captured inputs alive)
-            self._graph[1].replay()
-            return self._graph[2], self._graph[3]
-    return RenderLoopEngineX
+    def __init__(self, convs, z):
+        super().__init__(convs, z)
+        # trilinear resampling is a convex combination: max|x0| <= max|z_obj|
+        self.x0_bound = ops.amax_buffer(z.abs().max(), self.dev)
 
 
-_ENGINE_X = None
+def select_camera_blocks(conv_mode, shapes, C):
+    """engine.select_camera_blocks plus conv_mode 'winograd_f16x3' (16 -> 16 blocks only)."""
+    if conv_mode != 'winograd_f16x3':
+        return _engine.select_camera_blocks(conv_mode, shapes, C)
+    if not _engine._block_kinds(shapes, C)[0]:
+        raise NotImplementedError('winograd_f16x3 mode is implemented for 16->16 camera blocks')
+    return conv_mode, _Winograd16F16x3
 
 
-def RenderLoopEngineX(*args, **kwargs):
-    """Constructs the experimental engine (the class is built on first use: engine.py imports nothing from here)."""
-    global _ENGINE_X
-    if _ENGINE_X is None:
-        _ENGINE_X = make_engine_x()
-    return _ENGINE_X(*args, **kwargs)
+class RenderLoopEngineX(_engine.RenderLoopEngine):
+    """RenderLoopEngine plus:
+      conv_mode 'winograd_f16x3'   Winograd with fp32 transforms and three-term f16 products (22-bit operands: narrower
+                                   arithmetic than the reference's fp32 by construction);
+      fuse_projection 'bwd'        projection backward inside the first data-gradient conv (1.45 vs 0.40 + 0.95 ms,
+                                   profiles/r04_proj_fuse_ab.txt);
+      set_streams(k)               hypothesis groups on k HIP streams (no gain, profiles/r03_stream_groups_ab.json);
+      forward_backward_graph       hipGraph replay of one evaluation (186.8 vs 187.0 it/s, profiles/r04_hipgraph_ab.json)."""
+    CONV_MODES = _engine.CONV_MODES + ('winograd_f16x3',)
+    FUSE_FORMS = ('fwd', 'bwd')
+    _select_blocks = staticmethod(select_camera_blocks)
+
+    def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None):
+        super().__init__(photographer, z_obj, target_obs, loss_weights, conv_mode, fuse_projection)
+        self.streams, self._side_streams = 1, []
+        self._packs_built = False
+        self._graph = None
+
+    def _proj_bwd_fused(self, gp, acts, norms, flags):
+        if 'bwd' not in self.fuse_projection:
+            return None
+        i = self.nconv - 1
+        prev = (acts[i], norms[i - 1], flags) if i > 0 else None
+        g = conv3d_c16_wino_projbwd(gp, self.proj_fused[1], self.proj[2], acts[i + 1], norms[i], flags,
+                                    self.plan.packs[i][1], self.plan.he[i], prev=prev)
+        return g, i - 1
+
+    def set_streams(self, k):
+        """Number of hypothesis groups evaluated concurrently on separate HIP streams (1 = everything on the current stream)."""
+        self.streams = max(1, int(k))
+        while len(self._side_streams) < self.streams:
+            self._side_streams.append(torch.cuda.Stream(device=self.dev))
+        return self
+
+    def _run(self, params, intr, z_span, need_grad, zt, masked_depth):
+        """With `streams` = k > 1 the N hypotheses are evaluated as k independent groups on k HIP streams: hypotheses do not
+        interact (the reference optimises N separate cameras, estimation.py:580-594); same kernels, same per-hypothesis
+        arithmetic: bit-identical to the single-stream evaluation (tests/test_engine_gpu.py)."""
+        n = params.shape[0]
+        k = min(self.streams, n)
+        if k > 1 and not self._packs_built:
+            # weight packs are memoised on the parameters when the HOST enqueues the packing kernels (ops._cached), with no
+            # stream attached: the first evaluation therefore runs on the current stream alone (ADVICE r03)
+            k = 1
+        self._packs_built = True
+        if k <= 1:
+            return self._forward_backward_group(params, intr, z_span, need_grad, 1.0, zt, masked_depth)
+        main = torch.cuda.current_stream()
+        ready = torch.cuda.Event()
+        ready.record(main)
+        bounds = [(n * i) // k for i in range(k + 1)]
+        outs = []
+        for i in range(k):
+            b, e = bounds[i], bounds[i + 1]
+            st = self._side_streams[i]
+            st.wait_event(ready)
+            params.record_stream(st)                           # (made on the main stream, read on the side streams)
+            intr.record_stream(st)
+            if zt is not None:
+                zt.record_stream(st)
+            with torch.cuda.stream(st):
+                # d(mean over all N) = (group size / N) x d(mean over the group)
+                lo, gp = self._forward_backward_group(params[b:e], intr[b:e], z_span, need_grad, (e - b) / n,
+                                                      zt[b:e] if zt is not None else None, masked_depth)
+                done = torch.cuda.Event()
+                done.record(st)
+            outs.append((lo, gp, done))
+        for lo, gp, done in outs:
+            main.wait_event(done)
+            lo.record_stream(main)
+            if gp is not None:
+                gp.record_stream(main)
+        losses = torch.cat([o[0] for o in outs], dim=0)
+        gparams = torch.cat([o[1] for o in outs], dim=0) if need_grad else None
+        return losses, gparams
+
+    def forward_backward_graph(self, camera, params):
+        """forward_backward(need_grad=True) replayed from a hipGraph (stream capture through torch.cuda.graph of the C-ABI
+        launches).  Conditions: `params` is the SAME (N,10) device tensor on every call, the loss weights have not been
+        re-set, no latent term, one stream, no kernel timer.  Returns the graph's static output tensors (overwritten by the
+        next replay).  A model whose renderer parameters still require grad is frozen for warm-up and capture (replays need
+        no autograd state)."""
+        if ops.KERNEL_TIMER is not None or self.streams > 1 or self.w_latent != 0.0:
+            return self.forward_backward(camera, need_grad=True, params=params)
+        pc = params.detach()
+        if not pc.is_contiguous():
+            raise ValueError('forward_backward_graph needs a contiguous (N,10) parameter block')
+        K = camera.intrinsic
+        if self._intr is None or self._intr[0] is not K or self._intr[1] != K._version:
+            self._intr = (K, K._version, _engine.camera_intrinsics(camera))
+        intr = self._intr[2]
+        # (the captured kernels hold raw pointers: the graph is valid for exactly these tensors -- compared by identity, and
+        # kept alive in the tuple below, so a freed buffer's address cannot come back as a false match)
+        key = (pc.data_ptr(), tuple(pc.shape), intr.data_ptr(), float(camera.z_span))
+        if self._graph is None or self._graph[0] != key or self._graph[6] is not self.weights or self._graph[7] is not params:
+            with _engine._frozen(self._params):
+                cur = torch.cuda.current_stream()
+                side = torch.cuda.Stream(device=self.dev)
+                side.wait_stream(cur)
+                with torch.cuda.stream(side), torch.no_grad():        # warm-up: weight packs, allocator pools, code objects
+                    for _ in range(2):
+                        self._forward_backward_group(pc, intr, float(camera.z_span), True, 1.0)
+                cur.wait_stream(side)
+                self._packs_built = True
+                g = torch.cuda.CUDAGraph()
+                with torch.no_grad(), torch.cuda.graph(g):
+                    lo, gp = self._forward_backward_group(pc, intr, float(camera.z_span), True, 1.0)
+            self._graph = (key, g, lo, gp, pc, intr, self.weights, params)        # (keeps the captured inputs alive)
+        self._graph[1].replay()
+        return self._graph[2], self._graph[3]
+

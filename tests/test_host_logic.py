@@ -783,3 +783,39 @@ def test_wino_fused_xcd_order_is_a_permutation():
         assert len(seen) == gx * gy
         assert all(len(v) == 1 for v in xcd_of.values())
         assert all(max(v) - min(v) == gy - 1 for v in order.values())   # consecutive slots of that XCD
+
+
+def test_camera_block_plan_selection():
+    """engine.select_camera_blocks: 'auto' resolution, the refusals, and the experimental family's way in -- host logic only."""
+    from latentfusion_amd import engine, experimental
+    sel = engine.select_camera_blocks
+    c16, wide64, wide256, c32 = [(16, 16)] * 4, [(64, 64), (96, 64), (96, 96), (64, 96)], [(256, 256)] * 2, [(32, 32)] * 2
+    assert sel('auto', c16, 16) == ('winograd', engine._Winograd16)
+    assert sel('auto', wide64, 64) == ('winograd', engine._WideWinograd)
+    assert sel('auto', wide256, 256) == ('winograd', engine._WideWinograd)
+    assert sel('auto', c32, 32) == ('fp32', engine._Fp32Direct)
+    assert sel('auto', [], 16) == ('fp32', engine._Fp32Direct)
+    assert sel('auto', c16, 32) == ('fp32', engine._Fp32Direct)            # (16 -> 16 kernels need the 16-channel volume too)
+    assert sel('fp32', c16, 16) == ('fp32', engine._Fp32Direct)
+    assert sel('f16x3', c16, 16) == ('f16x3', engine._Direct16F16x3)
+    assert sel('f16x3', wide256, 256) == ('f16x3', engine._WideWinogradF16x3)
+    for mode in ('winograd', 'f16x3'):
+        with pytest.raises(NotImplementedError):
+            sel(mode, c32, 32)
+    with pytest.raises(ValueError):
+        sel('bf16', c16, 16)
+    # the experimental family: refused by the product selection, accepted by the experimental one, which defers otherwise
+    with pytest.raises(ValueError):
+        sel('winograd_f16x3', c16, 16)
+    assert experimental.select_camera_blocks('winograd_f16x3', c16, 16) == ('winograd_f16x3', experimental._Winograd16F16x3)
+    assert experimental.select_camera_blocks('auto', wide64, 64) == sel('auto', wide64, 64)
+    with pytest.raises(NotImplementedError):
+        experimental.select_camera_blocks('winograd_f16x3', wide64, 64)
+    with pytest.raises(ValueError):
+        experimental.select_camera_blocks('bf16', c16, 16)
+    # what the engine asks its plan: constants per family
+    flags = {f.__name__: (f.folds_prev, f.wide, f.wino16, f.plain_factor_only) for f in
+             (engine._Winograd16, engine._Direct16F16x3, engine._WideWinograd, engine._WideWinogradF16x3, experimental._Winograd16F16x3)}
+    assert flags == {'_Winograd16': (True, False, True, False), '_Direct16F16x3': (True, False, False, True),
+                     '_WideWinograd': (False, True, False, False), '_WideWinogradF16x3': (False, True, False, True),
+                     '_Winograd16F16x3': (True, False, False, True)}

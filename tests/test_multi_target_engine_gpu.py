@@ -145,7 +145,8 @@ def test_wide_branch_g20_with_gradients_within_rounding_per_target(golden):
     with model.frozen():
         eng, _, _ = _compare(model.photographer, g['z_obj'].to(DEV), targets, cams, g['loss']['weights'], n, exact=False,
                              gtol=2e-3)
-    assert eng.wgemm is not None
+    from latentfusion_amd.engine import _WideWinograd
+    assert type(eng.plan) is _WideWinograd
 
 
 def test_wide_branch_g20_ranking_within_single_target_tolerance(golden):

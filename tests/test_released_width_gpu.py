@@ -81,14 +81,14 @@ def test_g20_encode_decode_modules(golden):
 def test_g20_engine_wide_branch(golden):
     """RenderLoopEngine on 64-channel camera blocks: the wide Winograd branch of the fused forward + backward
     against the reference's default_pose_loss components and d(mean weighted loss)/d(camera parameters)."""
-    from latentfusion_amd.engine import RenderLoopEngine
+    from latentfusion_amd.engine import RenderLoopEngine, _WideWinograd
     g, t7 = golden('g20_released_width'), golden('g7_adam_trace')
     model = _model(g)
     L = g['loss']
     target = _target(t7)
     assert RenderLoopEngine.supports(model.photographer, L['weights'])
     eng = RenderLoopEngine(model.photographer, g['z_obj'].to(DEV), target, L['weights'])
-    assert eng.conv_mode == 'winograd' and eng.wgemm is not None, 'the wide Winograd branch should drive 64-channel camera blocks'
+    assert eng.conv_mode == 'winograd' and type(eng.plan) is _WideWinograd, 'the wide Winograd branch should drive 64-channel camera blocks'
     zc = prod_camera(L['zoomed'])
     (losses, gparams), tags = _wide_kernels_used(lambda: eng.forward_backward(zc))
     assert any(t.startswith('wino3d') for t in tags), tags

@@ -145,13 +145,13 @@ def _rw():
 def test_g20_engine_f16x3(golden):
     """RenderLoopEngine(conv_mode='f16x3') on the released-width model: every camera-block convolution on the new kernel, loss
     components, camera gradients and loss order within the bars of the fp32 wide branch."""
-    from latentfusion_amd.engine import RenderLoopEngine
+    from latentfusion_amd.engine import RenderLoopEngine, _WideWinogradF16x3
     rw = _rw()
     g, t7 = golden('g20_released_width'), golden('g7_adam_trace')
     model = rw._model(g)
     L = g['loss']
     eng = RenderLoopEngine(model.photographer, g['z_obj'].to(DEV), rw._target(t7), L['weights'], conv_mode='f16x3')
-    assert eng.conv_mode == 'f16x3' and eng.wgemm_x is not None and eng.wgemm is None
+    assert eng.conv_mode == 'f16x3' and type(eng.plan) is _WideWinogradF16x3
     zc = rw.prod_camera(L['zoomed'])
     (losses, gparams), tags = rw._wide_kernels_used(lambda: eng.forward_backward(zc))
     assert 'wino3d_fused_f16x3' in tags and 'wino3d_fused' not in tags, tags
