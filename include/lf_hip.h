@@ -82,6 +82,27 @@ int lf_resample3d_bwd_coef_part(const float* gout, const float* vol, int vol_n, 
                                 float* gcoef, void* scratch, size_t scratch_bytes,
                                 int N, int D, int H, int W, int C, int part_n, void* stream);
 
+/* Several source volumes behind one launch: `vol` holds vol_n >= 1 channels-last volumes [vol_n][D][H][W][C] back to back and
+ * `vol_idx` is a DEVICE array of N int32; sample i reads volume vol_idx[i].  The reference renders one object per call --
+ * Photographer.decode expands its single volume over the N cameras, recon/models.py:489-494 -- so the hypotheses of several
+ * objects (pose refinement of a whole scene, pose/estimation.py:52-143 once per object) take one decode each; this is the
+ * form that expansion needs when row i of the batch belongs to object vol_idx[i].
+ * Everything else is lf_resample3d_fwd / lf_resample3d_bwd_coef_part: per sample the same operations in the same order, so
+ * sample i's output is bit-identical to lf_resample3d_fwd(vol + vol_idx[i]*D*H*W*C, vol_n = 1, ...) on that sample, and its
+ * 18 sums to lf_resample3d_bwd_coef called with N = part_n on that volume.  The lf_set_tuning forms without an indexed kernel
+ * (key 1 = 4, 5; key 2 other than 10) run the default form.
+ * Checked before anything is launched: NULL pointers, vol_n < 1, part_n < 1 -> LF_EINVAL; vol_idx not 4-byte aligned ->
+ * LF_EALIGN; a volume or output pointer that is not 16-byte aligned takes the scalar kernels, as above; scratch below
+ * lf_resample3d_bwd_coef_indexed_scratch_bytes(N, part_n, D, H, W) -> LF_ENOSPC.  The TABLE's contents live on the device and
+ * are not inspected by the host: the kernels clamp every entry into [0, vol_n), so a bad entry reads another volume, never
+ * outside the buffer (the Python wrapper ops.volume_table rejects one with ValueError when it builds the table). */
+int lf_resample3d_fwd_indexed(const float* vol, int vol_n, const int32_t* vol_idx, const float* coef, int kind,
+                              float* out, int N, int D, int H, int W, int C, void* stream);
+size_t lf_resample3d_bwd_coef_indexed_scratch_bytes(int N, int part_n, int D, int H, int W);
+int lf_resample3d_bwd_coef_indexed(const float* gout, const float* vol, int vol_n, const int32_t* vol_idx, const float* coef,
+                                   float* gcoef, void* scratch, size_t scratch_bytes,
+                                   int N, int D, int H, int W, int C, int part_n, void* stream);
+
 /* d(loss)/d(vol) (trilinear splat, fp32 atomics; training / encoder backward only).
  * gvol must be zero-initialised by the caller; with vol_n == 1 all samples accumulate into one
  * volume. */

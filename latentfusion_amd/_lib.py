@@ -34,6 +34,9 @@ SIGNATURES = {
     'lf_resample3d_bwd_coef': (c_int, [P, P, c_int, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_resample3d_bwd_coef_part_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     'lf_resample3d_bwd_coef_part': (c_int, [P, P, c_int, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_resample3d_fwd_indexed': (c_int, [P, c_int, P, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_resample3d_bwd_coef_indexed_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    'lf_resample3d_bwd_coef_indexed': (c_int, [P, P, c_int, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_resample3d_bwd_vol_det_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     'lf_resample3d_bwd_vol_det': (c_int, [P, P, c_int, P, c_int, P, c_size_t, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_conv3x3_cout_padded': (c_int, [c_int]),

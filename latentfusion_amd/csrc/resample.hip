@@ -773,6 +773,7 @@ __global__ void __launch_bounds__(256, MINW) resample_bwd_coef_c16_dedup_kernel(
 }
 
 #include "resample_staged.inc"
+#include "resample_indexed.inc"
 
 #ifdef STAGED_TPW_OVERRIDE
 constexpr int STAGED_TPW = STAGED_TPW_OVERRIDE;
@@ -1624,6 +1625,105 @@ extern "C" int lf_resample3d_bwd_coef_part(const float* gout, const float* vol, 
   if (!gout || !vol || !coef || !gcoef || !scratch) return LF_EINVAL;
   if (part_n <= 0 || N <= 0) return LF_EINVAL;
   return bwd_coef_launch(gout, vol, vol_n, coef, gcoef, scratch, scratch_bytes, N, part_n, D, H, W, C, stream);
+}
+
+// ---- several source volumes behind one launch: sample i reads volume vol_idx[i] (lf_hip.h) ----------------------------------
+// Same shape rules, tiles and grids as lf_resample3d_fwd; the kernels are those of resample_indexed.inc.  The lf_set_tuning
+// forms that have no indexed kernel (staged footprint, per-voxel dedup gather) run the default form here.
+extern "C" int lf_resample3d_fwd_indexed(const float* vol, int vol_n, const int* vol_idx, const float* coef, int kind, float* out,
+                                         int N, int D, int H, int W, int C, void* stream) {
+  lf_clear_error();
+  if (!vol || !vol_idx || !coef || !out) return LF_EINVAL;
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || vol_n < 1) return LF_EINVAL;
+  if (kind != LF_MAP_O2C && kind != LF_MAP_C2O) return LF_EINVAL;
+  if (((uintptr_t)vol_idx & 3) != 0) return LF_EALIGN;
+  if ((long)D * H * W >= 0x7fffffffL) return LF_EINVAL;
+  const long bstride = (long)D * H * W * C;                // every volume is addressed through the table, vol_n == 1 included
+  const bool vec = (C % 4 == 0) && lf_aligned16(vol) && lf_aligned16(out);
+  const int lpv = vec ? C / 4 : C;
+  const int lpt = lpv < 256 ? lpv : 256;
+  int lg = 0;
+  while ((2 << lg) * lpt <= 256) ++lg;
+  int tlx, tly, tlz;
+  if (lg >= 6) { tlx = (lg + 2) / 3; tly = (lg + 1) / 3; tlz = lg / 3; }
+  else         { tlx = lg < 2 ? lg : 2; tly = lg - tlx < 2 ? lg - tlx : 2; tlz = lg - tlx - tly; }
+  const int nbz = (D + (1 << tlz) - 1) >> tlz;
+  if ((long)nbz * N > 65535 || ((H + (1 << tly) - 1) >> tly) > 65535) return LF_EINVAL;
+  dim3 grid((unsigned)((W + (1 << tlx) - 1) >> tlx), (unsigned)((H + (1 << tly) - 1) >> tly), (unsigned)(nbz * N)), block(256);
+  const Steps st = make_steps(D, H, W);
+  hipStream_t s = (hipStream_t)stream;
+  if (g_resample_variant >= 3 && vec && C == 16 && (long)D * H * W * 64 < 0xffffffffL) {
+    const int nbz4 = (D + 3) >> 2;
+    if ((long)nbz4 * N > 65535 || ((H + 3) >> 2) > 65535) return LF_EINVAL;
+    dim3 g4((unsigned)((W + 3) >> 2), (unsigned)((H + 3) >> 2), (unsigned)(nbz4 * N));
+    if (kind == LF_MAP_O2C)
+      hipLaunchKernelGGL((resample_fwd_c16_indexed_kernel<LF_MAP_O2C>), g4, block, 0, s, vol, bstride, vol_idx, vol_n, coef, out, D, H, W, nbz4, st);
+    else
+      hipLaunchKernelGGL((resample_fwd_c16_indexed_kernel<LF_MAP_C2O>), g4, block, 0, s, vol, bstride, vol_idx, vol_n, coef, out, D, H, W, nbz4, st);
+    return lf_launch_status();
+  }
+  if (g_resample_variant >= 2 && vec && (long)D * H * W * C * 4 < 0xffffffffL) {
+    if (kind == LF_MAP_O2C)
+      hipLaunchKernelGGL((resample_fwd_lean_indexed_kernel<LF_MAP_O2C>), grid, block, 0, s, vol, bstride, vol_idx, vol_n, coef, out, D, H, W, C, lpt, tlx, tly, tlz, nbz, st);
+    else
+      hipLaunchKernelGGL((resample_fwd_lean_indexed_kernel<LF_MAP_C2O>), grid, block, 0, s, vol, bstride, vol_idx, vol_n, coef, out, D, H, W, C, lpt, tlx, tly, tlz, nbz, st);
+    return lf_launch_status();
+  }
+#define LAUNCH(K, V) hipLaunchKernelGGL((resample_fwd_indexed_kernel<K, V>), grid, block, 0, s, vol, bstride, vol_idx, vol_n, coef, out, N, D, H, W, C, lpt, tlx, tly, tlz, nbz, st)
+  if (kind == LF_MAP_O2C) { if (vec) LAUNCH(LF_MAP_O2C, 4); else LAUNCH(LF_MAP_O2C, 1); }
+  else                    { if (vec) LAUNCH(LF_MAP_C2O, 4); else LAUNCH(LF_MAP_C2O, 1); }
+#undef LAUNCH
+  return lf_launch_status();
+}
+
+extern "C" size_t lf_resample3d_bwd_coef_indexed_scratch_bytes(int N, int part_n, int D, int H, int W) {
+  if (N <= 0 || part_n <= 0) return 0;
+  return bwd_coef_scratch_bytes(N, part_n, D, H, W);
+}
+
+// lf_resample3d_bwd_coef_part over a table of volumes: the partition, the grids and the fixed-order finish are bwd_coef_launch's.
+// 16 channels run the default forms (lf_set_tuning key 2 = 10: the per-voxel dedup kernel when a block holds >= 256 voxels, else
+// the four-lanes-per-voxel kernel); other values of that key run these two as well.
+extern "C" int lf_resample3d_bwd_coef_indexed(const float* gout, const float* vol, int vol_n, const int* vol_idx, const float* coef,
+                                              float* gcoef, void* scratch, size_t scratch_bytes,
+                                              int N, int D, int H, int W, int C, int part_n, void* stream) {
+  lf_clear_error();
+  if (!gout || !vol || !vol_idx || !coef || !gcoef || !scratch) return LF_EINVAL;
+  if (part_n <= 0 || N <= 0 || vol_n < 1) return LF_EINVAL;
+  if (D <= 0 || H <= 0 || W <= 0 || C <= 0) return LF_EINVAL;
+  if (((uintptr_t)vol_idx & 3) != 0) return LF_EALIGN;
+  if (scratch_bytes < bwd_coef_scratch_bytes(N, part_n, D, H, W)) return LF_ENOSPC;
+  if ((long)D * H * W >= 0x7fffffffL) return LF_EINVAL;
+  const long nvox = (long)D * H * W;
+  const int vpb = bwd_vox_per_block(nvox, part_n);
+  const BwdTile bt = bwd_tile(vpb, D, H, W);
+  const long nblk_l = (long)bt.ntx * bt.nty * bt.ntz;
+  if (nblk_l * N > 0x7fffffffL) return LF_EINVAL;
+  const int nblk = (int)nblk_l;
+  const long bstride = nvox * C;
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)(nblk_l * N)), block(256);
+  float* partial = (float*)scratch;
+  const bool vec = (C % 4 == 0) && lf_aligned16(gout) && lf_aligned16(vol);
+  const int groups = vec ? C / 4 : C;
+  int lpv = 1;
+  while (lpv < groups) lpv <<= 1;
+  if (lpv > 64) return LF_EINVAL;                       // C > 256 (vec) / C > 64 (scalar)
+  const Steps stp = make_steps(D, H, W);
+  if (g_resample_variant >= 2 && vec && C == 16 && vpb >= 64 && nvox * 64 < 0xffffffffL) {
+    if (vpb >= 256)
+      hipLaunchKernelGGL((resample_bwd_coef_c16_dedup_indexed_kernel<2, 1, true>), grid, block, 0, s, gout, vol, bstride, vol_idx, vol_n, coef, partial, nblk, vpb, bt, D, H, W, stp);
+    else
+      hipLaunchKernelGGL((resample_bwd_coef_c16_indexed_kernel<8, 1>), grid, block, 0, s, gout, vol, bstride, vol_idx, vol_n, coef, partial, nblk, vpb, bt, D, H, W, stp);
+  } else if (vec) {
+    hipLaunchKernelGGL((resample_bwd_coef_indexed_kernel<4>), grid, block, 0, s, gout, vol, bstride, vol_idx, vol_n, coef, partial, nblk, vpb, bt, N, D, H, W, C, lpv, stp);
+  } else {
+    hipLaunchKernelGGL((resample_bwd_coef_indexed_kernel<1>), grid, block, 0, s, gout, vol, bstride, vol_idx, vol_n, coef, partial, nblk, vpb, bt, N, D, H, W, C, lpv, stp);
+  }
+  int st = lf_launch_status();
+  if (st) return st;
+  hipLaunchKernelGGL(resample_bwd_coef_reduce, dim3(N), dim3(256), 0, s, partial, nblk, gcoef);
+  return lf_launch_status();
 }
 
 extern "C" int lf_resample3d_bwd_vol(const float* gout, const float* coef, int kind, float* gvol, int vol_n,

@@ -372,15 +372,7 @@ class RenderLoopEngine:
         self.ph = photographer
         self.cube = photographer.cube_size
         dev = z_obj.device
-        self.z = ops.cl(z_obj.reshape(1, *z_obj.shape[-4:]))              # (1,C,S,S,S) channels-last, resident
-        if len(photographer.object_blocks):
-            # object-frame blocks act on the volume BEFORE the camera transform (reference recon/models.py:410-415): every
-            # hypothesis sees the same input, so they are evaluated once per object here, not once per hypothesis per call
-            with torch.no_grad():
-                zo = self.z
-                for blk in photographer.object_blocks:
-                    zo = blk(zo)
-            self.z = ops.cl(zo.detach())
+        self.z = self._resident_volume(photographer, z_obj)
         self.S = self.z.shape[-1]
         self.C = self.z.shape[1]
         self.crop = photographer.out_size
@@ -467,6 +459,20 @@ class RenderLoopEngine:
             hw = self.heads[0]
             self.heads_pack = (ops.he_constant(hw), ops.pack_conv1x1(hw.reshape(hw.shape[0], hw.shape[1])),
                                ops.pack_conv1x1(hw.reshape(hw.shape[0], hw.shape[1]).t()))
+
+    @staticmethod
+    def _resident_volume(photographer, z_obj):
+        """The volume the resampler reads: (1,C,S,S,S) channels-last, after the renderer's object-frame blocks."""
+        z = ops.cl(z_obj.reshape(1, *z_obj.shape[-4:]))
+        if len(photographer.object_blocks):
+            # object-frame blocks act on the volume BEFORE the camera transform (reference recon/models.py:410-415): every
+            # hypothesis sees the same input, so they are evaluated once per object here, not once per hypothesis per call
+            with torch.no_grad():
+                zo = z
+                for blk in photographer.object_blocks:
+                    zo = blk(zo)
+            z = ops.cl(zo.detach())
+        return z
 
     def set_weights(self, loss_weights):
         self.weights = torch.tensor([loss_weights.get(k, 0.0) for k in self.LOSS_KEYS], dtype=torch.float32,

@@ -1,4 +1,4 @@
-"""The render-and-score engine over several target frames of one object in one batch.
+"""The render-and-score engine over several target frames in one batch: frames of one object, or of several objects.
 
 T targets x n hypotheses, grouped by target (row i belongs to target i // n), run through ONE sequence of launches of
 RenderLoopEngine.  Everything below the loss already works per hypothesis; what is per target here:
@@ -12,16 +12,60 @@ kernels whose per-sample arithmetic does not depend on the batch.  Exceptions (t
 their tolerances): conv_mode 'f16x3' (batch-wide gradient scales) and every renderer with wide (>= 64-channel) layers, the
 released architecture included: lf_wino_fused_gemm picks its workgroup configuration (pick_fused_cfg) and its frequency
 split (fused_zsplit) from the batch's tile count N x tiles, so a row's summation order follows the batch size.
+
+Several objects (a scene's frame holds a few, each with its own latent volume): `z_obj` is then a sequence of T volumes, one
+per target.  Nothing below the resampler is per object -- camera blocks, projection, decoder, loss and optimiser work per row
+with shared weights -- so the only change to an iteration is that the two resampler launches take a per-row table of volumes
+(lf_resample3d_fwd_indexed, lf_resample3d_bwd_coef_indexed); per row they are bit-identical to the one-volume entry points
+on that row's volume, so everything above holds per (object, target) as it does per target.
 """
 import torch
 
 from . import _lib, ops
 from ._lib import check
-from .engine import RenderLoopEngine, _PoseLoss, _pose_loss_bwd, _pose_loss_fwd, _s
+from .engine import LF_MAP_O2C, RenderLoopEngine, _PoseLoss, _pose_loss_bwd, _pose_loss_fwd, _s
+
+
+def distinct_volumes(z_objs):
+    """(volumes, index): the distinct tensor OBJECTS of a sequence in order of first appearance, and for every entry its
+    position among them.  Identity, not value: the caller that passes one tensor for three frames of an object says so by
+    passing the same tensor, and comparing 128 MiB volumes element by element is not a constructor's business."""
+    vols, index, seen = [], [], {}
+    for z in z_objs:
+        k = seen.get(id(z))
+        if k is None:
+            k = seen[id(z)] = len(vols)
+            vols.append(z)
+        index.append(k)
+    return vols, index
+
+
+def check_volumes(z_objs, num_targets):
+    """Argument check of a per-target volume list (engine and estimator): one tensor per target, alike in shape, dtype and
+    device."""
+    z_objs = list(z_objs)
+    if len(z_objs) != num_targets:
+        raise ValueError(f'{len(z_objs)} volumes for {num_targets} targets: a volume list holds one entry per target')
+    for i, z in enumerate(z_objs):
+        if not isinstance(z, torch.Tensor):
+            raise ValueError(f'volume {i} is a {type(z).__name__}: expected a tensor')
+        if z.dim() < 4:
+            raise ValueError(f'volume {i} has shape {tuple(z.shape)}: expected (.., C, S, S, S)')
+    kinds = {(tuple(z.shape[-4:]), z.dtype, z.device) for z in z_objs}
+    if len(kinds) != 1:
+        raise ValueError('the volumes differ in shape, dtype or device: ' + ', '.join(
+            f'{shape} {dtype} {dev}' for shape, dtype, dev in sorted(kinds, key=str)))
+    return z_objs
 
 
 class MultiTargetEngine(RenderLoopEngine):
-    """RenderLoopEngine for T single-frame targets of the same object and frame size, n hypotheses each.
+    """RenderLoopEngine for T single-frame targets of the same frame size, n hypotheses each.
+
+    z_obj: one volume shared by all targets (the one-object form: one resident volume and the one-volume resampler entry
+    points, as before), or a sequence of T volumes of one shape, dtype and device, entry t the object of target t.  Entries
+    that are the same tensor object share one resident copy ("3 frames of A, 2 of B" keeps two volumes), and the renderer's
+    object-frame blocks run once per distinct volume.  Resident memory grows by one volume per distinct object: 128 MiB each
+    at SYN(128,16) (16 channels x 128^3 fp32).  The per-row table of volumes is built once per n.
 
     forward_backward(camera, n) takes the T * n cameras grouped by target and returns the single-target engine's layout:
     (losses (T*n, 8), gparams (T*n, 10) or None), gparams = d(sum_t mean over target t's rows of the weighted loss).
@@ -49,8 +93,19 @@ class MultiTargetEngine(RenderLoopEngine):
             raise NotImplementedError(f'conv_mode {conv_mode!r}: the multi-target engine runs {RenderLoopEngine.CONV_MODES}')
         if fuse_projection is True or (isinstance(fuse_projection, (tuple, list, set)) and 'bwd' in fuse_projection):
             raise NotImplementedError('the fused projection backward is an experimental.RenderLoopEngineX option')
+        vols = index = None
+        if isinstance(z_obj, (list, tuple)):
+            vols, index = distinct_volumes(check_volumes(z_obj, len(targets)))
+            z_obj = vols[0]
         super().__init__(photographer, z_obj, targets[0], loss_weights, conv_mode=conv_mode, fuse_projection=fuse_projection)
         dev = self.dev
+        # several objects: the distinct volumes back to back [K][S][S][S][C], self.z the first of them (a view: no second copy)
+        self.zs = self.vol_of = None
+        if vols is not None:
+            self.zs = ops.cl(torch.cat([self.z] + [self._resident_volume(photographer, z) for z in vols[1:]]))
+            self.z = self.zs[:1]
+            self.vol_of = index
+            self._tables = {}
         # one resident [T][H*W] buffer each (raw device pointers reach the kernels: nothing host-resident)
         self.tdepth = torch.stack([t.depth.reshape(-1).float().to(dev) for t in targets]).contiguous()
         self.tmask = torch.stack([t.mask.reshape(-1).float().to(dev) for t in targets]).contiguous()
@@ -109,9 +164,39 @@ class MultiTargetEngine(RenderLoopEngine):
         return torch.cat([RenderLoopEngine._latent_distance(self, zp[t * k:(t + 1) * k], zt[t * k:(t + 1) * k], k)
                           for t in range(self.T)])
 
+    def _table(self, rows):
+        """Volume of every row (n rows per target, grouped by target) as the device table of the indexed resampler."""
+        n = self._n
+        if rows != self.T * n:
+            raise ValueError(f'{rows} rows are not {self.T} targets x n = {n}')
+        if n not in self._tables:
+            self._tables[n] = ops.volume_table([k for k in self.vol_of for _ in range(n)], self.zs.shape[0], self.dev)
+        return self._tables[n]
+
+    def _resample(self, cf20, n):
+        if self.zs is None:
+            return RenderLoopEngine._resample(self, cf20, n)
+        L = _lib.lib()
+        S = self.S
+        x0 = ops.empty_cl((n, self.C, S, S, S), self.dev)
+        table = self._table(n)
+        with ops._timed('resample_fwd'):
+            check(L.lf_resample3d_fwd_indexed(self.zs.data_ptr(), self.zs.shape[0], table.data_ptr(), cf20.data_ptr(), LF_MAP_O2C,
+                                              x0.data_ptr(), n, S, S, S, self.C, _s()), 'lf_resample3d_fwd_indexed')
+        return x0
+
     def _bwd_coef(self, g, cf20, gcoef18, n):
         L = _lib.lib()
         S = self.S
+        if self.zs is not None:
+            table = self._table(n)
+            nbytes = L.lf_resample3d_bwd_coef_indexed_scratch_bytes(n, self._n, S, S, S)
+            scratch = torch.empty(nbytes // 4 + 1, device=self.dev, dtype=torch.float32)
+            with ops._timed('resample_bwd_coef'):
+                check(L.lf_resample3d_bwd_coef_indexed(g.data_ptr(), self.zs.data_ptr(), self.zs.shape[0], table.data_ptr(),
+                                                       cf20.data_ptr(), gcoef18.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
+                                                       n, S, S, S, self.C, self._n, _s()), 'lf_resample3d_bwd_coef_indexed')
+            return
         nbytes = L.lf_resample3d_bwd_coef_part_scratch_bytes(n, self._n, S, S, S)
         scratch = torch.empty(nbytes // 4 + 1, device=self.dev, dtype=torch.float32)
         with ops._timed('resample_bwd_coef'):

@@ -706,6 +706,66 @@ def resample_c2o(vol, coef):
     return _Resample.apply(vol, coef, LF_MAP_C2O)
 
 
+def volume_table(indices, vol_n, device):
+    """The `vol_idx` argument of the indexed resampler: row i of a batch reads volume indices[i] of vol_n.  The library cannot
+    inspect a device table (its kernels clamp), so the range is checked here, on the host, before the table is uploaded."""
+    idx = [int(i) for i in indices]
+    if vol_n < 1 or not idx:
+        raise ValueError(f'a volume table needs at least one row and one volume (got {len(idx)} rows, vol_n = {vol_n})')
+    bad = [(r, i) for r, i in enumerate(idx) if not 0 <= i < vol_n]
+    if bad:
+        raise ValueError(f'volume table row {bad[0][0]} names volume {bad[0][1]}: outside [0, {vol_n})')
+    return torch.tensor(idx, dtype=torch.int32).to(device)
+
+
+def _indexed_args(vols, table, rows):
+    _req(vols, 'vols')
+    if vols.dim() != 5 or not vols.is_contiguous(memory_format=torch.channels_last_3d):
+        raise ValueError('vols: (K,C,D,H,W) volumes in channels-last layout, back to back (ops.cl)')
+    if table.dtype != torch.int32 or table.device != vols.device or table.dim() != 1 or not table.is_contiguous():
+        raise ValueError('table: a contiguous int32 vector on the device of the volumes (ops.volume_table)')
+    if table.numel() != rows:
+        raise ValueError(f'the table has {table.numel()} rows, the batch {rows}')
+
+
+def resample_fwd_indexed(vols, table, coef, kind=LF_MAP_O2C):
+    """lf_resample3d_fwd_indexed: vols (K,C,D,H,W) channels-last, table (N,) from volume_table, coef (N,<=20) -> (N,C,D,H,W);
+    row i is the resample of vols[table[i]] under coef[i].  Forward only (the pose loop's coefficient gradient is
+    resample_bwd_coef_indexed)."""
+    L = _lib.lib()
+    n = coef.shape[0]
+    _indexed_args(vols, table, n)
+    K, C, D, H, W = vols.shape
+    out = empty_cl((n, C, D, H, W), vols.device)
+    cf = torch.zeros(n, LF_MAP_COEFS, device=vols.device, dtype=torch.float32)
+    cf[:, :coef.shape[1]] = coef
+    check(L.lf_resample3d_fwd_indexed(_ptr(vols), K, _ptr(table), _ptr(cf), kind, _ptr(out), n, D, H, W, C, _stream()),
+          'lf_resample3d_fwd_indexed')
+    return out
+
+
+def resample_bwd_coef_indexed(gout, vols, table, coef, part_n):
+    """lf_resample3d_bwd_coef_indexed: d(loss)/d(O2C coefficients) (N,18) of resample_fwd_indexed's rows, every row summed in
+    the block partition of a launch of part_n rows (lf_resample3d_bwd_coef_part)."""
+    L = _lib.lib()
+    g = cl(_req(gout, 'gout'))
+    n, C, D, H, W = g.shape
+    _indexed_args(vols, table, n)
+    if tuple(vols.shape[1:]) != (C, D, H, W):
+        raise ValueError(f'gout rows {tuple(g.shape[1:])} and volumes {tuple(vols.shape[1:])} differ in shape')
+    if part_n < 1:
+        raise ValueError('part_n >= 1')
+    cf = torch.zeros(n, LF_MAP_COEFS, device=g.device, dtype=torch.float32)
+    cf[:, :coef.shape[1]] = coef
+    gcoef = torch.empty(n, 18, device=g.device, dtype=torch.float32)
+    nbytes = L.lf_resample3d_bwd_coef_indexed_scratch_bytes(n, part_n, D, H, W)
+    scratch = torch.empty(nbytes // 4 + 1, device=g.device, dtype=torch.float32)
+    check(L.lf_resample3d_bwd_coef_indexed(_ptr(g), _ptr(vols), vols.shape[0], _ptr(table), _ptr(cf), _ptr(gcoef),
+                                           _ptr(scratch, True), scratch.numel() * 4, n, D, H, W, C, part_n, _stream()),
+          'lf_resample3d_bwd_coef_indexed')
+    return gcoef
+
+
 # ---------------------------------------------------------------------------------------------
 # convolutions with fused epilogue
 # ---------------------------------------------------------------------------------------------

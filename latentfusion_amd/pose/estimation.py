@@ -717,7 +717,7 @@ class GradientPoseEstimator(PoseEstimator):
                 break
         return st['stat_history'], st['camera_history']
 
-    # ---- several target frames of one object in one render loop ----
+    # ---- several target frames, of one object or of several, in one render loop ----
     def estimate_batch(self, z_obj, targets, cameras=None):
         """Refines T single-frame targets of one object in ONE batched loop on engine_multi.MultiTargetEngine.  Entry t of
         the returned list is what estimate(z_obj, targets[t], camera=cameras[t]) returns (the best cameras, plus stat_history /
@@ -734,7 +734,13 @@ class GradientPoseEstimator(PoseEstimator):
         All rows start together, so the one step counter of BatchedOptimizer (Adam's bias correction) is right for each.
         More than MultiTargetEngine.MAX_ROWS rows run as successive groups of whole targets (`last_batch_groups` records
         the group sizes).  Without an applicable engine (use_engine=False, a renderer the engine does not sequence, a
-        custom loss_func) the targets run one estimate() after another."""
+        custom loss_func) the targets run one estimate() after another.
+
+        Several objects: `z_obj` may be a sequence of T volumes (one shape, dtype and device), entry t the object of
+        target t; entry t of the result is then what estimate(z_obj[t], targets[t], camera=cameras[t]) returns, under the
+        conditions above.  Entries that are the same tensor share one resident volume in the engine; a group split off at
+        MAX_ROWS carries only its own targets' volumes; a host-resident volume in the list sends all targets down the
+        one-estimate()-per-target path, as a host-resident single volume does."""
         targets = list(targets)
         if not targets:
             raise ValueError('estimate_batch needs at least one target')
@@ -751,13 +757,18 @@ class GradientPoseEstimator(PoseEstimator):
             counts = {len(c) for c in cameras}
             if len(counts) != 1:
                 raise ValueError(f'every target needs the same number of hypotheses, got {sorted(counts)}')
+        z_of = None                                                  # per-target volumes; None: one object
+        if isinstance(z_obj, (list, tuple)):
+            from ..engine_multi import check_volumes
+            z_of = check_volumes(z_obj, len(targets))
         if self.shard_hypotheses:
             raise NotImplementedError('estimate_batch does not shard hypotheses over ranks')
         if cameras is None:
             cameras = [pu.sample_cameras_with_estimate(n=self.num_samples, camera_est=self.initial_pose(t)) for t in targets]
-        if not self._multi_engine_applies(z_obj):
+        if not self._multi_engine_applies(z_obj if z_of is None else z_of[0]):     # (the volumes agree in device)
             self.last_batch_groups = [1] * len(targets)
-            return [self.estimate(z_obj, t, camera=c) for t, c in zip(targets, cameras)]
+            return [self.estimate(z_obj if z_of is None else z_of[i], t, camera=c)
+                    for i, (t, c) in enumerate(zip(targets, cameras))]
         if self.engine_streams > 1 or self.engine_graph:
             raise NotImplementedError('engine_streams / engine_graph are experimental.RenderLoopEngineX options')
         from ..engine_multi import MultiTargetEngine
@@ -771,7 +782,8 @@ class GradientPoseEstimator(PoseEstimator):
                 self.last_batch_groups = [e - b for b, e in groups]
                 out = []
                 for b, e in groups:                                  # (whole targets per group)
-                    eng = MultiTargetEngine(self.model.photographer, z_obj, dev_targets[b:e], self.loss_weights,
+                    eng = MultiTargetEngine(self.model.photographer, z_obj if z_of is None else z_of[b:e], dev_targets[b:e],
+                                            self.loss_weights,
                                             conv_mode=self.conv_mode, fuse_projection=self.fuse_projection)
                     out += self._run_batch(eng, dev_targets[b:e], zoomed[b:e])
                     del eng

@@ -1,0 +1,82 @@
+"""Shows that a change to csrc/resample.hip left the device code of the EXISTING resampler kernels alone.
+
+Compiles resample.hip of a parent revision (git archive) and of the working tree to gfx950 code objects with the
+library's flags, disassembles both, and diffs every kernel symbol the parent's code object holds, instruction by
+instruction (addresses dropped, encodings kept).  Kernels that only the working tree has are listed, not compared.
+
+    python tools/resample_isa_diff.py [--rev HEAD] [--out profiles/resample_indexed_isa.txt]
+
+The report's diff section is empty when nothing changed; the exit status is 1 otherwise.  Needs hipcc, no GPU.
+"""
+import argparse
+import difflib
+import os
+import re
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from latentfusion_amd.csrc import build as hip_build  # noqa: E402
+
+SRC = os.path.join('latentfusion_amd', 'csrc', 'resample.hip')
+
+
+def _objdump():
+    hipcc = hip_build._hipcc()
+    for cand in (os.path.join(os.path.dirname(os.path.realpath(hipcc)), '..', 'llvm', 'bin', 'llvm-objdump'),
+                 '/opt/rocm/llvm/bin/llvm-objdump'):
+        if os.path.exists(cand):
+            return cand
+    return 'llvm-objdump'
+
+
+def disassemble(tree, workdir, tag):
+    """{symbol: [instruction lines]} of resample.hip's gfx950 code object in `tree`."""
+    co = os.path.join(workdir, tag + '.co')
+    cmd = [hip_build._hipcc(), '-x', 'hip', '--cuda-device-only', '--no-gpu-bundle-output', '-c', os.path.join(tree, SRC), '-o', co]
+    cmd += [f for f in hip_build.FLAGS if f != '-fPIC'] + hip_build.EXTRA.get('resample.hip', [])
+    subprocess.run(cmd, check=True)
+    text = subprocess.run([_objdump(), '-d', '--no-leading-addr', co], check=True, stdout=subprocess.PIPE).stdout.decode()
+    syms, cur = {}, None
+    for line in text.splitlines():
+        m = re.match(r'^[0-9a-f]*\s*<(.+)>:$', line)
+        if m:
+            cur = syms.setdefault(m.group(1), [])
+        elif cur is not None and line.strip():
+            # "\tinsn operands   // 000000020C10: BF88003C <sym+0x104>": the address goes, the encoding and the target stay
+            cur.append(re.sub(r'//\s*[0-9A-Fa-f]+:', '//', line).rstrip())
+    return syms
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument('--rev', default='HEAD')
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'resample_indexed_isa.txt'))
+    a = ap.parse_args()
+    rev = subprocess.run(['git', '-C', ROOT, 'rev-parse', '--short', a.rev], check=True, stdout=subprocess.PIPE).stdout.decode().strip()
+    with tempfile.TemporaryDirectory() as tmp:
+        parent = os.path.join(tmp, 'parent')
+        os.makedirs(parent)
+        ar = subprocess.run(['git', '-C', ROOT, 'archive', a.rev, 'latentfusion_amd/csrc', 'include'], check=True, stdout=subprocess.PIPE)
+        subprocess.run(['tar', '-x', '-C', parent], input=ar.stdout, check=True)
+        old = disassemble(parent, tmp, 'parent')
+        new = disassemble(ROOT, tmp, 'tree')
+    lines = [f'# {SRC}: kernel symbols of revision {rev} against the working tree, gfx950, flags {" ".join(hip_build.FLAGS)}',
+             '# symbol: instructions (parent / tree)']
+    diff = []
+    for name in sorted(old):
+        lines.append(f'#   {name}: {len(old[name])} / {len(new.get(name, []))}')
+        diff += list(difflib.unified_diff(old[name], new.get(name, []), 'parent:' + name, 'tree:' + name, lineterm='', n=2))
+    lines.append('# symbols only in the tree (not compared):')
+    lines += [f'#   {name}: {len(new[name])}' for name in sorted(new) if name not in old]
+    lines.append(f'# diff over the {len(old)} parent symbols ({len(diff)} lines):')
+    with open(a.out, 'w') as f:
+        f.write('\n'.join(lines + diff) + '\n')
+    print(f'{len(old)} symbols compared, {len(diff)} diff lines -> {a.out}')
+    return 1 if diff else 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
