@@ -24,9 +24,9 @@ def needs_build():
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(HERE, s) for s in SOURCES if os.path.exists(os.path.join(HERE, s))]
-    deps += [os.path.join(HERE, 'lf_common.h'), os.path.join(HERE, 'resample_staged.inc'), os.path.join(HERE, 'resample_indexed.inc'),
-             os.path.join(HERE, 'ring_tile.h'),
-             os.path.join(HERE, '..', '..', 'include', 'lf_hip.h'), os.path.join(HERE, '..', '..', 'include', 'lf_hip_experimental.h')]
+    # every header and include file of this directory (a new one cannot be forgotten) and the two public headers
+    deps += [os.path.join(HERE, f) for f in os.listdir(HERE) if f.endswith(('.h', '.inc'))]
+    deps += [os.path.join(HERE, '..', '..', 'include', 'lf_hip.h'), os.path.join(HERE, '..', '..', 'include', 'lf_hip_experimental.h')]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -1,25 +1,31 @@
-// Indexed forms of the default resampler kernels: sample n reads source volume vol_idx[n] of vol_n volumes laid back to back
-// (lf_resample3d_fwd_indexed / lf_resample3d_bwd_coef_indexed: several objects' hypotheses in one launch).  Included by
-// resample.hip inside its anonymous namespace.
+// The six default resampler kernels (trilinear gather and its coefficient gradient), written once and compiled twice.
+// resample.hip includes this file two times inside its anonymous namespace, under three macros:
+//   GATHER_KERNEL(stem)    the kernel's name: stem_kernel (plain), stem_indexed_kernel (indexed);
+//   GATHER_TABLE_PARAMS    the extra parameters after vol_bstride: nothing, or `const int* __restrict__ vol_idx, int vol_n,`;
+//   GATHER_VOL_OFFSET      element offset of sample n's source volume: n * vol_bstride, or vol_offset(n, vol_bstride, vol_idx, vol_n)
+//                          (sample n reads volume vol_idx[n] of vol_n volumes laid back to back: several objects' hypotheses in
+//                          one launch, lf_resample3d_fwd_indexed / lf_resample3d_bwd_coef_indexed).
+// Everything else -- helpers, the kernels that have no indexed form -- lives in resample.hip.
 //
-// Each kernel below is the kernel of resample.hip named above it with ONE change: the source volume's base is
-// vol + vol_offset(n, ...) instead of vol + n * vol_bstride.  They are separate kernels on purpose.  A body shared with the plain
-// kernels (tried as a forceinline function taking a null table) changed the plain kernels' register allocation and instruction
-// order; their device code is pinned (profiles/resample_indexed_isa.txt, tools/resample_isa_diff.py).  Per sample the operations
-// and their order are the plain kernels', so the outputs are bit-identical (tests/test_resample_indexed_gpu.py): keep the two
-// copies in step when one changes.
+// The sharing is textual on purpose: the compiler sees the token streams of two hand-written sets of kernels, so the plain
+// kernels' device code cannot move when the indexed form is touched and the two forms cannot drift apart (per sample the operations
+// and their order are the same, so the outputs are bit-identical: tests/test_resample_indexed_gpu.py).  The C++ routes were
+// measured with tools/resample_isa_diff.py and all re-scheduled kernels nobody has timed:
+//   * one __forceinline__ body taking a null table: changed the plain kernels' register allocation and instruction order;
+//   * a `template <..., bool IDX>` device body behind two thin __global__ wrappers, `if constexpr` around the base offset: 31 of
+//     84 symbols differed (resample_fwd_kernel<*,4> re-scheduled, every resample_bwd_coef* kernel 1 to 5 instructions longer or
+//     shorter, resample_fwd_c16_kernel with swapped operands);
+//   * the kernels themselves templated on `bool IDX` with a VolSrc<IDX> struct in place of (vol, vol_bstride): 33 of 84 symbols
+//     differed, the plain resample_fwd_c16_kernel 3 instructions longer.
+// A change here is checked the same way: tools/resample_isa_diff.py (profiles/resample_shared_isa.txt: 84 symbols, no difference
+// against the two hand-written copies this file replaced).
 
-// Element offset of sample n's volume.  n is workgroup-uniform in every kernel here, so this is one scalar load per workgroup;
-// the index is clamped into [0, vol_n) -- a bad table can never leave the buffer -- and the offset is formed in 64 bits.
-__device__ __forceinline__ long vol_offset(int n, long vol_bstride, const int* __restrict__ vol_idx, int vol_n) {
-  const int v = vol_idx[n];
-  return (long)(v < 0 ? 0 : (v >= vol_n ? vol_n - 1 : v)) * vol_bstride;
-}
-
-// resample_fwd_kernel
+// VEC = 4: one thread per (voxel, 4-channel group), C % 4 == 0.  VEC = 1: one thread per (voxel, channel).
+// A block covers a compact 2^lx x 2^ly x 2^lz output tile (4x4x4 for C = 16), so that the 8-corner
+// footprints of its voxels overlap in L1; 32-bit index math only.
 template <int KIND, int VEC>
-__global__ void __launch_bounds__(256) resample_fwd_indexed_kernel(
-    const float* __restrict__ vol, long vol_bstride, const int* __restrict__ vol_idx, int vol_n, const float* __restrict__ coef,
+__global__ void __launch_bounds__(256) GATHER_KERNEL(resample_fwd)(
+    const float* __restrict__ vol, long vol_bstride, GATHER_TABLE_PARAMS const float* __restrict__ coef,
     float* __restrict__ out, int N, int D, int H, int W, int C, int lpt, int lx, int ly, int lz, int nbz, Steps st) {
   // lpt = threads cooperating on one voxel (<= 256); tile = (1<<lx, 1<<ly, 1<<lz) voxels per block
   const int lpv = C / VEC;
@@ -39,7 +45,7 @@ __global__ void __launch_bounds__(256) resample_fwd_indexed_kernel(
   const float w100 = wx0 * wy0 * wz1, w101 = wx1 * wy0 * wz1, w110 = wx0 * wy1 * wz1, w111 = wx1 * wy1 * wz1;
   const int r00 = (t.z0 * H + t.y0) * W, r01 = (t.z0 * H + t.y1) * W;        // voxel indices of the 4 rows
   const int r10 = (t.z1 * H + t.y0) * W, r11 = (t.z1 * H + t.y1) * W;
-  const float* base = vol + vol_offset(n, vol_bstride, vol_idx, vol_n);
+  const float* base = vol + GATHER_VOL_OFFSET;
   float* orow = out + ((long)n * D * H * W + ((long)z * H + y) * W + x) * C;
   for (int q = q0; q < lpv; q += lpt) {
     const int co = q * VEC;
@@ -61,91 +67,10 @@ __global__ void __launch_bounds__(256) resample_fwd_indexed_kernel(
   }
 }
 
-// resample_fwd_lean_kernel
-template <int KIND>
-__global__ void __launch_bounds__(256) resample_fwd_lean_indexed_kernel(
-    const float* __restrict__ vol, long vol_bstride, const int* __restrict__ vol_idx, int vol_n, const float* __restrict__ coef,
-    float* __restrict__ out, int D, int H, int W, int C, int lpt, int lx, int ly, int lz, int nbz, Steps st) {
-  const int lpv = C >> 2;
-  const int n = blockIdx.z / nbz, bz = blockIdx.z - n * nbz;
-  const int slot = threadIdx.x / lpt, q0 = threadIdx.x - slot * lpt;
-  if (slot >= (1 << (lx + ly + lz))) return;
-  const int x = (blockIdx.x << lx) + (slot & ((1 << lx) - 1));
-  const int y = (blockIdx.y << ly) + ((slot >> lx) & ((1 << ly) - 1));
-  const int z = (bz << lz) + (slot >> (lx + ly));
-  if (x >= W || y >= H || z >= D) return;
-  const u32 rec = (u32)C * 4u;
-  const u32 sample_bytes = (u32)D * (u32)H * (u32)W * rec;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(vol + vol_offset(n, vol_bstride, vol_idx, vol_n)), 0, sample_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)(out + (long)n * D * H * W * C), 0, sample_bytes, 0x00020000);
-  const float* cf = coef + n * LF_MAP_COEFS;
-  float gx, gy, gz, a, b, k;
-  eval_grid<KIND>(cf, x, y, z, W, H, D, st, gx, gy, gz, a, b, k);
-  const Tap32 t = make_tap32(gx, gy, gz, W, H, D, rec);
-  const float wx1 = t.tx, wx0 = 1.f - t.tx, wy1 = t.ty, wy0 = 1.f - t.ty, wz1 = t.tz, wz0 = 1.f - t.tz;
-  const float w000 = wx0 * wy0 * wz0, w001 = wx1 * wy0 * wz0, w010 = wx0 * wy1 * wz0, w011 = wx1 * wy1 * wz0;
-  const float w100 = wx0 * wy0 * wz1, w101 = wx1 * wy0 * wz1, w110 = wx0 * wy1 * wz1, w111 = wx1 * wy1 * wz1;
-  const u32 orow = (u32)((z * H + y) * W + x) * rec;
-  for (int q = q0; q < lpv; q += lpt) {
-    const u32 co = (u32)q * 16u;
-    const f32x4 v000 = ldrec(rs, t.o000 + co), v001 = ldrec(rs, t.o001 + co), v010 = ldrec(rs, t.o010 + co), v011 = ldrec(rs, t.o011 + co);
-    const f32x4 v100 = ldrec(rs, t.o100 + co), v101 = ldrec(rs, t.o101 + co), v110 = ldrec(rs, t.o110 + co), v111 = ldrec(rs, t.o111 + co);
-    const f32x4 r = v000 * w000 + v001 * w001 + v010 * w010 + v011 * w011 + v100 * w100 + v101 * w101 + v110 * w110 + v111 * w111;
-    // streamed output (nt): keep L2 for the gathered volume
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, r), ro, (int)(orow + co), 0, 2);
-  }
-}
-
-// resample_fwd_c16_kernel
-template <int KIND, int IO = 0>
-__global__ void __launch_bounds__(256) resample_fwd_c16_indexed_kernel(
-    const float* __restrict__ vol, long vol_bstride, const int* __restrict__ vol_idx, int vol_n, const float* __restrict__ coef,
-    float* __restrict__ out, int D, int H, int W, int nbz, Steps st) {
-  constexpr bool IN16 = (IO & 1) != 0, OUT16 = (IO & 2) != 0;
-  constexpr u32 IREC = IN16 ? 32u : 64u, OREC = OUT16 ? 32u : 64u;
-  const int n = blockIdx.z / nbz, bz = blockIdx.z - n * nbz;
-  const int q = threadIdx.x & 3, vs = threadIdx.x >> 2;
-  const int x = (blockIdx.x << 2) + (vs & 3), y = (blockIdx.y << 2) + ((vs >> 2) & 3), z = (bz << 2) + (vs >> 4);
-  if (x >= W || y >= H || z >= D) return;
-  const u32 nvox = (u32)D * (u32)H * (u32)W;
-  // (vol_bstride counts ELEMENTS; the pointers are declared float*: byte arithmetic for the bf16 forms)
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)vol + vol_offset(n, vol_bstride, vol_idx, vol_n) * (IN16 ? 2 : 4)), 0, nvox * IREC, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)out + (long)n * nvox * OREC), 0, nvox * OREC, 0x00020000);
-  const float* cf = coef + n * LF_MAP_COEFS;
-  float gx, gy, gz, a, b, k;
-  eval_grid<KIND>(cf, x, y, z, W, H, D, st, gx, gy, gz, a, b, k);
-  const Tap32 t = make_tap32(gx, gy, gz, W, H, D, IREC);
-  const u32 co = (u32)q * (IREC / 4u);
-  const f32x4 v000 = ldrec_t<IN16>(rs, t.o000 + co), v001 = ldrec_t<IN16>(rs, t.o001 + co), v010 = ldrec_t<IN16>(rs, t.o010 + co), v011 = ldrec_t<IN16>(rs, t.o011 + co);
-  const f32x4 v100 = ldrec_t<IN16>(rs, t.o100 + co), v101 = ldrec_t<IN16>(rs, t.o101 + co), v110 = ldrec_t<IN16>(rs, t.o110 + co), v111 = ldrec_t<IN16>(rs, t.o111 + co);
-  const float wx1 = t.tx, wx0 = 1.f - t.tx, wy1 = t.ty, wy0 = 1.f - t.ty, wz1 = t.tz, wz0 = 1.f - t.tz;
-  const float w000 = wx0 * wy0 * wz0, w001 = wx1 * wy0 * wz0, w010 = wx0 * wy1 * wz0, w011 = wx1 * wy1 * wz0;
-  const float w100 = wx0 * wy0 * wz1, w101 = wx1 * wy0 * wz1, w110 = wx0 * wy1 * wz1, w111 = wx1 * wy1 * wz1;
-  f32x4 r;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    float acc = v000[e] * w000;
-    // (inline asm keeps these as v_fmac_f32 with the weight as a plain operand)
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v001[e]), "v"(w001));
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v010[e]), "v"(w010));
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v011[e]), "v"(w011));
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v100[e]), "v"(w100));
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v101[e]), "v"(w101));
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v110[e]), "v"(w110));
-    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v111[e]), "v"(w111));
-    r[e] = acc;
-  }
-  if constexpr (OUT16)
-    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, __builtin_convertvector(r, bf16x4r)), ro,
-                                          (int)((u32)((z * H + y) * W + x) * 32u + (u32)q * 8u), 0, 2);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, r), ro, (int)((u32)((z * H + y) * W + x) * 64u + (u32)q * 16u), 0, 2);
-}
-
-// resample_bwd_coef_kernel
+// coefficient gradient, stage 1, generic form (block geometry: bwd_vox_per_block / bwd_tile; stage 2: resample_bwd_coef_reduce)
 template <int VEC>
-__global__ void __launch_bounds__(256) resample_bwd_coef_indexed_kernel(
-    const float* __restrict__ gout, const float* __restrict__ vol, long vol_bstride, const int* __restrict__ vol_idx, int vol_n,
+__global__ void __launch_bounds__(256) GATHER_KERNEL(resample_bwd_coef)(
+    const float* __restrict__ gout, const float* __restrict__ vol, long vol_bstride, GATHER_TABLE_PARAMS
     const float* __restrict__ coef, float* __restrict__ partial, int nblk, int vpb, BwdTile bt,
     int N, int D, int H, int W, int C, int lpv, Steps st) {
   // lpv = lanes cooperating on one voxel: a power of two <= 64 with lpv * VEC >= C
@@ -177,7 +102,7 @@ __global__ void __launch_bounds__(256) resample_bwd_coef_indexed_kernel(
       float gx, gy, gz;
       eval_grid<LF_MAP_O2C>(cf, x, y, z, W, H, D, st, gx, gy, gz, a, b, k);
       const Tap t = make_tap(gx, gy, gz, W, H, D);
-      const float* base = vol + vol_offset(n, vol_bstride, vol_idx, vol_n) + (long)q * VEC;
+      const float* base = vol + GATHER_VOL_OFFSET + (long)q * VEC;
       const float* g = gout + (((long)n * nvox + v) * C) + (long)q * VEC;
       const long o00 = (long)((t.z0 * H + t.y0) * W) * C, o01 = (long)((t.z0 * H + t.y1) * W) * C;
       const long o10 = (long)((t.z1 * H + t.y0) * W) * C, o11 = (long)((t.z1 * H + t.y1) * W) * C;
@@ -230,10 +155,98 @@ __global__ void __launch_bounds__(256) resample_bwd_coef_indexed_kernel(
   }
 }
 
-// resample_bwd_coef_c16_kernel
+// lean gather (what makes the lean variants lean: above Tap32 in resample.hip):
+// one thread per (voxel, 4-channel group); block = compact 2^lx x 2^ly x 2^lz tile; C % 4 == 0
+template <int KIND>
+__global__ void __launch_bounds__(256) GATHER_KERNEL(resample_fwd_lean)(
+    const float* __restrict__ vol, long vol_bstride, GATHER_TABLE_PARAMS const float* __restrict__ coef,
+    float* __restrict__ out, int D, int H, int W, int C, int lpt, int lx, int ly, int lz, int nbz, Steps st) {
+  const int lpv = C >> 2;
+  const int n = blockIdx.z / nbz, bz = blockIdx.z - n * nbz;
+  const int slot = threadIdx.x / lpt, q0 = threadIdx.x - slot * lpt;
+  if (slot >= (1 << (lx + ly + lz))) return;
+  const int x = (blockIdx.x << lx) + (slot & ((1 << lx) - 1));
+  const int y = (blockIdx.y << ly) + ((slot >> lx) & ((1 << ly) - 1));
+  const int z = (bz << lz) + (slot >> (lx + ly));
+  if (x >= W || y >= H || z >= D) return;
+  const u32 rec = (u32)C * 4u;
+  const u32 sample_bytes = (u32)D * (u32)H * (u32)W * rec;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(vol + GATHER_VOL_OFFSET), 0, sample_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)(out + (long)n * D * H * W * C), 0, sample_bytes, 0x00020000);
+  const float* cf = coef + n * LF_MAP_COEFS;
+  float gx, gy, gz, a, b, k;
+  eval_grid<KIND>(cf, x, y, z, W, H, D, st, gx, gy, gz, a, b, k);
+  const Tap32 t = make_tap32(gx, gy, gz, W, H, D, rec);
+  const float wx1 = t.tx, wx0 = 1.f - t.tx, wy1 = t.ty, wy0 = 1.f - t.ty, wz1 = t.tz, wz0 = 1.f - t.tz;
+  const float w000 = wx0 * wy0 * wz0, w001 = wx1 * wy0 * wz0, w010 = wx0 * wy1 * wz0, w011 = wx1 * wy1 * wz0;
+  const float w100 = wx0 * wy0 * wz1, w101 = wx1 * wy0 * wz1, w110 = wx0 * wy1 * wz1, w111 = wx1 * wy1 * wz1;
+  const u32 orow = (u32)((z * H + y) * W + x) * rec;
+  for (int q = q0; q < lpv; q += lpt) {
+    const u32 co = (u32)q * 16u;
+    const f32x4 v000 = ldrec(rs, t.o000 + co), v001 = ldrec(rs, t.o001 + co), v010 = ldrec(rs, t.o010 + co), v011 = ldrec(rs, t.o011 + co);
+    const f32x4 v100 = ldrec(rs, t.o100 + co), v101 = ldrec(rs, t.o101 + co), v110 = ldrec(rs, t.o110 + co), v111 = ldrec(rs, t.o111 + co);
+    const f32x4 r = v000 * w000 + v001 * w001 + v010 * w010 + v011 * w011 + v100 * w100 + v101 * w101 + v110 * w110 + v111 * w111;
+    // streamed output (nt): keep L2 for the gathered volume
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, r), ro, (int)(orow + co), 0, 2);
+  }
+}
+
+// C == 16 specialisation of the lean gather (variant 3): fixed 4x4x4 tile, no integer division, no channel loop, one
+// scalar-weight FMA per channel and corner (the generic form lets the compiler pack the FMAs in pairs, which costs
+// a register move per weight to build the pairs).
+// IO (round 5, training step under the bf16 storage policy): bit 0 -- the sampled volume, bit 1 -- the output are bf16
+// channels-last records (32 B per voxel); the interpolation itself is the same fp32 arithmetic.
+template <int KIND, int IO = 0>
+__global__ void __launch_bounds__(256) GATHER_KERNEL(resample_fwd_c16)(
+    const float* __restrict__ vol, long vol_bstride, GATHER_TABLE_PARAMS const float* __restrict__ coef,
+    float* __restrict__ out, int D, int H, int W, int nbz, Steps st) {
+  constexpr bool IN16 = (IO & 1) != 0, OUT16 = (IO & 2) != 0;
+  constexpr u32 IREC = IN16 ? 32u : 64u, OREC = OUT16 ? 32u : 64u;
+  const int n = blockIdx.z / nbz, bz = blockIdx.z - n * nbz;
+  const int q = threadIdx.x & 3, vs = threadIdx.x >> 2;
+  const int x = (blockIdx.x << 2) + (vs & 3), y = (blockIdx.y << 2) + ((vs >> 2) & 3), z = (bz << 2) + (vs >> 4);
+  if (x >= W || y >= H || z >= D) return;
+  const u32 nvox = (u32)D * (u32)H * (u32)W;
+  // (vol_bstride counts ELEMENTS; the pointers are declared float*: byte arithmetic for the bf16 forms)
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)vol + GATHER_VOL_OFFSET * (IN16 ? 2 : 4)), 0, nvox * IREC, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void*)((char*)out + (long)n * nvox * OREC), 0, nvox * OREC, 0x00020000);
+  const float* cf = coef + n * LF_MAP_COEFS;
+  float gx, gy, gz, a, b, k;
+  eval_grid<KIND>(cf, x, y, z, W, H, D, st, gx, gy, gz, a, b, k);
+  const Tap32 t = make_tap32(gx, gy, gz, W, H, D, IREC);
+  const u32 co = (u32)q * (IREC / 4u);
+  const f32x4 v000 = ldrec_t<IN16>(rs, t.o000 + co), v001 = ldrec_t<IN16>(rs, t.o001 + co), v010 = ldrec_t<IN16>(rs, t.o010 + co), v011 = ldrec_t<IN16>(rs, t.o011 + co);
+  const f32x4 v100 = ldrec_t<IN16>(rs, t.o100 + co), v101 = ldrec_t<IN16>(rs, t.o101 + co), v110 = ldrec_t<IN16>(rs, t.o110 + co), v111 = ldrec_t<IN16>(rs, t.o111 + co);
+  const float wx1 = t.tx, wx0 = 1.f - t.tx, wy1 = t.ty, wy0 = 1.f - t.ty, wz1 = t.tz, wz0 = 1.f - t.tz;
+  const float w000 = wx0 * wy0 * wz0, w001 = wx1 * wy0 * wz0, w010 = wx0 * wy1 * wz0, w011 = wx1 * wy1 * wz0;
+  const float w100 = wx0 * wy0 * wz1, w101 = wx1 * wy0 * wz1, w110 = wx0 * wy1 * wz1, w111 = wx1 * wy1 * wz1;
+  f32x4 r;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float acc = v000[e] * w000;
+    // (inline asm keeps these as v_fmac_f32 with the weight as a plain operand)
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v001[e]), "v"(w001));
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v010[e]), "v"(w010));
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v011[e]), "v"(w011));
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v100[e]), "v"(w100));
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v101[e]), "v"(w101));
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v110[e]), "v"(w110));
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "v"(v111[e]), "v"(w111));
+    r[e] = acc;
+  }
+  if constexpr (OUT16)
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2_t, __builtin_convertvector(r, bf16x4r)), ro,
+                                          (int)((u32)((z * H + y) * W + x) * 32u + (u32)q * 8u), 0, 2);
+  else
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, r), ro, (int)((u32)((z * H + y) * W + x) * 64u + (u32)q * 16u), 0, 2);
+}
+
+// coefficient gradient, C == 16 (4 lanes per voxel, 64 voxels per block-iteration): block = 2^lg-voxel tile walked in
+// 4x4x4 sub-tiles; thread (v = tid >> 2, q = tid & 3) keeps its position inside the sub-tile, the sub-tile index is
+// wave-uniform
 template <int MINW, int UNR>
-__global__ void __launch_bounds__(256, MINW) resample_bwd_coef_c16_indexed_kernel(
-    const float* __restrict__ gout, const float* __restrict__ vol, long vol_bstride, const int* __restrict__ vol_idx, int vol_n,
+__global__ void __launch_bounds__(256, MINW) GATHER_KERNEL(resample_bwd_coef_c16)(
+    const float* __restrict__ gout, const float* __restrict__ vol, long vol_bstride, GATHER_TABLE_PARAMS
     const float* __restrict__ coef, float* __restrict__ partial, int nblk, int vpb, BwdTile bt,
     int D, int H, int W, Steps st) {
   const unsigned fb = xcd_contiguous(blockIdx.x, gridDim.x);
@@ -241,7 +254,7 @@ __global__ void __launch_bounds__(256, MINW) resample_bwd_coef_c16_indexed_kerne
   const float* cf = coef + n * LF_MAP_COEFS;
   const u32 rec = 64u;
   const u32 sample_bytes = (u32)D * (u32)H * (u32)W * rec;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(vol + vol_offset(n, vol_bstride, vol_idx, vol_n)), 0, sample_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(vol + GATHER_VOL_OFFSET), 0, sample_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)(gout + (long)n * D * H * W * 16), 0, sample_bytes, 0x00020000);
   const int tx = blk % bt.ntx, ty = (blk / bt.ntx) % bt.nty, tz = blk / (bt.ntx * bt.nty);
   const int q = threadIdx.x & 3, vs = threadIdx.x >> 2;          // vs = position inside a 4x4x4 sub-tile
@@ -319,10 +332,20 @@ __global__ void __launch_bounds__(256, MINW) resample_bwd_coef_c16_indexed_kerne
   }
 }
 
-// resample_bwd_coef_c16_dedup_kernel
+// coefficient gradient, C == 16, per-voxel arithmetic done ONCE per voxel (variant 6 of lf_set_tuning key 2).
+// The kernel above spends most of its VALU issue on work that is identical in the four lanes sharing a voxel (map, taps,
+// derivative algebra: ~3/4 of its ~200 instructions per lane and voxel), and VALU issue is what bounds it (DESIGN 4.4).
+// Here a WAVE owns a 4x4x4 sub-tile and works on it in three phases that only meet through 3 KB of wave-private LDS:
+//   A  lane = voxel (64 voxels per instruction): map, clip, corner offsets -> one 16-byte record per voxel in LDS
+//      (fractions, clip masks and lattice coordinates stay in the lane's registers for phase C);
+//   B  four passes of 16 voxels, lane = (voxel, channel quarter) as before: the gathers stay coalesced 64-byte records
+//      through L1 (a lane-per-voxel gather would quadruple the L1 look-ups), contraction with the gradient, quad sums;
+//      the 8 per-corner scalars of a voxel go back to LDS;
+//   C  lane = voxel again: spatial derivatives, clip masks, the 18 basis sums.
+// No workgroup barrier; waves walk their own sub-tiles.  Same value as the kernel above, different summation order.
 template <int PIF, int MINW, bool GOPF = false>
-__global__ void __launch_bounds__(256, MINW) resample_bwd_coef_c16_dedup_indexed_kernel(
-    const float* __restrict__ gout, const float* __restrict__ vol, long vol_bstride, const int* __restrict__ vol_idx, int vol_n,
+__global__ void __launch_bounds__(256, MINW) GATHER_KERNEL(resample_bwd_coef_c16_dedup)(
+    const float* __restrict__ gout, const float* __restrict__ vol, long vol_bstride, GATHER_TABLE_PARAMS
     const float* __restrict__ coef, float* __restrict__ partial, int nblk, int vpb, BwdTile bt,
     int D, int H, int W, Steps st) {
   __shared__ u32x4_t tapbuf[4][64];                             // per wave: o000 | dead, x / y / z corner strides (bytes, 0 if clamped)
@@ -333,7 +356,7 @@ __global__ void __launch_bounds__(256, MINW) resample_bwd_coef_c16_dedup_indexed
   const float* cf = coef + n * LF_MAP_COEFS;
   const u32 rec = 64u;
   const u32 sample_bytes = (u32)D * (u32)H * (u32)W * rec;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(vol + vol_offset(n, vol_bstride, vol_idx, vol_n)), 0, sample_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)(vol + GATHER_VOL_OFFSET), 0, sample_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)(gout + (long)n * D * H * W * 16), 0, sample_bytes, 0x00020000);
   const int tx = blk % bt.ntx, ty = (blk / bt.ntx) % bt.nty, tz = blk / (bt.ntx * bt.nty);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

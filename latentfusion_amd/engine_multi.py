@@ -16,8 +16,8 @@ split (fused_zsplit) from the batch's tile count N x tiles, so a row's summation
 Several objects (a scene's frame holds a few, each with its own latent volume): `z_obj` is then a sequence of T volumes, one
 per target.  Nothing below the resampler is per object -- camera blocks, projection, decoder, loss and optimiser work per row
 with shared weights -- so the only change to an iteration is that the two resampler launches take a per-row table of volumes
-(lf_resample3d_fwd_indexed, lf_resample3d_bwd_coef_indexed); per row they are bit-identical to the one-volume entry points
-on that row's volume, so everything above holds per (object, target) as it does per target.
+(lf_resample3d_fwd_indexed, lf_resample3d_bwd_coef_indexed: the one-volume kernels' source compiled a second time with the
+table lookup, csrc/resample_gather.inc); per row they are bit-identical to the one-volume entry points on that row's volume, so everything above holds per (object, target) as it does per target.
 """
 import torch
 
@@ -186,20 +186,15 @@ class MultiTargetEngine(RenderLoopEngine):
         return x0
 
     def _bwd_coef(self, g, cf20, gcoef18, n):
+        # (one path: a table of volumes only chooses the entry point, its scratch rule and how the volume is named)
         L = _lib.lib()
         S = self.S
-        if self.zs is not None:
-            table = self._table(n)
-            nbytes = L.lf_resample3d_bwd_coef_indexed_scratch_bytes(n, self._n, S, S, S)
-            scratch = torch.empty(nbytes // 4 + 1, device=self.dev, dtype=torch.float32)
-            with ops._timed('resample_bwd_coef'):
-                check(L.lf_resample3d_bwd_coef_indexed(g.data_ptr(), self.zs.data_ptr(), self.zs.shape[0], table.data_ptr(),
-                                                       cf20.data_ptr(), gcoef18.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
-                                                       n, S, S, S, self.C, self._n, _s()), 'lf_resample3d_bwd_coef_indexed')
-            return
-        nbytes = L.lf_resample3d_bwd_coef_part_scratch_bytes(n, self._n, S, S, S)
+        if self.zs is None:
+            name, vol = 'lf_resample3d_bwd_coef_part', (self.z.data_ptr(), 1)
+        else:
+            name, vol = 'lf_resample3d_bwd_coef_indexed', (self.zs.data_ptr(), self.zs.shape[0], self._table(n).data_ptr())
+        nbytes = getattr(L, name + '_scratch_bytes')(n, self._n, S, S, S)
         scratch = torch.empty(nbytes // 4 + 1, device=self.dev, dtype=torch.float32)
         with ops._timed('resample_bwd_coef'):
-            check(L.lf_resample3d_bwd_coef_part(g.data_ptr(), self.z.data_ptr(), 1, cf20.data_ptr(), gcoef18.data_ptr(),
-                                                scratch.data_ptr(), scratch.numel() * 4, n, S, S, S, self.C, self._n, _s()),
-                  'lf_resample3d_bwd_coef_part')
+            check(getattr(L, name)(g.data_ptr(), *vol, cf20.data_ptr(), gcoef18.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
+                                   n, S, S, S, self.C, self._n, _s()), name)

@@ -6,6 +6,10 @@ instruction (addresses dropped, encodings kept).  Kernels that only the working 
 
     python tools/resample_isa_diff.py [--rev HEAD] [--out profiles/resample_indexed_isa.txt]
 
+The kernels that exist as a plain and an indexed form are written once (csrc/resample_gather.inc, included twice by
+resample.hip) and keep their names, so a change to that file is checked here like any other: every symbol of both forms
+against the parent's (profiles/resample_shared_isa.txt is the report of the change that folded the two copies into one).
+
 The report's diff section is empty when nothing changed; the exit status is 1 otherwise.  Needs hipcc, no GPU.
 """
 import argparse
