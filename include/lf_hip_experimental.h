@@ -26,7 +26,9 @@ extern "C" {
  * the output voxels per tile when every sample has its own volume), 3 = as 2 without the binned form, 4 = as 2 with the tile pass that
  * gives a list entry 16 lanes instead of a lane quad (round-6 A/B: slower, profiles/r06_splat_ab.txt).  key 5: resident workgroups
  * per CU of lf_conv3d_c16_ring_bf16, 2 (default) or 3.  key 6: samples per pass of the binned splat at most (0 = default: as many
- * as 512 MB of lists hold; tests use 1 or 2 to walk the multi-pass path at small sizes).
+ * as 512 MB of lists hold; tests use 1 or 2 to walk the multi-pass path at small sizes).  key 7: the fp32 Winograd 16-channel
+ * kernels (lf_conv3d_c16_wino, _projfwd, _projbwd), 1 = the transforms next to the MFMAs as packed fp32 instructions (default),
+ * 0 = the scalar form they replace (bit-identical results; profiles/wino_pack_ab.json).
  * Returns the previous value or LF_EINVAL. */
 int lf_set_tuning(int key, int value);
 

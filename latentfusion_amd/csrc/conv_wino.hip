@@ -88,10 +88,22 @@ __device__ __forceinline__ float fast_rcp(float x) {
 }
 
 // a - b as two v_pk_add_f32 with negated second source.  (LLVM packs <4 x float> fadd into v_pk_add_f32 but
-// scalarises fsub; on this kernel every VALU instruction competes with the fp32 MFMAs for the issue pipe.)
-// Only used where neither operand is an MFMA result and the result does not feed an MFMA directly: the
-// MFMA <-> VALU wait states are inserted by the compiler, which does not look inside asm (feeding the
-// B operand of an MFMA straight from this asm gave wrong results on gfx950).
+// scalarises fsub; on this kernel every VALU instruction competes with the fp32 MFMAs for the issue pipe: a packed
+// add costs 1.2x a scalar one there and does the work of two, profiles/wino_pack_rates.txt.)
+// The compiler pads MFMA <-> VALU wait states only between instructions it can see, and it does not look inside asm.
+// pk_sub itself is for operands that are not MFMA results and results that do not feed an MFMA.  The forms next to
+// an MFMA (wino_rows_packed, below) keep the wait states by construction; the rules, read from the compiler's own padding of
+// the scalar form (ROCm 7.2, gfx950):
+//   R1  VALU write -> v_mfma_f32_16x16x4_f32 reading it as B: 2 wait states.  The packed values of an MFMA pair pass
+//       through pk_fence (an `s_nop 1` every producer feeds and every MFMA of the pair reads from).
+//   R2  v_mfma_f32_16x16x4_f32 result -> VALU read: 10 wait states (40 clk).  The MFMA holds the pipe for 8 passes (32 clk),
+//       so an instruction behind TWO later MFMAs of the same wave is >= 64 clk behind the result's MFMA; sched_barrier(0)
+//       on both sides of those two MFMAs keeps the reader behind them.  The last row of a group has no later MFMA: its
+//       readers sit behind a compiler-visible read of the same registers, which the compiler pads, and take that read's
+//       value as an operand (`gate`).
+//   R3  VALU write over a register an MFMA in flight still reads: every packed op here writes IN PLACE over its first
+//       source (a transform value no MFMA reads, or an accumulator whose MFMAs have retired by R2), so the register
+//       allocator never hands an asm result a register that an MFMA has just released.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x4 pk_sub(f32x4 a, f32x4 b) {
   f32x2 lo, hi;
@@ -101,9 +113,93 @@ __device__ __forceinline__ f32x4 pk_sub(f32x4 a, f32x4 b) {
   return (f32x4){lo[0], lo[1], hi[0], hi[1]};
 }
 
+// a -= b / a += b in place, two packed instructions each (R3 above); `gate` is an ordering operand only (R2)
+__device__ __forceinline__ void pk_sub_to(f32x4& a, const f32x4 b, int gate = 0) {
+  f32x2 alo = {a[0], a[1]}, ahi = {a[2], a[3]};
+  const f32x2 blo = {b[0], b[1]}, bhi = {b[2], b[3]};
+  asm("v_pk_add_f32 %0, %0, %1 neg_lo:[0,1] neg_hi:[0,1]" : "+v"(alo) : "v"(blo), "s"(gate));
+  asm("v_pk_add_f32 %0, %0, %1 neg_lo:[0,1] neg_hi:[0,1]" : "+v"(ahi) : "v"(bhi), "s"(gate));
+  a = (f32x4){alo[0], alo[1], ahi[0], ahi[1]};
+}
+__device__ __forceinline__ void pk_add_to(f32x4& a, const f32x4 b, int gate = 0) {
+  f32x2 alo = {a[0], a[1]}, ahi = {a[2], a[3]};
+  const f32x2 blo = {b[0], b[1]}, bhi = {b[2], b[3]};
+  asm("v_pk_add_f32 %0, %0, %1" : "+v"(alo) : "v"(blo), "s"(gate));
+  asm("v_pk_add_f32 %0, %0, %1" : "+v"(ahi) : "v"(bhi), "s"(gate));
+  a = (f32x4){alo[0], alo[1], ahi[0], ahi[1]};
+}
+// R1: both B operands of an MFMA pair pass through here after their last packed write
+__device__ __forceinline__ void pk_fence(f32x4& a, f32x4& b) { asm("s_nop 1" : "+v"(a), "+v"(b)); }
+
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+// The MFMA phase of one 16-tile group in the packed form: rows b = 0..3 of the y input transform, their 16 MFMAs each
+// and the x / y output transforms, as eight MFMA pairs p = (b, cp) of 2 x 4 chained MFMAs.  Per pair:
+//   [barrier] the pair's first two MFMAs [barrier] output-transform ops on the PREVIOUS pair's results (R2: two MFMAs
+//   behind them), B operands of the NEXT pair (in place, fenced: R1, R3), the pair's other six MFMAs.
+// Between the barriers the compiler schedules freely.
+__device__ __forceinline__ void wino_rows_packed(f32x4 (&vx)[4][4], const float (&wt)[64], f32x4 (&Yg)[4]) {
+  f32x4 m[4][4];                                               // [b][c]
+  f32x4 vb[8][2];                                              // B operands of pair p
+  auto operands = [&](int p) {
+    const int b = p >> 1, cp = (p & 1) * 2;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int c = cp + h;
+      if (b == 0) { pk_sub_to(vx[0][c], vx[2][c]); vb[p][h] = vx[0][c]; }      // vx[0] is not read again
+      if (b == 1) vb[p][h] = vx[1][c] + vx[2][c];                             // (compiler-visible: padded by the compiler)
+      if (b == 2) { pk_sub_to(vx[2][c], vx[1][c]); vb[p][h] = vx[2][c]; }      // vx[2] is not read again
+      if (b == 3) { pk_sub_to(vx[1][c], vx[3][c]); vb[p][h] = vx[1][c]; }
+    }
+    if (b != 1) pk_fence(vb[p][0], vb[p][1]);
+  };
+  // x output transform t0 = (m0 + m1) + m2, t1 = (m1 - m2) - m3 of row b, then the y output transform accumulates
+  auto row_first = [&](int b) { pk_add_to(m[b][0], m[b][1]); };                // m0 <- m0 + m1
+  auto row_rest = [&](int b, int gate = 0) {
+    pk_add_to(m[b][0], m[b][2], gate);                                        // t0
+    pk_sub_to(m[b][1], m[b][2], gate);
+    pk_sub_to(m[b][1], m[b][3], gate);                                        // t1
+    const f32x4 t0 = m[b][0], t1 = m[b][1];
+    if (b == 0) { Yg[0] = t0; Yg[1] = t1; }
+    if (b == 1) { pk_add_to(Yg[0], t0); pk_add_to(Yg[1], t1); Yg[2] = t0; Yg[3] = t1; }
+    if (b == 2) { pk_add_to(Yg[0], t0); pk_add_to(Yg[1], t1); pk_sub_to(Yg[2], t0); pk_sub_to(Yg[3], t1); }
+    if (b == 3) { pk_sub_to(Yg[2], t0); pk_sub_to(Yg[3], t1); }
+  };
+  operands(0);
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    const int b = p >> 1, cp = (p & 1) * 2;
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      m[b][cp + h] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[(b * 4 + cp + h) * 4], vb[p][h][0], (f32x4){0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (p > 0) {
+      if (p & 1) row_first(b);
+      else row_rest(b - 1);
+    }
+    if (p < 7) operands(p + 1);
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        m[b][cp + h] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[(b * 4 + cp + h) * 4 + i], vb[p][h][i], m[b][cp + h], 0, 0, 0);
+    if constexpr ((WINO_ABL & 4) != 0) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          m[b][cp + h] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[(b * 4 + cp + h) * 4 + i], vb[p][h][i], m[b][cp + h], 0, 0, 0);
+    }
+  }
+  // R2, last row: no later MFMA to stand behind.  One compiler-visible VALU read of each of the two last results (the
+  // compiler pads it and then knows the results have landed); every packed op that reads them takes that read's value
+  // as an operand, so it cannot be scheduled ahead of it.
+  const int landed = __builtin_amdgcn_readfirstlane(__float_as_int(m[3][2][0])) | __builtin_amdgcn_readfirstlane(__float_as_int(m[3][3][0]));
+  row_rest(3, landed);
+}
 
 // SPLIT = false: all-fp32 products, wt = U[a][(b,c)][k-chunk] for v_mfma_f32_16x16x4_f32.
 // SPLIT = true : every Winograd-domain product U.V from three v_mfma_f32_16x16x16_f16 accumulating in fp32,
@@ -111,7 +207,10 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 //                whi / wlo = the two halves of U, V is split on the fly after scaling by the power of two in_scale.
 // OFFX (the fused forms, which have no registers to spare): only off[r][0] is kept; the rows dy = 2, 3, whose quarter
 // swizzle differs in bit 0, derive their offset with one v_xor per read instead of a second register per residue.
-template <int A, bool SPLIT, bool OFFX = false>
+// PACK (all-fp32 path only): the y input transform that feeds the B operands and the x / y output transforms on the MFMA
+// results as packed asm (rules R1 - R3 at pk_sub), same operations in the same order and association as the scalar
+// form, which stays selectable (lf_set_tuning key 7) for the bit-identity test and the A/B.
+template <int A, bool SPLIT, bool OFFX = false, bool PACK = false>
 __device__ __forceinline__ void wino_compute(const unsigned char* __restrict__ buf, const int (&off)[8][2],
                                               const float (&wt)[64], const f16x4 (&whi)[16], const f16x4 (&wlo)[16],
                                               float in_scale, unsigned char* __restrict__ pdst,
@@ -177,71 +276,75 @@ __device__ __forceinline__ void wino_compute(const unsigned char* __restrict__ b
     }
     CTS(9 + 2 * g);
     __builtin_amdgcn_s_setprio(WINO_PM);
+    if constexpr (PACK && !SPLIT) {
+      wino_rows_packed(vx, wt, Yg);
+    } else {
 #pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      f32x4 m[4];
-      // two frequencies of the row advance together, one k-chunk at a time: a 16x16x4 f32 MFMA can issue every
-      // 32 cycles but its result feeds a dependent one only after 40, so a single back-to-back chain would bubble
+      for (int b = 0; b < 4; ++b) {
+        f32x4 m[4];
+        // two frequencies of the row advance together, one k-chunk at a time: a 16x16x4 f32 MFMA can issue every
+        // 32 cycles but its result feeds a dependent one only after 40, so a single back-to-back chain would bubble
 #pragma unroll
-      for (int cp = 0; cp < 4; cp += 2) {
-        f32x4 v[2];
+        for (int cp = 0; cp < 4; cp += 2) {
+          f32x4 v[2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int c = cp + h;
-          v[h] = (b == 0) ? (vx[0][c] - vx[2][c])
-               : (b == 1) ? (vx[1][c] + vx[2][c])
-               : (b == 2) ? (vx[2][c] - vx[1][c])
-                          : (vx[1][c] - vx[3][c]);
-          m[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        }
-        if constexpr (!SPLIT) {
+          for (int h = 0; h < 2; ++h) {
+            const int c = cp + h;
+            v[h] = (b == 0) ? (vx[0][c] - vx[2][c])
+                 : (b == 1) ? (vx[1][c] + vx[2][c])
+                 : (b == 2) ? (vx[2][c] - vx[1][c])
+                            : (vx[1][c] - vx[3][c]);
+            m[c] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          }
+          if constexpr (!SPLIT) {
 #pragma unroll
-          for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-              m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[(b * 4 + cp + h) * 4 + i], v[h][i], m[cp + h], 0, 0, 0);
-          if constexpr ((WINO_ABL & 4) != 0) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
               for (int h = 0; h < 2; ++h)
                 m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[(b * 4 + cp + h) * 4 + i], v[h][i], m[cp + h], 0, 0, 0);
-          }
-        } else {
-          // fp32 Winograd-domain value -> f16 hi + lo (exact to 22 bits), three product terms
-          f16x4 vhi[2], vlo[2], vl2[2];
+            if constexpr ((WINO_ABL & 4) != 0) {
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const f32x4 vs = v[h] * in_scale;
-            vhi[h] = __builtin_convertvector(vs, f16x4);
-            const f32x4 r1 = vs - __builtin_convertvector(vhi[h], f32x4);
-            vlo[h] = __builtin_convertvector(r1, f16x4);
-            if constexpr ((WINO_ABL & 8) != 0)                  // timing proxy of a THREE-piece split: third piece + 6 products
-              vl2[h] = __builtin_convertvector(r1 - __builtin_convertvector(vlo[h], f32x4), f16x4);
-          }
+              for (int i = 0; i < 2; ++i)
 #pragma unroll
-          for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(whi[b * 4 + cp + h], vlo[h], m[cp + h], 0, 0, 0);
+                for (int h = 0; h < 2; ++h)
+                  m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x4f32(wt[(b * 4 + cp + h) * 4 + i], v[h][i], m[cp + h], 0, 0, 0);
+            }
+          } else {
+            // fp32 Winograd-domain value -> f16 hi + lo (exact to 22 bits), three product terms
+            f16x4 vhi[2], vlo[2], vl2[2];
 #pragma unroll
-          for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(wlo[b * 4 + cp + h], vhi[h], m[cp + h], 0, 0, 0);
+            for (int h = 0; h < 2; ++h) {
+              const f32x4 vs = v[h] * in_scale;
+              vhi[h] = __builtin_convertvector(vs, f16x4);
+              const f32x4 r1 = vs - __builtin_convertvector(vhi[h], f32x4);
+              vlo[h] = __builtin_convertvector(r1, f16x4);
+              if constexpr ((WINO_ABL & 8) != 0)                  // timing proxy of a THREE-piece split: third piece + 6 products
+                vl2[h] = __builtin_convertvector(r1 - __builtin_convertvector(vlo[h], f32x4), f16x4);
+            }
 #pragma unroll
-          for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(whi[b * 4 + cp + h], vhi[h], m[cp + h], 0, 0, 0);
-          if constexpr ((WINO_ABL & 8) != 0) {
+            for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(whi[b * 4 + cp + h], vlo[h], m[cp + h], 0, 0, 0);
 #pragma unroll
-            for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(wlo[b * 4 + cp + h], vlo[h], m[cp + h], 0, 0, 0);
+            for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(wlo[b * 4 + cp + h], vhi[h], m[cp + h], 0, 0, 0);
 #pragma unroll
-            for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(whi[b * 4 + cp + h], vl2[h], m[cp + h], 0, 0, 0);
+            for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(whi[b * 4 + cp + h], vhi[h], m[cp + h], 0, 0, 0);
+            if constexpr ((WINO_ABL & 8) != 0) {
 #pragma unroll
-            for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(wlo[b * 4 + cp + h], vl2[h], m[cp + h], 0, 0, 0);
+              for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(wlo[b * 4 + cp + h], vlo[h], m[cp + h], 0, 0, 0);
+#pragma unroll
+              for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(whi[b * 4 + cp + h], vl2[h], m[cp + h], 0, 0, 0);
+#pragma unroll
+              for (int h = 0; h < 2; ++h) m[cp + h] = __builtin_amdgcn_mfma_f32_16x16x16f16(wlo[b * 4 + cp + h], vl2[h], m[cp + h], 0, 0, 0);
+            }
           }
         }
+        // x output transform, then accumulate the y output transform
+        const f32x4 t0 = m[0] + m[1] + m[2];
+        const f32x4 t1 = m[1] - m[2] - m[3];
+        if (b == 0) { Yg[0] = t0; Yg[1] = t1; }
+        if (b == 1) { Yg[0] += t0; Yg[1] += t1; Yg[2] = t0; Yg[3] = t1; }
+        if (b == 2) { Yg[0] += t0; Yg[1] += t1; Yg[2] = pk_sub(Yg[2], t0); Yg[3] = pk_sub(Yg[3], t1); }
+        if (b == 3) { Yg[2] = pk_sub(Yg[2], t0); Yg[3] = pk_sub(Yg[3], t1); }
       }
-      // x output transform, then accumulate the y output transform
-      const f32x4 t0 = m[0] + m[1] + m[2];
-      const f32x4 t1 = m[1] - m[2] - m[3];
-      if (b == 0) { Yg[0] = t0; Yg[1] = t1; }
-      if (b == 1) { Yg[0] += t0; Yg[1] += t1; Yg[2] = t0; Yg[3] = t1; }
-      if (b == 2) { Yg[0] += t0; Yg[1] += t1; Yg[2] = pk_sub(Yg[2], t0); Yg[3] = pk_sub(Yg[3], t1); }
-      if (b == 3) { Yg[2] = pk_sub(Yg[2], t0); Yg[3] = pk_sub(Yg[3], t1); }
     }
     // partial outputs of z-frequency A -> the exchange region (separate from the halo, free since the last
     // barrier of the previous tile): 1 KiB blocks [wave][g][tyb][j], 64 float4 slots each at (L ^ ((L >> 3) & 7)),
@@ -284,7 +387,7 @@ struct WinoProj {
 // conflict-free by ds_read_b128 with lane = q * 16 + v (the hardware's lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...)
 __device__ __forceinline__ int tr_swz(int v) { return (0x78 >> (2 * ((v >> 2) & 3))) & 3; }
 
-template <bool SPLIT, int FUSE = 0>
+template <bool SPLIT, int FUSE = 0, bool PACK = false>
 __device__ __forceinline__ void conv3d_c16_wino_body(
     const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ norm_out,
@@ -608,10 +711,10 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
     unsigned* const tsp = nullptr;
 #endif
     switch (fa) {
-      case 0: wino_compute<0, SPLIT, FUSE != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
-      case 1: wino_compute<1, SPLIT, FUSE != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
-      case 2: wino_compute<2, SPLIT, FUSE != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
-      default: wino_compute<3, SPLIT, FUSE != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      case 0: wino_compute<0, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      case 1: wino_compute<1, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      case 2: wino_compute<2, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      default: wino_compute<3, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
     }
     TS(1);
     lds_barrier();                                  // every wave is done reading the halo; all partials are in LDS
@@ -838,12 +941,13 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
   }
 }
 
+template <bool PACK>
 __global__ void __launch_bounds__(256, 2) conv3d_c16_wino_kernel(
     const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ norm_out, int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z,
     int ntiles, float he, unsigned flags, float slope, float eps, const float* __restrict__ prev_y,
     const float* __restrict__ prev_norm, unsigned prev_flags, float* __restrict__ amax_out) {
-  conv3d_c16_wino_body<false>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags, slope, eps,
+  conv3d_c16_wino_body<false, 0, PACK>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags, slope, eps,
                               prev_y, prev_norm, prev_flags, nullptr, amax_out);
 }
 
@@ -857,26 +961,31 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_wino_f16x3_kernel(
                              prev_y, prev_norm, prev_flags, amax_in, amax_out);
 }
 
+template <bool PACK>
 __global__ void __launch_bounds__(256, 2) conv3d_c16_wino_projfwd_kernel(
     const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ norm_out, int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z,
     int ntiles, float he, unsigned flags, float slope, float eps, const float* __restrict__ prev_y,
     const float* __restrict__ prev_norm, unsigned prev_flags, WinoProj pj) {
-  conv3d_c16_wino_body<false, 1>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags, slope,
+  conv3d_c16_wino_body<false, 1, PACK>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags, slope,
                                  eps, prev_y, prev_norm, prev_flags, nullptr, nullptr, pj);
 }
 
+template <bool PACK>
 __global__ void __launch_bounds__(256, 2) conv3d_c16_wino_projbwd_kernel(
     const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ norm_out, int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z,
     int ntiles, float he, unsigned flags, float slope, float eps, const float* __restrict__ prev_y,
     const float* __restrict__ prev_norm, unsigned prev_flags, WinoProj pj) {
-  conv3d_c16_wino_body<false, 2>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags, slope,
+  conv3d_c16_wino_body<false, 2, PACK>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags, slope,
                                  eps, prev_y, prev_norm, prev_flags, nullptr, nullptr, pj);
 }
 
-template <bool COLUMNS = false, typename K, typename... Extra>
-int launch_wino(K kernel, const float* x, const void* upack, const float* bias, float* y, float* norm_out, int N, int D,
+// lf_set_tuning key 7: 1 = packed transforms next to the MFMAs (wino_rows_packed; default), 0 = the scalar form.  Bit-identical.
+int g_wino_pack = 1;
+
+template <auto kernel, bool COLUMNS = false, typename... Extra>
+int launch_wino(const float* x, const void* upack, const float* bias, float* y, float* norm_out, int N, int D,
                 int H, int W, float he, unsigned flags, float slope, float eps, const float* prev_y, const float* prev_norm,
                 unsigned prev_flags, void* stream, Extra... extra) {
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return LF_EINVAL;
@@ -896,7 +1005,7 @@ int launch_wino(K kernel, const float* x, const void* upack, const float* bias, 
            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
   }
   const size_t shmem = (size_t)LDSw;
-  static lf_devmask_t attr_set;                                   // (one instance per kernel: the template is per K)
+  static lf_devmask_t attr_set;                                   // (one instance per kernel: the template is per kernel)
   {
     hipError_t e = lf_ensure_dyn_lds(attr_set, (const void*)kernel, (int)shmem);
     if (e != hipSuccess) return (int)e;
@@ -911,6 +1020,13 @@ int launch_wino(K kernel, const float* x, const void* upack, const float* bias, 
 
 }  // namespace
 
+// tuning hook for lf_set_tuning (key 7, resample.hip)
+int lf_internal_wino_set_pack(int v) {
+  const int prev = g_wino_pack;
+  if (v == 0 || v == 1) g_wino_pack = v;
+  return prev;
+}
+
 // floats of the transformed-weight pack: [4 z-freq][16 (y,x)-freq][4 k-chunks][64 lanes]
 extern "C" size_t lf_conv3d_c16_wino_upack_floats(void) { return (size_t)4 * 16 * 4 * 64; }
 
@@ -919,8 +1035,10 @@ extern "C" int lf_conv3d_c16_wino(const float* x, const float* upack, const floa
                                   const float* prev_y, const float* prev_norm, unsigned prev_flags,
                                   float* amax_out, void* stream) {
   lf_clear_error();
-  return launch_wino(conv3d_c16_wino_kernel, x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y, prev_norm,
-                     prev_flags, stream, amax_out);
+  return g_wino_pack ? launch_wino<conv3d_c16_wino_kernel<true>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y,
+                                                                  prev_norm, prev_flags, stream, amax_out)
+                     : launch_wino<conv3d_c16_wino_kernel<false>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y,
+                                                                   prev_norm, prev_flags, stream, amax_out);
 }
 
 // halfs of the split transformed-weight pack: [4 z-freq][16 (y,x)-freq][hi, lo][64 lanes][4 cin]
@@ -931,7 +1049,7 @@ extern "C" int lf_conv3d_c16_wino_split(const float* x, const void* upack, const
                                         const float* prev_y, const float* prev_norm, unsigned prev_flags,
                                         const float* amax_in, float* amax_out, void* stream) {
   lf_clear_error();
-  return launch_wino(conv3d_c16_wino_f16x3_kernel, x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y,
+  return launch_wino<conv3d_c16_wino_f16x3_kernel>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y,
                      prev_norm, prev_flags, stream, amax_in, amax_out);
 }
 
@@ -947,8 +1065,10 @@ extern "C" int lf_conv3d_c16_wino_projfwd(const float* x, const float* upack, co
   if (!lf_aligned16(proj_wA) || !lf_aligned16(zp) || (proj_bias && !lf_aligned16(proj_bias))) return LF_EALIGN;
   if ((proj_flags & ~(LF_EPI_LRELU | LF_EPI_PIXELNORM)) != 0) return LF_EINVAL;
   WinoProj pj = {proj_wA, proj_bias, zp, pnorm, nullptr, nullptr, proj_he, proj_flags};
-  return launch_wino<true>(conv3d_c16_wino_projfwd_kernel, x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps,
-                           nullptr, nullptr, 0u, stream, pj);
+  return g_wino_pack ? launch_wino<conv3d_c16_wino_projfwd_kernel<true>, true>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope,
+                                                                                eps, nullptr, nullptr, 0u, stream, pj)
+                     : launch_wino<conv3d_c16_wino_projfwd_kernel<false>, true>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope,
+                                                                                 eps, nullptr, nullptr, 0u, stream, pj);
 }
 
 extern "C" int lf_conv3d_c16_wino_projbwd(const float* gp, const float* proj_wtA, float proj_he, const float* act,
@@ -962,6 +1082,8 @@ extern "C" int lf_conv3d_c16_wino_projbwd(const float* gp, const float* proj_wtA
   if (!lf_aligned16(gp) || !lf_aligned16(proj_wtA) || (prev_y && !lf_aligned16(prev_y))) return LF_EALIGN;
   if (prev_y != nullptr && (prev_flags & LF_EPI_ADD)) return LF_EINVAL;
   WinoProj pj = {proj_wtA, nullptr, nullptr, nullptr, gp, act_norm, proj_he, act_flags};
-  return launch_wino<true>(conv3d_c16_wino_projbwd_kernel, act, upack, nullptr, y, nullptr, N, D, H, W, he, 0u, slope, 0.f,
-                           prev_y, prev_norm, prev_flags, stream, pj);
+  return g_wino_pack ? launch_wino<conv3d_c16_wino_projbwd_kernel<true>, true>(act, upack, nullptr, y, nullptr, N, D, H, W, he, 0u, slope,
+                                                                                0.f, prev_y, prev_norm, prev_flags, stream, pj)
+                     : launch_wino<conv3d_c16_wino_projbwd_kernel<false>, true>(act, upack, nullptr, y, nullptr, N, D, H, W, he, 0u, slope,
+                                                                                 0.f, prev_y, prev_norm, prev_flags, stream, pj);
 }

@@ -1281,6 +1281,7 @@ extern "C" int lf_set_tuning(int key, int value) {
     return prev;
   }
   if (key == 3) return lf_internal_fused_set_cfg(value);            // fused wide-conv GEMM: workgroup shape 0..3, -1 = by shape
+  if (key == 7) return lf_internal_wino_set_pack(value);            // fp32 Winograd 16-channel kernels: 1 = packed transforms (default), 0 = scalar
   if (key == 5) return lf_internal_ring_bf16_set_wgs(value);        // bf16 ring convolution: resident workgroups per CU
   if (key == 2) {
     const int prev = g_bwd_coef_variant;

@@ -7,7 +7,10 @@ most of the deltas being chased):
     python tools/wino_ab.py scratch/a.so scratch/b.so ...
 
 Each variant is checked against the first one (max |diff| of forward and fused-backward outputs) and timed
-round-robin: forward (bias + LeakyReLU + PixelNorm) and data-gradient fused with the previous layer's backward."""
+round-robin: forward (bias + LeakyReLU + PixelNorm), data-gradient fused with the previous layer's backward and the
+forward with the factor projection riding on it (lf_conv3d_c16_wino_projfwd).  A whole liblf_hip.so works as a variant
+too (the parent commit's against this one's), and `path@0` / `path@1` selects the scalar / packed transforms of that
+library through lf_set_tuning(7, .) before each of its calls."""
 import ctypes
 import os
 import sys
@@ -30,11 +33,35 @@ flags = LF_EPI_LRELU | LF_EPI_PIXELNORM
 st = torch.cuda.current_stream().cuda_stream
 
 
-def bind(path):
+wp = torch.randn(16, 16 * S, generator=g).cuda()
+wA, phe = ops.pack_wino_proj(wp), ops.he_constant(wp.view(16, 16 * S, 1, 1))
+PJ = []                                                       # per variant: the projfwd call
+
+
+def bind(spec):
+    path, _, pack = spec.partition('@')
     L = ctypes.CDLL(os.path.abspath(path))
-    f = L.lf_conv3d_c16_wino
-    f.restype = ctypes.c_int
-    f.argtypes = [P, P, P, P, P] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, ctypes.c_float, ctypes.c_float, P, P, ctypes.c_uint, P, P]
+    f0 = L.lf_conv3d_c16_wino
+    f0.restype = ctypes.c_int
+    f0.argtypes = [P, P, P, P, P] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, ctypes.c_float, ctypes.c_float, P, P, ctypes.c_uint, P, P]
+    p0 = L.lf_conv3d_c16_wino_projfwd
+    p0.restype = ctypes.c_int
+    p0.argtypes = [P, P, P, P, P] + [ctypes.c_int] * 4 + [ctypes.c_float, ctypes.c_uint, ctypes.c_float, ctypes.c_float, P, P, P, P,
+                                                          ctypes.c_float, ctypes.c_uint, P]
+
+    def select():
+        if pack:
+            L.lf_set_tuning(7, int(pack))
+
+    def f(*a):
+        select()
+        return f0(*a)
+
+    def pj(y, nrm, zp, pn):
+        select()
+        return p0(x.data_ptr(), up.data_ptr(), b.data_ptr(), y.data_ptr(), nrm.data_ptr(), N, S, S, S, he, flags, 0.2, 1e-8,
+                  wA.data_ptr(), None, zp.data_ptr(), pn.data_ptr(), phe, flags, st)
+    PJ.append(pj)
     return f
 
 
@@ -50,6 +77,7 @@ specs = [(a.split(':') + ['both'])[:2] for a in sys.argv[1:]]
 sys.argv[1:] = [a for a, _ in specs]
 only = [o for _, o in specs]
 fs = [bind(p) for p in sys.argv[1:]]
+zps = []
 outs = []
 for i, f in enumerate(fs):
     y, nrm, go = torch.empty_like(x), torch.empty(N * S ** 3, device='cuda'), torch.empty_like(x)
@@ -58,12 +86,18 @@ for i, f in enumerate(fs):
         assert bw() == 0
     else:
         go.copy_(outs[0][2])
+    zp, pn = ops.empty_cl((N, 16, S, S), 'cuda'), torch.empty(N * S * S, device='cuda')
+    assert PJ[i](torch.empty_like(x), torch.empty_like(nrm), zp, pn) == 0
     torch.cuda.synchronize()
     outs.append((y, nrm, go, bw))
+    zps.append((zp, pn))
 for i, p in enumerate(sys.argv[1:]):
-    print(f'{p}: fwd diff vs first {(outs[i][0] - outs[0][0]).abs().max().item():.2e}, bwd diff {(outs[i][2] - outs[0][2]).abs().max().item():.2e}')
+    print(f'{p}: fwd diff vs first {(outs[i][0] - outs[0][0]).abs().max().item():.2e}, bwd diff {(outs[i][2] - outs[0][2]).abs().max().item():.2e}, '
+          f'projfwd zp diff {(zps[i][0] - zps[0][0]).abs().max().item():.2e}; bit-identical to first: '
+          f'{torch.equal(outs[i][0], outs[0][0]) and torch.equal(outs[i][2], outs[0][2]) and torch.equal(zps[i][0], zps[0][0])}')
 tf = [[] for _ in fs]
 tb = [[] for _ in fs]
+tp = [[] for _ in fs]
 for r in range(ROUNDS):
     for i, f in enumerate(fs):
         y, nrm, go, bw = outs[i]
@@ -81,6 +115,14 @@ for r in range(ROUNDS):
             e1.record()
             torch.cuda.synchronize()
             acc[i].append(e0.elapsed_time(e1) / 5)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            PJ[i](y, nrm, *zps[i])
+        e1.record()
+        torch.cuda.synchronize()
+        tp[i].append(e0.elapsed_time(e1) / 5)
 for i, p in enumerate(sys.argv[1:]):
-    a, c = sorted(tf[i]), sorted(tb[i])
-    print(f'{p}: fwd median {a[len(a) // 2]:.4f} ms (min {a[0]:.4f}), bwd+prev median {c[len(c) // 2]:.4f} ms (min {c[0]:.4f})')
+    a, c, d = sorted(tf[i]), sorted(tb[i]), sorted(tp[i])
+    print(f'{p}: fwd median {a[len(a) // 2]:.4f} ms (min {a[0]:.4f}), bwd+prev median {c[len(c) // 2]:.4f} ms (min {c[0]:.4f}), '
+          f'projfwd median {d[len(d) // 2]:.4f} ms (min {d[0]:.4f})')
