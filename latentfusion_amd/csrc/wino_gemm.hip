@@ -7,7 +7,7 @@
 //   lf_wino3d_output_transform:  M -> y [N][D][H][W][Cout]  with He scale, bias, LeakyReLU, PixelNorm fused
 // Both kernels put the channel axis on the lanes (float4 per lane), so every global access is a contiguous
 // row of channels.  All arithmetic fp32.
-#include "lf_common.h"
+#include "wino_ring.h"
 
 namespace {
 
@@ -30,32 +30,15 @@ __global__ void __launch_bounds__(256) wino3d_input_kernel(const float* __restri
   const bool za_ok = (unsigned)za < (unsigned)D, zb_ok = (unsigned)zb < (unsigned)D;
   const float* xs = x + (long)n * D * H * W * C;
   for (int q = lane; q * 4 < C; q += 64) {
-    f32x4 vx[4][4];
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy) {
-      const int yy = y0 + dy;
-      const bool y_ok = (unsigned)yy < (unsigned)H;
-      f32x4 d[4];
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx) {
-        const int xx = x0 + dx;
-        const bool ok = y_ok && (unsigned)xx < (unsigned)W;
-        f32x4 va = (f32x4){0.f, 0.f, 0.f, 0.f}, vb = va;
-        if (ok && za_ok) va = *(const f32x4*)(xs + (((long)za * H + yy) * W + xx) * C + q * 4);
-        if (ok && zb_ok) vb = *(const f32x4*)(xs + (((long)zb * H + yy) * W + xx) * C + q * 4);
-        d[dx] = va + vb * sb;
-      }
-      vx[dy][0] = d[0] - d[2];
-      vx[dy][1] = d[1] + d[2];
-      vx[dy][2] = d[2] - d[1];
-      vx[dy][3] = d[1] - d[3];
-    }
+#define WINO_XFORM_DIMS 3
+#define WINO_XFORM_LIVE true
+#define WINO_XFORM_CH (q * 4)
+#include "wino_xform.inc"
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const f32x4 v = (b == 0) ? (vx[0][c] - vx[2][c]) : (b == 1) ? (vx[1][c] + vx[2][c])
-                      : (b == 2) ? (vx[2][c] - vx[1][c]) : (vx[1][c] - vx[3][c]);
+        const f32x4 v = WINO_XFORM_COL(vx, b, c);
         *(f32x4*)(V + ((long)(a * 16 + b * 4 + c) * T + tile) * C + q * 4) = v;
       }
   }
@@ -172,28 +155,15 @@ __global__ void __launch_bounds__(256) wino2d_input_kernel(const float* __restri
   const int y0 = 2 * by - 1, x0 = 2 * bx - 1;
   const float* xs = x + (long)n * H * W * C;
   for (int q = lane; q * 4 < C; q += 64) {
-    f32x4 vx[4][4];
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy) {
-      const int yy = y0 + dy;
-      f32x4 d[4];
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx) {
-        const int xx = x0 + dx;
-        d[dx] = ((unsigned)yy < (unsigned)H && (unsigned)xx < (unsigned)W) ? *(const f32x4*)(xs + ((long)yy * W + xx) * C + q * 4)
-                                                                         : (f32x4){0.f, 0.f, 0.f, 0.f};
-      }
-      vx[dy][0] = d[0] - d[2];
-      vx[dy][1] = d[1] + d[2];
-      vx[dy][2] = d[2] - d[1];
-      vx[dy][3] = d[1] - d[3];
-    }
+#define WINO_XFORM_DIMS 2
+#define WINO_XFORM_LIVE true
+#define WINO_XFORM_CH (q * 4)
+#include "wino_xform.inc"
 #pragma unroll
     for (int b = 0; b < 4; ++b)
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const f32x4 v = (b == 0) ? (vx[0][c] - vx[2][c]) : (b == 1) ? (vx[1][c] + vx[2][c])
-                      : (b == 2) ? (vx[2][c] - vx[1][c]) : (vx[1][c] - vx[3][c]);
+        const f32x4 v = WINO_XFORM_COL(vx, b, c);
         *(f32x4*)(V + ((long)(b * 4 + c) * T + tile) * C + q * 4) = v;
       }
   }

@@ -11,7 +11,7 @@ So per target the losses and camera gradients are bit-identical to RenderLoopEng
 kernels whose per-sample arithmetic does not depend on the batch.  Exceptions (tests/test_multi_target_engine_gpu.py names
 their tolerances): conv_mode 'f16x3' (batch-wide gradient scales) and every renderer with wide (>= 64-channel) layers, the
 released architecture included: lf_wino_fused_gemm picks its workgroup configuration (pick_fused_cfg) and its frequency
-split (fused_zsplit) from the batch's tile count N x tiles, so a row's summation order follows the batch size.
+split (wino_ring::Plan::split, csrc/wino_ring.h) from the batch's tile count N x tiles, so a row's summation order follows the batch size.
 
 Several objects (a scene's frame holds a few, each with its own latent volume): `z_obj` is then a sequence of T volumes, one
 per target.  Nothing below the resampler is per object -- camera blocks, projection, decoder, loss and optimiser work per row

@@ -402,22 +402,56 @@ def conv3d_c16_wino_projfwd(x, upack, bias, he, flags, proj_wA, proj_bias, proj_
 WIDE_CONV_MODE = 'fused'
 
 
-def pack_conv_wino_fused(weight, transpose=False):
-    """[Cout,Cin,3,3(,3)] -> U2 [64 | 16 f][CoutP][Cin] (output-channel major, CoutP = lf_wino_fused_cout_padded(Cout),
-    zero padded) for lf_wino_fused_gemm: U2[f][co][ci] = ((G x ..) w)[co][ci][f], evaluated in fp64."""
-    L = _lib.lib()
+def _wino_weights(weight, transpose=False):
+    """[Cout,Cin,3,3(,3)] -> the Winograd-domain weights U [64 | 16 f][Cout][Cin] = ((G x ..) w)[co][ci][f], evaluated in fp64;
+    transpose=True: those of the data gradient (channels swapped, taps flipped)."""
     w = weight.detach()
     if transpose:
         w = w.transpose(0, 1).flip(dims=tuple(range(2, w.dim())))
+    assert w.dim() in (4, 5) and tuple(w.shape[2:]) == (3,) * (w.dim() - 2)
     G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
-    cout, cin = w.shape[0], w.shape[1]
     if w.dim() == 5:
-        U = torch.einsum('ai,bj,ck,omijk->abcom', G, G, G, w.double()).reshape(64, cout, cin)
-    else:
-        U = torch.einsum('bj,ck,omjk->bcom', G, G, w.double()).reshape(16, cout, cin)
-    out = torch.zeros(U.shape[0], L.lf_wino_fused_cout_padded(cout), cin, device=w.device, dtype=torch.float32)
+        return torch.einsum('ai,bj,ck,omijk->abcom', G, G, G, w.double()).reshape(64, w.shape[0], w.shape[1])
+    return torch.einsum('bj,ck,omjk->bcom', G, G, w.double()).reshape(16, w.shape[0], w.shape[1])
+
+
+def pack_conv_wino_fused(weight, transpose=False):
+    """[Cout,Cin,3,3(,3)] -> U2 [64 | 16 f][CoutP][Cin] (output-channel major, CoutP = lf_wino_fused_cout_padded(Cout),
+    zero padded) for lf_wino_fused_gemm: U2[f][co][ci] = ((G x ..) w)[co][ci][f], evaluated in fp64."""
+    U = _wino_weights(weight, transpose)
+    F, cout, cin = U.shape
+    out = torch.zeros(F, _lib.lib().lf_wino_fused_cout_padded(cout), cin, device=U.device, dtype=torch.float32)
     out[:, :cout] = U.float()
     return out.contiguous()
+
+
+def _wino_conv_fused(x, cout, flags, depth_inner, v_shape, v_dtype, transform, scratch_bytes, gemm):
+    """The launch sequence of the fused wide convolutions, written once: V, input transform, y (or the depth-inner y), scratch,
+    GEMM, PixelNorm as a pass over the (small) output.  transform = (tag, f(V)) and gemm = (tag, f(V, y, scratch pointer or
+    None, scratch bytes, GEMM flags)) make their library call, each under _timed(tag); scratch_bytes() is the GEMM's query.
+    Returns (y, norm or None)."""
+    L = _lib.lib()
+    N, sp = x.shape[0], tuple(x.shape[2:])
+    V = torch.empty(v_shape, device=x.device, dtype=v_dtype)
+    with _timed(transform[0]):
+        transform[1](V)
+    if depth_inner:
+        assert len(sp) == 3
+        y = torch.empty((N, sp[1], sp[2], sp[0], cout), device=x.device, dtype=torch.float32)
+    else:
+        y = empty_cl((N, cout) + sp, x.device)
+    nscr = scratch_bytes()
+    scr = torch.empty(nscr // 4, device=x.device, dtype=torch.float32) if nscr else None
+    with _timed(gemm[0]):
+        gemm[1](V, y, _ptr(scr, True) if scr is not None else None, nscr,
+                (flags & LF_EPI_LRELU) | (_lib.LF_OUT_DEPTH_INNER if depth_inner else 0))
+    del V
+    norm = None
+    if flags & LF_EPI_PIXELNORM:
+        rows = N * math.prod(sp)
+        norm = torch.empty(rows, device=x.device, dtype=torch.float32)
+        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), rows, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+    return y, norm
 
 
 def conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner=False):
@@ -431,32 +465,18 @@ def conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner=False):
     D, H, W = (x.shape[2:] if dims == 3 else (1,) + tuple(x.shape[2:]))
     if dims == 3:
         T = L.lf_wino3d_tiles(N, D, H, W)
-        V = torch.empty(64, T, cin, device=x.device, dtype=torch.float32)
-        with _timed('wino3d_input'):
-            check(L.lf_wino3d_input_transform(_ptr(x), _ptr(V), N, D, H, W, cin, _stream()), 'lf_wino3d_input_transform')
+        transform = ('wino3d_input', lambda V: check(L.lf_wino3d_input_transform(_ptr(x), _ptr(V), N, D, H, W, cin, _stream()),
+                                                     'lf_wino3d_input_transform'))
     else:
         T = L.lf_wino2d_tiles(N, H, W)
-        V = torch.empty(16, T, cin, device=x.device, dtype=torch.float32)
-        with _timed('wino2d_input'):
-            check(L.lf_wino2d_input_transform(_ptr(x), _ptr(V), N, H, W, cin, _stream()), 'lf_wino2d_input_transform')
-    if depth_inner:
-        assert dims == 3
-        y = torch.empty((N, H, W, D, cout), device=x.device, dtype=torch.float32)
-    else:
-        y = empty_cl((N, cout) + tuple(x.shape[2:]), x.device)
-    nscr = L.lf_wino_fused_scratch_bytes(dims, N, D, H, W, cout)
-    scr = torch.empty(nscr // 4, device=x.device, dtype=torch.float32) if nscr else None
-    with _timed(f'wino{dims}d_fused'):
-        check(L.lf_wino_fused_gemm(_ptr(V), _ptr(U2), _ptr(bias) if bias is not None else None, _ptr(y),
-                                   _ptr(scr, True) if scr is not None else None, nscr, dims, N, D, H, W, cin,
-                                   cout, he, (flags & LF_EPI_LRELU) | (_lib.LF_OUT_DEPTH_INNER if depth_inner else 0), SLOPE, _stream()),
-              'lf_wino_fused_gemm')
-    del V
-    norm = None
-    if flags & LF_EPI_PIXELNORM:
-        norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32)
-        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * D * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
-    return y, norm
+        transform = ('wino2d_input', lambda V: check(L.lf_wino2d_input_transform(_ptr(x), _ptr(V), N, H, W, cin, _stream()),
+                                                     'lf_wino2d_input_transform'))
+
+    def gemm(V, y, scr, nscr, gflags):
+        check(L.lf_wino_fused_gemm(_ptr(V), _ptr(U2), _ptr(bias) if bias is not None else None, _ptr(y), scr, nscr, dims, N, D, H,
+                                   W, cin, cout, he, gflags, SLOPE, _stream()), 'lf_wino_fused_gemm')
+    return _wino_conv_fused(x, cout, flags, depth_inner, (16 if dims == 2 else 64, T, cin), torch.float32, transform,
+                            lambda: L.lf_wino_fused_scratch_bytes(dims, N, D, H, W, cout), (f'wino{dims}d_fused', gemm))
 
 
 def wide_conv(x, weight, bias, he, flags, transpose=False, depth_inner=False):
@@ -475,22 +495,13 @@ def pack_conv_wino_fused_f16x3(weight, transpose=False):
     U2s [F][CoutP][CinP/32][2][32] f16 (F = 64 frequencies in 3-D, 16 in 2-D), the Winograd weights of pack_conv_wino_fused
     (fp64) times 2^eU, split into hi = f16(u) and lo = f16(u - hi) per 32-channel record (CoutP = lf_wino_fused_cout_padded(Cout),
     CinP = lf_wino_f16x3_cin_padded(Cin), zero padded); eU puts max|U| 2^eU in [2^11, 2^12)."""
-    w = weight.detach()
-    if transpose:
-        w = w.transpose(0, 1).flip(dims=tuple(range(2, w.dim())))
-    assert w.dim() in (4, 5) and tuple(w.shape[2:]) == (3,) * (w.dim() - 2)
-    G = torch.tensor(_WINO_G, dtype=torch.float64, device=w.device)
-    cout, cin = w.shape[0], w.shape[1]
-    if w.dim() == 5:
-        U = torch.einsum('ai,bj,ck,omijk->abcom', G, G, G, w.double()).reshape(64, cout, cin)
-    else:
-        U = torch.einsum('bj,ck,omjk->bcom', G, G, w.double()).reshape(16, cout, cin)
-    F = U.shape[0]
+    U = _wino_weights(weight, transpose)
+    F, cout, cin = U.shape
     amax = U.abs().max().item()
     eU = 12 - math.frexp(amax)[1] if amax > 0 else 0
     coutp, cinp = (cout + 63) // 64 * 64, (cin + 31) // 32 * 32          # lf_wino_fused_cout_padded / lf_wino_f16x3_cin_padded
-    Us = torch.zeros(F, coutp, cinp, dtype=torch.float64, device=w.device)
-    Us[:, :cout, :cin] = torch.ldexp(U, torch.tensor(float(eU), dtype=torch.float64, device=w.device))
+    Us = torch.zeros(F, coutp, cinp, dtype=torch.float64, device=U.device)
+    Us[:, :cout, :cin] = torch.ldexp(U, torch.tensor(float(eU), dtype=torch.float64, device=U.device))
     hi = Us.half()
     lo = (Us - hi.double()).half()
     out = torch.stack((hi.reshape(F, coutp, cinp // 32, 32), lo.reshape(F, coutp, cinp // 32, 32)), dim=3)
@@ -516,28 +527,18 @@ def wide_conv_f16x3(x, weight, bias, he, flags, transpose=False, depth_inner=Fal
     if amax_in is None:
         amax_in = amax_buffer(x.detach().abs().amax(), x.device)
     T = L.lf_wino3d_tiles(N, D, H, W)
-    V = torch.empty(64, T, L.lf_wino_f16x3_cin_padded(cin) * 2, device=x.device, dtype=torch.float16)
-    with _timed('wino3d_input_f16x3'):
+
+    def transform(V):
         check(L.lf_wino3d_input_transform_f16x3(_ptr(x), _ptr(amax_in), _ptr(V), N, D, H, W, cin, _stream()),
               'lf_wino3d_input_transform_f16x3')
-    if depth_inner:
-        y = torch.empty((N, H, W, D, cout), device=x.device, dtype=torch.float32)
-    else:
-        y = empty_cl((N, cout, D, H, W), x.device)
-    nscr = L.lf_wino_fused_f16x3_scratch_bytes(N, D, H, W, cout)
-    scr = torch.empty(nscr // 4, device=x.device, dtype=torch.float32) if nscr else None
-    with _timed('wino3d_fused_f16x3'):
+
+    def gemm(V, y, scr, nscr, gflags):
         check(L.lf_wino_fused_f16x3_gemm(_ptr(V), _ptr(U2), eU, _ptr(amax_in), _ptr(bias) if bias is not None else None, _ptr(y),
-                                         _ptr(amax_out) if amax_out is not None else None,
-                                         _ptr(scr, True) if scr is not None else None, nscr, N, D, H, W, cin, cout, he,
-                                         (flags & LF_EPI_LRELU) | (_lib.LF_OUT_DEPTH_INNER if depth_inner else 0), SLOPE,
-                                         _stream()), 'lf_wino_fused_f16x3_gemm')
-    del V
-    norm = None
-    if flags & LF_EPI_PIXELNORM:
-        norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32)
-        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * D * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
-    return y, norm
+                                         _ptr(amax_out) if amax_out is not None else None, scr, nscr, N, D, H, W, cin, cout, he,
+                                         gflags, SLOPE, _stream()), 'lf_wino_fused_f16x3_gemm')
+    return _wino_conv_fused(x, cout, flags, depth_inner, (64, T, L.lf_wino_f16x3_cin_padded(cin) * 2), torch.float16,
+                            ('wino3d_input_f16x3', transform), lambda: L.lf_wino_fused_f16x3_scratch_bytes(N, D, H, W, cout),
+                            ('wino3d_fused_f16x3', gemm))
 
 
 def _wide_conv2d_f16x3(x, weight, bias, he, flags, transpose=False):
@@ -546,23 +547,17 @@ def _wide_conv2d_f16x3(x, weight, bias, he, flags, transpose=False):
     U2, eU = _pk(weight, 'wxb' if transpose else 'wxf', lambda w: pack_conv_wino_fused_f16x3(w, transpose=transpose))
     N, cin, H, W = x.shape
     T = L.lf_wino2d_tiles(N, H, W)
-    V = torch.empty(16, T, L.lf_wino_f16x3_cin_padded(cin) * 2, device=x.device, dtype=torch.float16)
     eV = torch.empty(T, device=x.device, dtype=torch.int32)
-    with _timed('wino2d_input_f16x3'):
+
+    def transform(V):
         check(L.lf_wino2d_input_transform_f16x3(_ptr(x), _ptr(V), _ptr(eV), N, H, W, cin, _stream()), 'lf_wino2d_input_transform_f16x3')
-    y = empty_cl((N, cout, H, W), x.device)
-    nscr = L.lf_wino_fused2d_f16x3_scratch_bytes(N, H, W, cout)
-    scr = torch.empty(nscr // 4, device=x.device, dtype=torch.float32) if nscr else None
-    with _timed('wino2d_fused_f16x3'):
-        check(L.lf_wino_fused2d_f16x3_gemm(_ptr(V), _ptr(eV), _ptr(U2), eU, _ptr(bias) if bias is not None else None, _ptr(y),
-                                           _ptr(scr, True) if scr is not None else None, nscr, N, H, W, cin, cout, he,
-                                           flags & LF_EPI_LRELU, SLOPE, _stream()), 'lf_wino_fused2d_f16x3_gemm')
-    del V
-    norm = None
-    if flags & LF_EPI_PIXELNORM:
-        norm = torch.empty(N * H * W, device=x.device, dtype=torch.float32)
-        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
-    return y, norm
+
+    def gemm(V, y, scr, nscr, gflags):
+        check(L.lf_wino_fused2d_f16x3_gemm(_ptr(V), _ptr(eV), _ptr(U2), eU, _ptr(bias) if bias is not None else None, _ptr(y), scr,
+                                           nscr, N, H, W, cin, cout, he, gflags, SLOPE, _stream()), 'lf_wino_fused2d_f16x3_gemm')
+    return _wino_conv_fused(x, cout, flags, False, (16, T, L.lf_wino_f16x3_cin_padded(cin) * 2), torch.float16,
+                            ('wino2d_input_f16x3', transform), lambda: L.lf_wino_fused2d_f16x3_scratch_bytes(N, H, W, cout),
+                            ('wino2d_fused_f16x3', gemm))
 
 
 # Scope of the split-precision 2-D decoder (RenderLoopEngine conv_mode='f16x3'): inside `with ops.wide2d_f16x3():` the wide 2-D

@@ -766,7 +766,8 @@ def test_diag_gmm_is_sklearns_algorithm():
 
 
 def test_wino_fused_xcd_order_is_a_permutation():
-    """csrc/wino_fused.hip re-numbers its workgroups so that the output-channel blocks of one tile block run side by side on one
+    """csrc/wino_ring.inc (the one copy of the skeleton that wino_fused.hip and wino_fused_f16x3.hip include) re-numbers its
+    workgroups so that the output-channel blocks of one tile block run side by side on one
     XCD (dispatch L lands on XCD L mod 8): the same arithmetic here must visit every (tile block, channel block) exactly once, keep
     a tile block's channel blocks on ONE XCD and put them next to each other in that XCD's dispatch order."""
     for gx, gy in ((8, 2), (512, 2), (64, 4), (24, 3), (16, 16)):

@@ -9,7 +9,7 @@ checked at the single-target tests' tolerances:
     test_engine_hypothesis_groups_on_streams_are_bit_identical (atol 1e-6 max|g|, rtol 2e-5);
   * the released-width renderer (golden g20) with gradients, like every renderer with wide (>= 64-channel) layers: its
     wide 3-D blocks and wide 2-D decoder layers run on lf_wino_fused_gemm, which picks its workgroup configuration
-    (pick_fused_cfg, wino_fused.hip) and its frequency split (fused_zsplit) from T = N x tiles, so a row's summation order
+    (pick_fused_cfg, wino_fused.hip) and its frequency split (wino_ring::Plan::split) from T = N x tiles, so a row's summation order
     changes with the batch size and the forward already differs in the last bits -- losses at close(), gradients at
     atol 2e-3 max|g|, rtol 2e-5 (one evaluation; measured 1.1e-4 absolute on a largest component of 0.19).  Over a loop
     Adam amplifies such differences: estimate_batch does not reproduce estimate on these renderers."""

@@ -4,7 +4,10 @@ Compiles resample.hip of a parent revision (git archive) and of the working tree
 library's flags, disassembles both, and diffs every kernel symbol the parent's code object holds, instruction by
 instruction (addresses dropped, encodings kept).  Kernels that only the working tree has are listed, not compared.
 
-    python tools/resample_isa_diff.py [--rev HEAD] [--out profiles/resample_indexed_isa.txt]
+    python tools/resample_isa_diff.py [--rev HEAD] [--out profiles/resample_indexed_isa.txt] [--src FILE.hip ...]
+
+--src names other files of csrc/ (each with its per-file flags of csrc/build.py), e.g. the wide Winograd family
+(profiles/wide_wino_shared_isa.txt: --src wino_fused.hip wino_fused_f16x3.hip wino_gemm.hip).
 
 The kernels that exist as a plain and an indexed form are written once (csrc/resample_gather.inc, included twice by
 resample.hip) and keep their names, so a change to that file is checked here like any other: every symbol of both forms
@@ -24,7 +27,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from latentfusion_amd.csrc import build as hip_build  # noqa: E402
 
-SRC = os.path.join('latentfusion_amd', 'csrc', 'resample.hip')
+CSRC = os.path.join('latentfusion_amd', 'csrc')
 
 
 def _objdump():
@@ -36,11 +39,11 @@ def _objdump():
     return 'llvm-objdump'
 
 
-def disassemble(tree, workdir, tag):
-    """{symbol: [instruction lines]} of resample.hip's gfx950 code object in `tree`."""
-    co = os.path.join(workdir, tag + '.co')
-    cmd = [hip_build._hipcc(), '-x', 'hip', '--cuda-device-only', '--no-gpu-bundle-output', '-c', os.path.join(tree, SRC), '-o', co]
-    cmd += [f for f in hip_build.FLAGS if f != '-fPIC'] + hip_build.EXTRA.get('resample.hip', [])
+def disassemble(tree, workdir, tag, src='resample.hip'):
+    """{symbol: [instruction lines]} of the gfx950 code object of csrc/`src` in `tree`."""
+    co = os.path.join(workdir, tag + '.' + src + '.co')
+    cmd = [hip_build._hipcc(), '-x', 'hip', '--cuda-device-only', '--no-gpu-bundle-output', '-c', os.path.join(tree, CSRC, src), '-o', co]
+    cmd += [f for f in hip_build.FLAGS if f != '-fPIC'] + hip_build.EXTRA.get(src, [])
     subprocess.run(cmd, check=True)
     text = subprocess.run([_objdump(), '-d', '--no-leading-addr', co], check=True, stdout=subprocess.PIPE).stdout.decode()
     syms, cur = {}, None
@@ -58,27 +61,30 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--rev', default='HEAD')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'resample_indexed_isa.txt'))
+    ap.add_argument('--src', nargs='+', default=['resample.hip'], help='files of csrc/ to compare')
     a = ap.parse_args()
     rev = subprocess.run(['git', '-C', ROOT, 'rev-parse', '--short', a.rev], check=True, stdout=subprocess.PIPE).stdout.decode().strip()
+    lines, diff, nsym = [], [], 0
     with tempfile.TemporaryDirectory() as tmp:
         parent = os.path.join(tmp, 'parent')
         os.makedirs(parent)
         ar = subprocess.run(['git', '-C', ROOT, 'archive', a.rev, 'latentfusion_amd/csrc', 'include'], check=True, stdout=subprocess.PIPE)
         subprocess.run(['tar', '-x', '-C', parent], input=ar.stdout, check=True)
-        old = disassemble(parent, tmp, 'parent')
-        new = disassemble(ROOT, tmp, 'tree')
-    lines = [f'# {SRC}: kernel symbols of revision {rev} against the working tree, gfx950, flags {" ".join(hip_build.FLAGS)}',
-             '# symbol: instructions (parent / tree)']
-    diff = []
-    for name in sorted(old):
-        lines.append(f'#   {name}: {len(old[name])} / {len(new.get(name, []))}')
-        diff += list(difflib.unified_diff(old[name], new.get(name, []), 'parent:' + name, 'tree:' + name, lineterm='', n=2))
-    lines.append('# symbols only in the tree (not compared):')
-    lines += [f'#   {name}: {len(new[name])}' for name in sorted(new) if name not in old]
-    lines.append(f'# diff over the {len(old)} parent symbols ({len(diff)} lines):')
+        for src in a.src:
+            old = disassemble(parent, tmp, 'parent', src)
+            new = disassemble(ROOT, tmp, 'tree', src)
+            lines += [f'# {os.path.join(CSRC, src)}: kernel symbols of revision {rev} against the working tree, gfx950, flags '
+                      f'{" ".join(hip_build.FLAGS + hip_build.EXTRA.get(src, []))}', '# symbol: instructions (parent / tree)']
+            for name in sorted(old):
+                lines.append(f'#   {name}: {len(old[name])} / {len(new.get(name, []))}')
+                diff += list(difflib.unified_diff(old[name], new.get(name, []), 'parent:' + name, 'tree:' + name, lineterm='', n=2))
+            lines.append('# symbols only in the tree (not compared):')
+            lines += [f'#   {name}: {len(new[name])}' for name in sorted(new) if name not in old]
+            nsym += len(old)
+    lines.append(f'# diff over the {nsym} parent symbols ({len(diff)} lines):')
     with open(a.out, 'w') as f:
         f.write('\n'.join(lines + diff) + '\n')
-    print(f'{len(old)} symbols compared, {len(diff)} diff lines -> {a.out}')
+    print(f'{nsym} symbols compared, {len(diff)} diff lines -> {a.out}')
     return 1 if diff else 0
 
 
