@@ -8,8 +8,12 @@
 // transposed weight blocks (towards x and towards h).  The one-output ring kernel spends most of a tile's time outside its
 // MFMAs (halo fetch, bf16 commit, barrier, epilogue: profiles/r05_ring_bf16_ablation.txt) -- here ONE staged halo serves NG
 // output groups: a workgroup is NG x 4 waves, group g owns weight pack g, its own accumulators and its own epilogue, the
-// halo pieces are fetched and committed by all NG x 4 waves together (6 / NG pieces each), the ring of six z-plane slots,
-// the operand order and the MFMA order per accumulator are those of conv3d_c16_f16x3_kernel<*, 1> (same sums bit for bit).
+// halo pieces are fetched and committed by all NG x 4 waves together (6 / NG pieces each: an NPW-piece table, idle lanes write
+// to DUMP_OFF, where conv_split.hip has five row pieces and one predicated edge piece).  The tile walk -- LDS clear, XCD-aware
+// tile range, plane fetch, priming, stepping to the next tile, per-column addressing, operand bases, the ring's turn, the last
+// tile's epilogue -- is conv3d_c16_f16x3_kernel's, written once in ring_walk.inc; the operand order and the MFMA order per
+// accumulator are those of conv3d_c16_f16x3_kernel<*, 1> (same sums bit for bit), the host side of a launch is ring_tile.h's
+// RingPlan.  This file adds the groups, RmArgs, the staging table, the product step on one bf16 piece and the EX epilogues.
 // On top, the element-wise stages of the recurrence ride in the epilogue of the convolution that owns the same voxels (EX):
 //     EX_RH    group 1 of (h -> upre, rpre): also r h = h s(rpre)                            (was lf_gru_train_stage_a)
 //     EX_BLEND (r h -> cand): also h' = h (1 - s(upre)) + cand s(upre)                       (was lf_gru_train_stage_b)
@@ -68,7 +72,7 @@ __global__ void __launch_bounds__(256 * NG, 2) ring_multi_kernel(const RmArgs A)
   constexpr int NPW = NPIECE / NG;                        // halo pieces per wave and incoming plane pair
   constexpr int NT = 256 * NG;
   static_assert(NPIECE % NG == 0, "pieces divide over the groups");
-  constexpr int OOB = (int)0x80000000;
+  constexpr int LDS_B = LDSg;
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -76,18 +80,10 @@ __global__ void __launch_bounds__(256 * NG, 2) ring_multi_kernel(const RmArgs A)
   const int pz = w4 & 1, ry = w4 >> 1;                    // this wave's output plane and row quad
   const int n = lane & 15, kg = lane >> 4;
   const int D = A.D, H = A.H, W = A.W;
-  for (int i = tid; i < LDSg / 16; i += NT) ((u32x4s*)smem)[i] = (u32x4s){0u, 0u, 0u, 0u};
-  __syncthreads();
+  const int &tiles_x = A.tiles_x, &tiles_y = A.tiles_y, &tiles_z = A.tiles_z, &ntiles = A.ntiles;   // (the walk's names for them)
+#define RING_WALK_SETUP
+#include "ring_walk.inc"
 
-  const int nb = gridDim.x;
-  const int lb = (nb % 8 == 0) ? (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8 : blockIdx.x;   // consecutive ranges per XCD
-  const int per = (A.ntiles + nb - 1) / nb;
-  const int t_begin = lb * per;
-  const int t_end = min(t_begin + per, A.ntiles);
-  if (t_begin >= t_end) return;
-
-  const long nvox = (long)D * H * W;
-  const unsigned sample_bytes = (unsigned)(nvox * 64);
   const float he = A.he;
   const RmGroup G = (NG > 1 && grp == 1) ? A.g[1] : A.g[0];
   const unsigned gfl = FL >= 0 ? (unsigned)FL : __builtin_amdgcn_readfirstlane(G.flags);
@@ -131,20 +127,8 @@ __global__ void __launch_bounds__(256 * NG, 2) ring_multi_kernel(const RmArgs A)
     f_x = (const unsigned char*)A.x + ((long)bn * nvox << IN_SH);
   };
   u32x4s stg[NPW];
-  auto fetch_plane = [&](int z, bool on) {
-    const bool v = on && (unsigned)z < (unsigned)D;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)f_x, 0, v ? in_sample_bytes : 0u, 0x00020000);
-    const int soff = v ? z * in_plane_bytes : 0;
-#pragma unroll
-    for (int k = 0; k < NPW; ++k) {
-      if constexpr (IN16) {
-        const u32x2s h = __builtin_amdgcn_raw_buffer_load_b64(rs, foff[k], soff, 0);
-        stg[k] = (u32x4s){h[0], h[1], 0u, 0u};
-      } else {
-        stg[k] = __builtin_amdgcn_raw_buffer_load_b128(rs, foff[k], soff, 0);
-      }
-    }
-  };
+#define RING_WALK_HALO
+#include "ring_walk.inc"
   auto commit_piece = [&](int slot, auto kc) {
     constexpr int k = decltype(kc)::v;
     bf16x4s h;
@@ -155,20 +139,8 @@ __global__ void __launch_bounds__(256 * NG, 2) ring_multi_kernel(const RmArgs A)
   };
   auto commit_plane = [&](int slot) { static_for<0, NPW>([&](auto kc) { commit_piece(slot, kc); }); };
 
-  int cx, cy, cz, cn;
-  {
-    int tt = t_begin;                                     // z fastest: a workgroup walks up columns of tiles
-    cz = tt % A.tiles_z; tt /= A.tiles_z;
-    cx = tt % A.tiles_x; tt /= A.tiles_x;
-    cy = tt % A.tiles_y; cn = tt / A.tiles_y;
-  }
-  int rot = 0;
-  fetch_column(cx, cy, cn);
-  fetch_plane(cz * TZs - 1 + pz, true);
-  commit_plane(pz);
-  fetch_plane(cz * TZs + 1 + pz, true);
-  commit_plane(2 + pz);
-  lds_barrier_s();
+#define RING_WALK_PRIME
+#include "ring_walk.inc"
 
   const int lane_b = (4 * ry * HXs + n) * 32 + (kg & 1) * 16;
 
@@ -299,32 +271,20 @@ __global__ void __launch_bounds__(256 * NG, 2) ring_multi_kernel(const RmArgs A)
     }
   };
 
-  f32x4 accP[RYs];
-#pragma unroll
-  for (int r = 0; r < RYs; ++r) accP[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  int px_ = cx, py_ = cy, pz_ = cz, pn_ = cn;
 #ifndef RM_E0
 #define RM_E0 1
 #endif
   constexpr int E0 = RM_E0, PF = 2;                     // (RM_E0 >= 32: the finished tile's epilogue BEHIND the MFMA phase, A/B)
+#define RING_WALK_HEAD
+#include "ring_walk.inc"
   for (int t = t_begin; t < t_end; ++t) {
-    int nx = cx, ny = cy, nz = cz + 1, nn = cn;
-    if (nz == A.tiles_z) { nz = 0; ++nx; }
-    if (nx == A.tiles_x) { nx = 0; ++ny; }
-    if (ny == A.tiles_y) { ny = 0; ++nn; }
-    const bool on = t + 1 < t_end;
-    const bool slide = on && nz != 0;
-    if (t == t_begin + 1 || (t > t_begin && pz_ == 0)) epi_column(px_, py_, pn_);
-    if (on && nz == 0) fetch_column(nx, ny, nn);
-    Epi E;
-    epi_tile(E, pz_, t > t_begin);
+#define RING_WALK_NEXT
+#include "ring_walk.inc"
     fetch_plane(nz * TZs - 1 + (slide ? 2 : 0) + pz, on);
     __builtin_amdgcn_sched_barrier(0);
 
-    const int s0 = mod6(rot + pz), s1 = mod6(s0 + 1), s2 = mod6(s1 + 1);
-    const int aP = ((kg >> 1) ? s1 : s0) * PLANE_B + lane_b;
-    const int aQ = s2 * PLANE_B + lane_b + (kg >> 1) * 32;
-    const int aR = s2 * PLANE_B + lane_b + 2 * 32 + (kg >> 1) * (HXs * 32);
+#define RING_WALK_OPERANDS
+#include "ring_walk.inc"
     const int cslot = mod6(rot + 4 + pz);
 
     f32x4 acc[RYs];
@@ -346,8 +306,7 @@ __global__ void __launch_bounds__(256 * NG, 2) ring_multi_kernel(const RmArgs A)
           const bf16x8s vh = bh[j % (PF + 1)];
           static_for<0, 3>([&](auto uc) {
             constexpr int u = decltype(uc)::v;
-            constexpr int r = cls < 2 ? h - u : (u == 0 ? h : (u == 1 ? h - 2 : -1));
-            constexpr int p = cls == 0 ? kx * 3 + u : (cls == 1 ? 9 + u : 12 + u);
+            constexpr int r = op_row(cls, h, u), p = op_pair(cls, kx, u);
             if constexpr (r >= 0 && r < RYs) acc[r] = mfma_k32(wreg[p], vh, acc[r]);
           });
         }
@@ -356,28 +315,14 @@ __global__ void __launch_bounds__(256 * NG, 2) ring_multi_kernel(const RmArgs A)
       });
     }
     if constexpr (E0 >= NOP + PF)
-      static_for<0, 2 * RYs>([&](auto ic) { epi_part(E, accP, IC<decltype(ic)::v / 2>{}, IC<decltype(ic)::v % 2>{}); });
+      ring_epilogue(epi_part, E, accP);
     commit_plane(cslot);
     lds_barrier_s();
-    if (on && !slide) {
-      rot = mod6(rot + 4);
-      fetch_plane(nz * TZs + 1 + pz, true);
-      commit_plane(mod6(rot + 2 + pz));
-      lds_barrier_s();
-    } else {
-      rot = mod6(rot + 2);
-    }
-#pragma unroll
-    for (int r = 0; r < RYs; ++r) accP[r] = acc[r];
-    px_ = cx; py_ = cy; pz_ = cz; pn_ = cn;
-    cx = nx; cy = ny; cz = nz; cn = nn;
+#define RING_WALK_TURN
+#include "ring_walk.inc"
   }
-  {
-    if (t_end - t_begin == 1 || pz_ == 0) epi_column(px_, py_, pn_);
-    Epi E;
-    epi_tile(E, pz_, true);
-    static_for<0, 2 * RYs>([&](auto ic) { epi_part(E, accP, IC<decltype(ic)::v / 2>{}, IC<decltype(ic)::v % 2>{}); });
-  }
+#define RING_WALK_LAST
+#include "ring_walk.inc"
   if constexpr (EX == 5) {
     // per-workgroup partial of the producer's bias gradient: lanes of one channel quad (kg) over the 16 voxels n, then the
     // four waves through LDS in wave order; partial[blockIdx][16] behind the 16 output floats of A.o2
@@ -432,8 +377,8 @@ static int ring_multi_launch(const void* x, int x_bf16, const void* wpack, int n
                              int extra, const void* e0, const void* e1, void* o2, void* o3,
                              int N, int D, int H, int W, float he, int addend_per_sample, void* stream) {
   lf_clear_error();
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || ngroups < 1 || ngroups > 2 || extra < 0 || extra > 5) return LF_EINVAL;
-  if ((long)D * H * W * 64 >= 0x7fffffffL) return LF_EINVAL;
+  RingPlan P;
+  if (!P.shape(N, D, H, W) || ngroups < 1 || ngroups > 2 || extra < 0 || extra > 5) return LF_EINVAL;
   if (x == nullptr || wpack == nullptr || y0 == nullptr || (ngroups == 2 && y1 == nullptr)) return LF_EINVAL;
   const unsigned known = LF_RING_ADD_BF16 | LF_RING_OUT_BF16 | LF_RING_ROUND;
   if ((flags0 & ~known) || (flags1 & ~known)) return LF_EINVAL;
@@ -485,21 +430,12 @@ static int ring_multi_launch(const void* x, int x_bf16, const void* wpack, int n
   A.g[1] = RmGroup{y1, add1, flags1};
   A.e0 = e0; A.e1 = e1; A.o2 = o2; A.o3 = o3;
   A.N = N; A.D = D; A.H = H; A.W = W;
-  A.tiles_x = (W + TXs - 1) / TXs; A.tiles_y = (H + TYs - 1) / TYs; A.tiles_z = (D + TZs - 1) / TZs;
-  const long pt = (long)A.tiles_x * A.tiles_y * A.tiles_z * N;
-  if (pt > 0x7fffffffL) return LF_EINVAL;
-  A.ntiles = (int)pt;
+  unsigned grid;
+  if (!P.grid(ngroups == 1 ? 2 : 1, grid)) return LF_EINVAL;      // 8 waves per CU either way
+  A.tiles_x = P.tiles_x; A.tiles_y = P.tiles_y; A.tiles_z = P.tiles_z; A.ntiles = P.ntiles;
   A.he = he;
   A.add_per_sample = addend_per_sample ? 1 : 0;
   A.slope = 0.2f;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  const long want = (long)(ngroups == 1 ? 2 : 1) * cus;           // 8 waves per CU either way
-  const unsigned grid = (unsigned)(pt < want ? pt : want);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * ngroups), (size_t)LDSg, (hipStream_t)stream, A);
   if (extra == LF_RING_EX_PREV) {
     const int st = lf_launch_status();

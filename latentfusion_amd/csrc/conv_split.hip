@@ -112,26 +112,13 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
   constexpr int IN_SH = IN16 ? 5 : 6;                     // log2 bytes per input voxel record
   const h1* wsplit = (const h1*)wsplit_v;
 
+  constexpr int NT = 256;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int pz = wv & 1, ry = wv >> 1;                    // this wave's output plane and row quad; also its fetch share
   const int n = lane & 15, kg = lane >> 4;
-  // zero-weight K slots and the rows an operand reads past its wave's share meet whatever is in LDS: 0 * garbage
-  // could be NaN, so everything starts as zeros (the planes hold finite f16 values from then on)
-  for (int i = tid; i < LDS_B / 16; i += 256) ((u32x4s*)smem)[i] = (u32x4s){0u, 0u, 0u, 0u};
-  __syncthreads();
-
-  // workgroups b, b+8, b+16, ... run on the same XCD (one L2 each): give them consecutive tile ranges so that the
-  // halo columns shared by neighbouring ranges are fetched from HBM once
-  const int nb = gridDim.x;
-  const int lb = (nb % 8 == 0) ? (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8 : blockIdx.x;
-  const int per = (ntiles + nb - 1) / nb;
-  const int t_begin = lb * per;
-  const int t_end = min(t_begin + per, ntiles);
-  if (t_begin >= t_end) return;
-
-  const long nvox = (long)D * H * W;
-  const unsigned sample_bytes = (unsigned)(nvox * 64);
+#define RING_WALK_SETUP
+#include "ring_walk.inc"
 
   // power-of-two input scale from the tensor's max-abs (gradient launches); 1 otherwise
   float in_scale = 1.f;
@@ -169,7 +156,6 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
   // inside one z plane of the sample (0x80000000 where the halo leaves the volume in x or y: the buffer load then
   // returns zeros), recomputed when the walk enters a new column; the plane itself is the instruction's SCALAR offset,
   // and a plane outside [0, D) -- wave-uniform, every wave fetches one plane -- gets a zero-sized descriptor. ----
-  constexpr int OOB = (int)0x80000000;
   const int frow0 = 5 * ry;
   const int erow = frow0 + (lane >> 3), ecol = 16 + ((lane >> 2) & 1);
   const int eldso = (erow * HXs + ecol) * 32 + (lane & 3) * 8;
@@ -178,7 +164,8 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
   const int in_plane_bytes = (H * W) << IN_SH;
   const unsigned in_sample_bytes = (unsigned)(nvox << IN_SH);
 
-  int foff[NPIECE];
+  constexpr int NPW = NPIECE;                             // (one group: every wave stages all six pieces of its plane)
+  int foff[NPW];
   const float* f_x = x;
   auto fetch_column = [&](int bx, int by, int bn) {
     const int ox = bx * TXs - 1, oy = by * TYs - 1;
@@ -192,21 +179,9 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
     foff[5] = (e_ok && (unsigned)c2 < (unsigned)W && (unsigned)row < (unsigned)H) ? ((row * W + c2) << IN_SH) + ((lane & 3) << (IN_SH - 2)) : OOB;
     f_x = x + (long)bn * nvox * (IN16 ? 8 : 16);          // (x is declared float*: a bf16 record is 8 floats' worth of bytes)
   };
-  u32x4s stg[NPIECE];
-  auto fetch_plane = [&](int z, bool on) {
-    const bool v = on && (unsigned)z < (unsigned)D;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)f_x, 0, v ? in_sample_bytes : 0u, 0x00020000);
-    const int soff = v ? z * in_plane_bytes : 0;
-#pragma unroll
-    for (int it = 0; it < NPIECE; ++it) {
-      if constexpr (IN16) {
-        const u32x2s h = __builtin_amdgcn_raw_buffer_load_b64(rs, foff[it], soff, 0);
-        stg[it] = (u32x4s){h[0], h[1], 0u, 0u};
-      } else {
-        stg[it] = __builtin_amdgcn_raw_buffer_load_b128(rs, foff[it], soff, 0);
-      }
-    }
-  };
+  u32x4s stg[NPW];
+#define RING_WALK_HALO
+#include "ring_walk.inc"
   // fp32 -> f16 hi / lo of staged piece `it`, into the plane slot at dst
   auto commit_piece = [&](unsigned char* dst, auto itc) {
     constexpr int it = decltype(itc)::v;
@@ -233,22 +208,8 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
     static_for<0, NPIECE>([&](auto itc) { commit_piece(dst, itc); });
   };
 
-  // tile coordinates are stepped, not divided: (cx, cy, cz, cn) = tile t, (nx, ny, nz, nn) = tile t + 1
-  int cx, cy, cz, cn;
-  {
-    int tt = t_begin;                                            // z fastest: a workgroup walks up columns of tiles
-    cz = tt % tiles_z; tt /= tiles_z;
-    cx = tt % tiles_x; tt /= tiles_x;
-    cy = tt % tiles_y; cn = tt / tiles_y;
-  }
-  // ring state: halo plane hp (0..3) of the current tile sits in slot (rot + hp) % 6
-  int rot = 0;
-  fetch_column(cx, cy, cn);
-  fetch_plane(cz * TZs - 1 + pz, true);
-  commit_plane(pz);
-  fetch_plane(cz * TZs + 1 + pz, true);
-  commit_plane(2 + pz);
-  lds_barrier_s();
+#define RING_WALK_PRIME
+#include "ring_walk.inc"
 
   f32x4 bv4 = (f32x4){0.f, 0.f, 0.f, 0.f};
   if (!GRAD && bias != nullptr) bv4 = *(const f32x4*)(bias + kg * 4);
@@ -363,34 +324,20 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
 #else
 #define TS(k) do {} while (0)
 #endif
-  f32x4 accP[RYs];                                                // the previous tile's sums, finished under this tile's MFMAs
-#pragma unroll
-  for (int r = 0; r < RYs; ++r) accP[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
-  int px_ = cx, py_ = cy, pz_ = cz, pn_ = cn;
+#define RING_WALK_HEAD
+#include "ring_walk.inc"
   for (int t = t_begin; t < t_end; ++t) {
     TS(0);
-    int nx = cx, ny = cy, nz = cz + 1, nn = cn;
-    if (nz == tiles_z) { nz = 0; ++nx; }
-    if (nx == tiles_x) { nx = 0; ++ny; }
-    if (ny == tiles_y) { ny = 0; ++nn; }
-    const bool on = t + 1 < t_end;
-    const bool slide = on && nz != 0;
-    // per-column addressing, recomputed when the previous tile (epilogue) / the next tile (halo) starts a column
-    if (t == t_begin + 1 || (t > t_begin && pz_ == 0)) epi_column(px_, py_, pn_);
-    if (on && nz == 0) fetch_column(nx, ny, nn);
-    Epi E;
-    epi_tile(E, pz_, t > t_begin);                     // (gradient form: the previous layer's activations, requested first)
+#define RING_WALK_NEXT
+#include "ring_walk.inc"
     // the two planes the next tile adds (slide: its halo planes 2, 3; new column: its planes 0, 1): in flight under
     // the MFMA phase, bound for the two ring slots this tile does not read
     if (!(SPLIT_ABL & 4)) fetch_plane(nz * TZs - 1 + (slide ? 2 : 0) + pz, on);
     __builtin_amdgcn_sched_barrier(0);                 // (the scheduler would sink the loads to their use, behind the MFMAs)
     TS(1);
 
-    // ---- operand base addresses of this wave: planes pz, pz+1 (pairs along z) and pz+2 ----
-    const int s0 = mod6(rot + pz), s1 = mod6(s0 + 1), s2 = mod6(s1 + 1);
-    const int aP = ((kg >> 1) ? s1 : s0) * PLANE_B + lane_b;
-    const int aQ = s2 * PLANE_B + lane_b + (kg >> 1) * 32;
-    const int aR = s2 * PLANE_B + lane_b + 2 * 32 + (kg >> 1) * (HXs * 32);
+#define RING_WALK_OPERANDS
+#include "ring_walk.inc"
     unsigned char* const cdst = smem + mod6(rot + 4 + pz) * PLANE_B;
 
     f32x4 acc[RYs];
@@ -415,8 +362,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
           // consecutive MFMAs go to different accumulators
           static_for<0, 9>([&](auto uc) {
             constexpr int term = decltype(uc)::v / 3, u = decltype(uc)::v % 3;
-            constexpr int r = cls < 2 ? h - u : (u == 0 ? h : (u == 1 ? h - 2 : -1));
-            constexpr int p = cls == 0 ? kx * 3 + u : (cls == 1 ? 9 + u : 12 + u);
+            constexpr int r = op_row(cls, h, u), p = op_pair(cls, kx, u);
             if constexpr (r >= 0 && r < RYs) {
               if constexpr (term == 0 && NP != 1) acc[r] = mfma_k32(whi[p], vl, acc[r]);
               if constexpr (term == 1 && NP != 1) acc[r] = mfma_k32(wlo[NP == 1 ? 0 : p], vh, acc[r]);
@@ -439,7 +385,7 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
     }
     TS(2);
     if constexpr (SPLIT_E0 >= NOP + SPLIT_PF)          // (A/B: epilogue / conversion behind the MFMA phase instead of inside it)
-      static_for<0, 2 * RYs>([&](auto ic) { epi_part(E, accP, IC<decltype(ic)::v / 2>{}, IC<decltype(ic)::v % 2>{}); });
+      ring_epilogue(epi_part, E, accP);
 #if SPLIT_ABL & 32
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     TS(3);
@@ -449,27 +395,11 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_f16x3_kernel(
     TS(4);
     lds_barrier_s();                                   // this tile's planes 0, 1 are free; the new planes are visible
     TS(6);
-    if (on && !slide) {
-      // bottom of a new column: what was fetched are its planes 0, 1 (now in slots rot+4, rot+5); planes 2, 3 go to
-      // the slots this tile has just released (exposed once per column)
-      rot = mod6(rot + 4);
-      fetch_plane(nz * TZs + 1 + pz, true);
-      commit_plane(mod6(rot + 2 + pz));
-      lds_barrier_s();
-    } else {
-      rot = mod6(rot + 2);
-    }
-#pragma unroll
-    for (int r = 0; r < RYs; ++r) accP[r] = acc[r];
-    px_ = cx; py_ = cy; pz_ = cz; pn_ = cn;
-    cx = nx; cy = ny; cz = nz; cn = nn;
+#define RING_WALK_TURN
+#include "ring_walk.inc"
   }
-  {                                                    // the last tile's epilogue
-    if (t_end - t_begin == 1 || pz_ == 0) epi_column(px_, py_, pn_);
-    Epi E;
-    epi_tile(E, pz_, true);
-    static_for<0, 2 * RYs>([&](auto ic) { epi_part(E, accP, IC<decltype(ic)::v / 2>{}, IC<decltype(ic)::v % 2>{}); });
-  }
+#define RING_WALK_LAST
+#include "ring_walk.inc"
   if (amax_out != nullptr) {
     float m = wave_amax;
 #pragma unroll
@@ -492,20 +422,13 @@ extern "C" int lf_conv3d_c16_split(const float* x, const void* wsplit, const flo
                                    const float* prev_y, const float* prev_norm, unsigned prev_flags,
                                    const float* amax_in, float* amax_out, void* stream) {
   lf_clear_error();
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return LF_EINVAL;
-  if ((long)D * H * W * 64 >= 0x7fffffffL || !(slope > 0.f && slope < 1.f)) return LF_EINVAL;
+  RingPlan P;
+  if (!P.shape(N, D, H, W) || !(slope > 0.f && slope < 1.f)) return LF_EINVAL;
   if (!lf_aligned16(x) || !lf_aligned16(y) || !lf_aligned16(wsplit) || (bias && !lf_aligned16(bias))) return LF_EALIGN;
   if (prev_y != nullptr && (flags != 0 || bias != nullptr)) return LF_EINVAL;
   if ((prev_flags & LF_EPI_PIXELNORM) && prev_y != nullptr && prev_norm == nullptr) return LF_EINVAL;
-  const int ptx = (W + TXs - 1) / TXs, pty = (H + TYs - 1) / TYs, ptz = (D + TZs - 1) / TZs;
-  const long pt = (long)ptx * pty * ptz * N;
-  if (pt > 0x7fffffffL) return LF_EINVAL;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
+  unsigned grid;
+  if (!P.grid(SPLIT_WGS, grid)) return LF_EINVAL;                 // two resident workgroups per CU
   const size_t shmem = (size_t)LDSs;
   typedef void (*kern_t)(const float*, const void*, const float*, float*, float*, int, int, int, int, int, int, int, int, float,
                          unsigned, float, float, const float*, const float*, unsigned, const float*, float*, int);
@@ -515,11 +438,10 @@ extern "C" int lf_conv3d_c16_split(const float* x, const void* wsplit, const flo
     hipError_t e = lf_ensure_dyn_lds(attr_set[i], (const void*)kerns[i], (int)shmem);
     if (e != hipSuccess) return (int)e;
   }
-  const long want = (long)SPLIT_WGS * cus;                        // two resident workgroups per CU
-  const unsigned grid = (unsigned)(pt < want ? pt : want);
   const kern_t kern = kerns[prev_y != nullptr ? 1 : 0];
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, (hipStream_t)stream, x, wsplit, bias, y, norm_out, N, D, H,
-                     W, ptx, pty, ptz, (int)pt, he, flags, slope, eps, prev_y, prev_norm, prev_flags, amax_in, amax_out, 0);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, (hipStream_t)stream, x, wsplit, bias, y, norm_out, N, D, H, W,
+                     P.tiles_x, P.tiles_y, P.tiles_z, P.ntiles, he, flags, slope, eps, prev_y, prev_norm, prev_flags, amax_in,
+                     amax_out, 0);
   return lf_launch_status();
 }
 
@@ -554,20 +476,13 @@ static int ring_bf16_launch(const void* x, const void* wpack, const float* bias,
                             int N, int D, int H, int W, float he, unsigned flags, float slope, float eps,
                             const void* addend, int round_out, int io, void* stream) {
   lf_clear_error();
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || round_out < 0 || round_out > 1) return LF_EINVAL;
-  if ((long)D * H * W * 64 >= 0x7fffffffL || !(slope > 0.f && slope < 1.f)) return LF_EINVAL;
+  RingPlan P;
+  if (!P.shape(N, D, H, W) || round_out < 0 || round_out > 1 || !(slope > 0.f && slope < 1.f)) return LF_EINVAL;
   if (flags & ~(LF_EPI_LRELU | LF_EPI_PIXELNORM)) return LF_EINVAL;
   if (!lf_aligned16(x) || !lf_aligned16(y) || !lf_aligned16(wpack) || (bias && !lf_aligned16(bias)) || (addend && !lf_aligned16(addend))) return LF_EALIGN;
   if (addend != nullptr && (flags != 0 || bias != nullptr || round_out != 0)) return LF_EINVAL;
-  const int ptx = (W + TXs - 1) / TXs, pty = (H + TYs - 1) / TYs, ptz = (D + TZs - 1) / TZs;
-  const long pt = (long)ptx * pty * ptz * N;
-  if (pt > 0x7fffffffL) return LF_EINVAL;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
+  unsigned grid;
+  if (!P.grid(g_ring_bf16_wgs, grid)) return LF_EINVAL;           // (35 KB of LDS and < 170 VGPRs: three fit)
   const size_t shmem = (size_t)(LO_OFF + GUARD_B);
   typedef void (*kern_t)(const float*, const void*, const float*, float*, float*, int, int, int, int, int, int, int, int, float,
                          unsigned, float, float, const float*, const float*, unsigned, const float*, float*, int);
@@ -580,10 +495,8 @@ static int ring_bf16_launch(const void* x, const void* wpack, const float* bias,
        conv3d_c16_f16x3_kernel<true, 1, 6>, conv3d_c16_f16x3_kernel<true, 1, 7>}};
   const kern_t kern = kerns[addend != nullptr ? 1 : 0][io];
   if (kern == nullptr) return LF_EINVAL;
-  const long want = (long)g_ring_bf16_wgs * cus;               // (35 KB of LDS and < 170 VGPRs: three fit)
-  const unsigned grid = (unsigned)(pt < want ? pt : want);
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), shmem, (hipStream_t)stream, (const float*)x, wpack, bias, (float*)y, norm_out,
-                     N, D, H, W, ptx, pty, ptz, (int)pt, he, flags, slope, eps, (const float*)addend, (const float*)nullptr,
-                     (unsigned)LF_EPI_ADD, (const float*)nullptr, (float*)nullptr, round_out);
+                     N, D, H, W, P.tiles_x, P.tiles_y, P.tiles_z, P.ntiles, he, flags, slope, eps, (const float*)addend,
+                     (const float*)nullptr, (unsigned)LF_EPI_ADD, (const float*)nullptr, (float*)nullptr, round_out);
   return lf_launch_status();
 }

@@ -998,12 +998,7 @@ int launch_wino(const float* x, const void* upack, const float* bias, float* y, 
   const int ptx = (W + TXw - 1) / TXw, pty = (H + TYw - 1) / TYw, ptz = (D + TZw - 1) / TZw;
   const long pt = (long)ptx * pty * ptz * N;
   if (pt > 0x7fffffffL) return LF_EINVAL;
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
+  const int cus = lf_cu_count();
   const size_t shmem = (size_t)LDSw;
   static lf_devmask_t attr_set;                                   // (one instance per kernel: the template is per kernel)
   {

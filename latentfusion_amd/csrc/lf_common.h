@@ -35,6 +35,20 @@ static inline hipError_t lf_ensure_dyn_lds(lf_devmask_t& done, const void* fn, i
   return e;
 }
 
+// Compute units of the CURRENT device, asked once per device ordinal (the grids of the persistent kernels are multiples of it;
+// a process that drives several GPUs gets each one's own count -- ADVICE r06); 256 where the runtime does not say.
+static inline int lf_cu_count() {
+  static std::atomic<int> cus[64];
+  int dev = 0, v = 0;
+  const bool known = hipGetDevice(&dev) == hipSuccess;
+  std::atomic<int>& slot = cus[dev & 63];
+  const int c = slot.load(std::memory_order_relaxed);
+  if (c != 0) return c;
+  const int n = (known && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  slot.store(n, std::memory_order_relaxed);
+  return n;
+}
+
 __device__ __forceinline__ float lf_wave_sum(float v) {
   // fixed-order butterfly over the 64 lanes of a wavefront (deterministic)
 #pragma unroll

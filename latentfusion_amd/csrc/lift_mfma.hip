@@ -319,16 +319,6 @@ __global__ void __launch_bounds__(256) proj16_bwd_reduce_kernel(const float* __r
   gw[o * (16 * S) + c * S + d] = s * he;
 }
 
-int lift_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return cus;
-}
-
 }  // namespace
 
 extern "C" int lf_lift16_fwd(const float* x, const void* wtab, const float* btab, void* vol, float* norm, long R, long P, int S,
@@ -344,14 +334,14 @@ extern "C" int lf_lift16_fwd(const float* x, const void* wtab, const float* btab
     if (e != hipSuccess) return (int)e;
   }
   const long groups = R / 16;
-  long nb = 2L * lift_cus();
+  long nb = 2L * lf_cu_count();
   if (nb * 4 > groups) nb = (groups + 3) / 4;
   hipLaunchKernelGGL(lift_fwd_mfma_kernel, dim3((unsigned)nb), dim3(256), shmem, (hipStream_t)stream, x, (const __bf16*)wtab, btab,
                      (unsigned char*)vol, norm, R, P, S, he, slope, eps);
   return lf_launch_status();
 }
 
-extern "C" size_t lf_lift16_bwd_scratch_bytes(int S) { return (size_t)lift_cus() * (size_t)S * (256 + 16) * sizeof(float); }
+extern "C" size_t lf_lift16_bwd_scratch_bytes(int S) { return (size_t)lf_cu_count() * (size_t)S * (256 + 16) * sizeof(float); }
 
 extern "C" int lf_lift16_bwd(const void* gvol, const void* yvol, const float* norm, const float* x, const void* wtab_t, float* gx, float* gw,
                              float* gb, void* scratch, size_t scratch_bytes, long R, long P, int S, float he, float slope, int round_gx,
@@ -362,7 +352,7 @@ extern "C" int lf_lift16_bwd(const void* gvol, const void* yvol, const float* no
   if (S != 16 && S != 32 && S != 64 && S != 128) return LF_EINVAL;
   if (!lf_aligned16(gvol) || !lf_aligned16(yvol) || !lf_aligned16(x) || !lf_aligned16(wtab_t) || !lf_aligned16(gx) || !lf_aligned16(scratch)) return LF_EALIGN;
   const long groups = R / 16;
-  int nwg = lift_cus();
+  int nwg = lf_cu_count();
   if (nwg > groups) nwg = (int)groups;
   if (scratch == nullptr || scratch_bytes < (size_t)nwg * S * (256 + 16) * sizeof(float)) return LF_ENOSPC;
   float* pw = (float*)scratch;
@@ -399,14 +389,14 @@ extern "C" int lf_proj16_fwd(const void* vol, const void* wtab, const float* bia
     if (e != hipSuccess) return (int)e;
   }
   const long groups = R / 16;
-  long nb = 2L * lift_cus();
+  long nb = 2L * lf_cu_count();
   if (nb * 4 > groups) nb = (groups + 3) / 4;
   hipLaunchKernelGGL(proj16_fwd_kernel, dim3((unsigned)nb), dim3(256), shmem, (hipStream_t)stream, (const unsigned char*)vol,
                      (const __bf16*)wtab, bias, y, norm, R, P, S, he, slope, eps);
   return lf_launch_status();
 }
 
-extern "C" size_t lf_proj16_bwd_scratch_bytes(int S) { return (size_t)lift_cus() * (size_t)S * 256 * sizeof(float); }
+extern "C" size_t lf_proj16_bwd_scratch_bytes(int S) { return (size_t)lf_cu_count() * (size_t)S * 256 * sizeof(float); }
 
 extern "C" int lf_proj16_bwd(const float* gp, const void* vol, const void* wtab_t, void* gxvol, float* gw, void* scratch,
                              size_t scratch_bytes, long R, long P, int S, float he, void* stream) {
@@ -416,7 +406,7 @@ extern "C" int lf_proj16_bwd(const float* gp, const void* vol, const void* wtab_
   if (S != 16 && S != 32 && S != 64 && S != 128) return LF_EINVAL;
   if (!lf_aligned16(gp) || !lf_aligned16(vol) || !lf_aligned16(wtab_t) || !lf_aligned16(gxvol) || !lf_aligned16(scratch)) return LF_EALIGN;
   const long groups = R / 16;
-  int nwg = lift_cus();
+  int nwg = lf_cu_count();
   if (nwg > groups) nwg = (int)groups;
   if (scratch == nullptr || scratch_bytes < (size_t)nwg * S * 256 * sizeof(float)) return LF_ENOSPC;
   const size_t shmem = (size_t)S * 512 + 8 * 1024;

@@ -1,6 +1,7 @@
-// The tile / ring geometry and the small device helpers shared by the ring convolutions (conv_split.hip: the f16x3 and bf16
-// forms of the 16 -> 16 convolution; conv_gru.hip: the multi-output forms of the ConvGRU recurrence).  See conv_split.hip for
-// the organisation these constants describe.
+// What the ring convolutions share as C++ (conv_split.hip: the f16x3 and bf16 forms of the 16 -> 16 convolution; conv_gru.hip:
+// the multi-output forms of the ConvGRU recurrence): the tile / ring geometry, the operand tables, the small device helpers and
+// the host side of a launch (RingPlan).  The kernels' tile walk is shared as text (ring_walk.inc, which says why).  See
+// conv_split.hip for the organisation these constants describe.
 #pragma once
 #include "lf_common.h"
 
@@ -43,6 +44,10 @@ __host__ __device__ constexpr int op_cls(int i) { return i < 18 ? 0 : (i < 24 ? 
 __host__ __device__ constexpr int op_h(int i) { return i % 6; }
 __host__ __device__ constexpr int op_kx(int i) { return i < 18 ? i / 6 : 0; }
 
+// the up to three uses of operand (cls, h, kx), u = 0..2: output row (outside [0, RYs): none) and weight pair
+__host__ __device__ constexpr int op_row(int cls, int h, int u) { return cls < 2 ? h - u : (u == 0 ? h : (u == 1 ? h - 2 : -1)); }
+__host__ __device__ constexpr int op_pair(int cls, int kx, int u) { return cls == 0 ? kx * 3 + u : (cls == 1 ? 9 + u : 12 + u); }
+
 __device__ __forceinline__ void lds_barrier_s() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // sum over the four lanes n, n+16, n+32, n+48 (the four channel quarters of a voxel), same value in all four:
 // v_permlane32_swap / v_permlane16_swap exchange half-waves / neighbouring rows of 16 in the VALU (a __shfl_xor is a
@@ -67,5 +72,34 @@ __device__ __forceinline__ f32x4 mfma_k32(const bf16x8s a, const bf16x8s b, cons
 __device__ __forceinline__ float rb16(float v) { return (float)(__bf16)v; }
 __device__ __forceinline__ int mod6(int v) { return v >= 6 ? v - 6 : v; }      // v in [0, 12)
 
+// the epilogue of a finished tile in one piece: 2 parts per output row (epi_part is the kernel's lambda)
+template <class P, class E>
+__device__ __forceinline__ void ring_epilogue(P& epi_part, const E& e, const f32x4 (&a)[RYs]) {
+  static_for<0, 2 * RYs>([&](auto ic) { epi_part(e, a, IC<decltype(ic)::v / 2>{}, IC<decltype(ic)::v % 2>{}); });
+}
+
+// The host side of a ring launch, shared by lf_conv3d_c16_split, ring_bf16_launch (conv_split.hip) and ring_multi_launch
+// (conv_gru.hip): the shape checks, the tile counts and the grid of the persistent walk.
+struct RingPlan {
+  int tiles_x, tiles_y, tiles_z, ntiles;
+  long pt;
+  // false for an empty shape or a sample of 2^31 bytes or more as fp32 records (the kernels address a sample with 32-bit byte
+  // offsets: per-lane offset + the plane as the scalar offset)
+  bool shape(int N, int D, int H, int W) {
+    if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return false;
+    if ((long)D * H * W * 64 >= 0x7fffffffL) return false;
+    tiles_x = (W + TXs - 1) / TXs; tiles_y = (H + TYs - 1) / TYs; tiles_z = (D + TZs - 1) / TZs;
+    pt = (long)tiles_x * tiles_y * tiles_z * N;
+    ntiles = (int)pt;
+    return true;
+  }
+  // grid = min(tiles, wgs resident workgroups on each CU of the current device); false when the tiles do not count in 31 bits
+  bool grid(int wgs, unsigned& g) const {
+    if (pt > 0x7fffffffL) return false;
+    const long want = (long)wgs * lf_cu_count();
+    g = (unsigned)(pt < want ? pt : want);
+    return true;
+  }
+};
 
 }  // namespace

@@ -829,22 +829,12 @@ bool wgrad_plan(int dims, long total, int Cin, int Cout, bool ones, WgradPlan& p
 
 }  // namespace
 
-static int wgrad_cus() {
-  static int cus = 0;
-  if (cus == 0) {
-    int dev = 0, v = 0;
-    cus = (hipGetDevice(&dev) == hipSuccess &&
-           hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return cus;
-}
-
 static bool wgrad_fast3d(int dims, int N, int D, int H, int W, int Cin, int Cout) {
   return dims == 3 && Cin == 16 && Cout == 16 && (long)D * H * W * 64 < 0x7fffffffL && (long)N * D * H * W >= 8192;
 }
 
 extern "C" size_t lf_conv_bwd_weight_scratch_bytes(int dims, int N, int D, int H, int W, int Cin, int Cout) {
-  if (wgrad_fast3d(dims, N, D, H, W, Cin, Cout)) return (size_t)wgrad_cus() * 8 * 27 * 256 * sizeof(float);
+  if (wgrad_fast3d(dims, N, D, H, W, Cin, Cout)) return (size_t)lf_cu_count() * 8 * 27 * 256 * sizeof(float);
   WgradPlan p;
   if (!wgrad_plan(dims, (long)N * D * H * W, Cin > 0 ? Cin : 1, Cout, Cin <= 0, p)) return 0;
   return (size_t)p.nblk * p.taps * p.nct * p.ncit * 256 * sizeof(float);
@@ -869,7 +859,7 @@ extern "C" int lf_conv_bwd_weight(const float* x, const float* gpre, float* gw, 
     return lf_launch_status();
   }
   if (!ones && wgrad_fast3d(dims, N, D, H, W, Cin, Cout) && lf_aligned16(x) && lf_aligned16(gpre)) {
-    const int cus = wgrad_cus();
+    const int cus = lf_cu_count();
     if (scratch_bytes < (size_t)cus * 8 * 27 * 256 * sizeof(float)) return LF_ENOSPC;
     const int ptx = (W + WTX - 1) / WTX, pty = (H + WTY - 1) / WTY, ptz = (D + WTZ - 1) / WTZ;
     const long pt = (long)ptx * pty * ptz * N;
@@ -932,9 +922,9 @@ static int wgrad_bf16_launch(const void* x, const void* gpre, float* gw, void* s
   // the kernel's 32-bit offsets reach three planes past the sample (halo planes of the last tile + the pair's second plane)
   if ((long)(D + 3) * H * W * 64 > 0xffffffffL) return LF_EINVAL;
 #ifdef WG_OLD
-  const int nb = 2 * wgrad_cus();
+  const int nb = 2 * lf_cu_count();
 #else
-  const int nb = WG_TR_WGS * wgrad_cus();
+  const int nb = WG_TR_WGS * lf_cu_count();
 #endif
   if (scratch_bytes < (size_t)nb * 27 * 256 * sizeof(float)) return LF_ENOSPC;
   const int ptx = (W + WTX - 1) / WTX, pty = (H + WTY - 1) / WTY, ptz = (D + WTZ - 1) / WTZ;

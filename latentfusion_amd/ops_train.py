@@ -2,6 +2,7 @@
 weight / bias gradients, the 16 -> 16 layers and resampler under the bf16 autocast + storage policy, the ConvGRU fuser as one
 autograd node, the fused lift.  Reached through `ops.<name>` (ops.__getattr__) and through ops' dispatchers (conv3x3, conv1x1,
 resample_*, lift), which pick these forms when a gradient is wanted / the policy is on."""
+import functools
 import math  # noqa: F401
 
 import torch
@@ -630,6 +631,35 @@ class _LstmCell(torch.autograd.Function):
         return gcc, gc
 
 
+def _gru_conv(ac, he, x, pack, addend=None, bias=None, out=None, out16=False, rnd=0):
+    """One 16 -> 16 convolution of the per-gate path of _GruFuse: the bf16 ring kernel under the autocast policy (`ac`), the
+    fp32 Winograd kernel otherwise; `addend` selects the addend form."""
+    if ac:
+        return conv3d_c16_ring_bf16_io(x, pack, bias, he, 0, rnd if addend is None else 0, addend=addend, out=out,
+                                       out_bf16=out16)[0]
+    prev = None if addend is None else (addend, None, _lib.LF_EPI_ADD)
+    return conv3d_c16_wino(x, pack, bias, he, 0, prev=prev, out=out)[0]
+
+
+def _gru_weight_grads(ctx, gwb, acc, c16, ws, he, ac):
+    """The (weight, bias) gradients of the three gates from the per-step / per-chunk blocks gwb [*][gate][z | state][27][16][16]
+    (summed in a fixed order) and the gate gradients' sums over the views acc[gate] (coordinate channels, bias)."""
+    outs = []
+    gsum = gwb.sum(dim=0)                                     # [gate][z | state][27][16][16]
+    for k, w in enumerate(ws):
+        gwt = torch.empty(27, 16, w.shape[1], device=gwb.device, dtype=torch.float32)
+        gwt[:, :, :16] = gsum[k, 0]
+        gwt[:, :, 19:] = gsum[k, 1]
+        gc_, _ = conv_bwd_weight(c16, acc[k], 3, 16, he, want_bias=False, bf16=ac)
+        gwt[:, :, 16:19] = gc_[:, :, :3]
+        gw = gwt.reshape(3, 3, 3, 16, w.shape[1]).permute(3, 4, 0, 1, 2).contiguous()
+        if ac:
+            gw = round_bf16(gw)
+        outs.append(gw if ctx.needs_input_grad[2 + 2 * k] else None)
+        outs.append(bias_grad(acc[k], 3) if (ctx.has_bias[k] and ctx.needs_input_grad[3 + 2 * k]) else None)
+    return outs
+
+
 class _GruFuse(torch.autograd.Function):
     """GRUFuser.forward for 16-channel volumes as ONE autograd node (recon/fusion.py:188-197 over modules/gru.py:30-43): the
     recurrence h_i = cell(cat(z_i, coords), h_{i-1}), h_0 = z_0, forward and backward sequenced explicitly.
@@ -665,12 +695,7 @@ class _GruFuse(torch.autograd.Function):
             return _cached(w, 'gru_fuse' + ('@ac' if ac else ''), make)
         pk = [packs(w) for w, _ in gates]                         # [gate][z | coords | state][fwd | transposed]
 
-        def conv(x, pack, addend=None, bias=None, out=None, out16=False, rnd=0):
-            if ac:
-                return conv3d_c16_ring_bf16_io(x, pack, bias, he, 0, rnd if addend is None else 0, addend=addend, out=out,
-                                               out_bf16=out16)[0]
-            prev = None if addend is None else (addend, None, _lib.LF_EPI_ADD)
-            return conv3d_c16_wino(x, pack, bias, he, 0, prev=prev, out=out)[0]
+        conv = functools.partial(_gru_conv, ac, he)
         n = zz[0].numel()
         s = _stream()
         base = [conv(c16, pk[k][1][0], bias=(b.detach() if b is not None else None)) for k, (_, b) in enumerate(gates)]
@@ -767,14 +792,8 @@ class _GruFuse(torch.autograd.Function):
         need_w = any(ctx.needs_input_grad[i] for i in (2, 3, 4, 5, 6, 7))
         g = cl(g.reshape(shape1))
         if ctx.ring:
-            return _GruFuse._backward_ring(ctx, g, zz, c16, (wu, wr, wo), need_z, need_w)
-
-        def conv(x, pack, addend=None, out=None, out16=False, rnd=0):
-            if ac:
-                return conv3d_c16_ring_bf16_io(x, pack, None, he, 0, rnd if addend is None else 0, addend=addend, out=out,
-                                               out_bf16=out16)[0]
-            prev = None if addend is None else (addend, None, _lib.LF_EPI_ADD)
-            return conv3d_c16_wino(x, pack, None, he, 0, prev=prev, out=out)[0]
+            return _gru_backward_ring(ctx, g, zz, c16, (wu, wr, wo), need_z, need_w)
+        conv = functools.partial(_gru_conv, ac, he)
         gz = empty_cl16((V, 16, D, H, W), dev, zz.dtype == torch.bfloat16) if need_z else None
         acc = [empty_cl(shape1, dev).zero_() for _ in range(3)] if need_w else [None] * 3
         # weight-gradient blocks [step][gate][z | state][27][16][16], summed over the steps at the end (fixed order)
@@ -856,21 +875,7 @@ class _GruFuse(torch.autograd.Function):
         if need_z:
             gz[0:1].copy_(g)
         outs = [gz.view(ctx.zshape) if need_z else None, None]
-        if need_w:
-            gsum = gwb.sum(dim=0)                                 # [gate][z | state][27][16][16]
-            for k, w in enumerate((wu, wr, wo)):
-                gwt = torch.empty(27, 16, w.shape[1], device=dev, dtype=torch.float32)
-                gwt[:, :, :16] = gsum[k, 0]
-                gwt[:, :, 19:] = gsum[k, 1]
-                gc_, _ = conv_bwd_weight(c16, acc[k], 3, 16, he, want_bias=False, bf16=ac)
-                gwt[:, :, 16:19] = gc_[:, :, :3]
-                gw = gwt.reshape(3, 3, 3, 16, w.shape[1]).permute(3, 4, 0, 1, 2).contiguous()
-                if ac:
-                    gw = round_bf16(gw)
-                outs.append(gw if ctx.needs_input_grad[2 + 2 * k] else None)
-                outs.append(bias_grad(acc[k], 3) if (ctx.has_bias[k] and ctx.needs_input_grad[3 + 2 * k]) else None)
-        else:
-            outs += [None] * 6
+        outs += _gru_weight_grads(ctx, gwb, acc, c16, (wu, wr, wo), he, ac) if need_w else [None] * 6
         return tuple(outs)
 
 
@@ -896,7 +901,6 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
     shape1 = (1,) + tuple(zz.shape[1:])
     n = zz[0].numel()
     s = _stream()
-    wu, wr, wo = ws
     # transposed packs: [o: towards r h | towards x], [u: towards x | towards h], [r: towards x | towards h]
     tp = tuple(torch.stack(p) for p in ((pk[2][2][1], pk[2][0][1]), (pk[0][0][1], pk[0][2][1]), (pk[1][0][1], pk[1][2][1])))
     gz = empty_cl16((V, 16, D, H, W), dev, True)
@@ -973,23 +977,8 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
         gz = gz.float()
     gz[0:1].copy_(g)
     outs = [gz.view(ctx.zshape) if need_z else None, None]
-    if need_w:
-        gsum = gwb.sum(dim=0)                                     # [gate][z | state][27][16][16], fixed order
-        for k, w in enumerate((wu, wr, wo)):
-            gwt = torch.empty(27, 16, w.shape[1], device=dev, dtype=torch.float32)
-            gwt[:, :, :16] = gsum[k, 0]
-            gwt[:, :, 19:] = gsum[k, 1]
-            gc_, _ = conv_bwd_weight(c16, acc[k], 3, 16, he, want_bias=False, bf16=True)
-            gwt[:, :, 16:19] = gc_[:, :, :3]
-            gw = round_bf16(gwt.reshape(3, 3, 3, 16, w.shape[1]).permute(3, 4, 0, 1, 2).contiguous())
-            outs.append(gw if ctx.needs_input_grad[2 + 2 * k] else None)
-            outs.append(bias_grad(acc[k], 3) if (ctx.has_bias[k] and ctx.needs_input_grad[3 + 2 * k]) else None)
-    else:
-        outs += [None] * 6
+    outs += _gru_weight_grads(ctx, gwb, acc, c16, ws, he, True) if need_w else [None] * 6
     return tuple(outs)
-
-
-_GruFuse._backward_ring = staticmethod(_gru_backward_ring)
 
 
 def gru_fuse(z, c16, cell):

@@ -54,7 +54,9 @@ def test_conv3d_c16_bf16_kernel(shape):
 def test_conv3d_c16_ring_bf16_kernel(shape):
     """lf_conv3d_c16_ring_bf16 (the f16x3 kernel's ring organisation with one bf16 piece: the kernel the autocast step
     uses) against the same emulation of autocast as above -- forward with both epilogues, the data gradient, and the
-    addend form of the ConvGRU gates; ragged extents, odd depths, several columns per workgroup; run-to-run identical."""
+    addend form of the ConvGRU gates; ragged extents, odd depths; run-to-run identical.  These shapes have at most 204 tiles:
+    fewer than the launch's workgroups on a device of more than 102 CUs, where every workgroup then gets ONE tile --
+    test_conv3d_c16_ring_bf16_tile_walk is the shape that walks."""
     from latentfusion_amd import ops
     from latentfusion_amd._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM
     g = torch.Generator().manual_seed(sum(shape) + 1)
@@ -87,6 +89,57 @@ def test_conv3d_c16_ring_bf16_kernel(shape):
     add = torch.randn(shape, generator=g)
     ya, _ = ops.conv3d_c16_ring_bf16(xd, wp, None, he, 0, 0, addend=ops.cl(add.to(DEV)))
     torch.testing.assert_close(ya.cpu().double(), acc * he + add.double(), atol=2e-5, rtol=1e-5)
+
+
+def test_conv3d_c16_ring_bf16_tile_walk():
+    """lf_conv3d_c16_ring_bf16 at the smallest shape whose tiles outnumber the workgroups of the launch (two per CU) more than
+    twice: D = 9 and H = 37 give 5 x 5 ragged tiles in z and y, W as many 16-voxel tiles as it takes.  Every workgroup then
+    walks three or more consecutive tiles (z fastest) and the ranges start at every z phase of the five-tile columns: the ring
+    slides, new columns are entered, and every tile's epilogue rides under the next tile's MFMAs.  Forward with LeakyReLU +
+    PixelNorm and the addend form against fp64, the storage variants of lf_conv3d_c16_ring_bf16_io against the fp32-storage
+    launch bit for bit, two launches bit-equal."""
+    from latentfusion_amd import ops
+    from latentfusion_amd._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tx = 4 * cus // 25 + 1                                                  # the smallest tx with 25 tx > 4 CUs
+    D, H, W = 9, 37, 16 * tx - 13
+    ntiles = ((D + 1) // 2) * ((H + 7) // 8) * ((W + 15) // 16)
+    assert ntiles > 4 * cus, f'{ntiles} tiles on {cus} CUs: fewer than three tiles per workgroup'
+    shape = (1, 16, D, H, W)
+    g = torch.Generator().manual_seed(77)
+    x = bf(torch.randn(shape, generator=g))
+    w = torch.randn(16, 16, 3, 3, 3, generator=g)
+    b = torch.randn(16, generator=g) * 0.1
+    add = bf(torch.randn(shape, generator=g))
+    he = ops.he_constant(w)
+    xd, addd, bd = ops.cl(x.to(DEV)), ops.cl(add.to(DEV)), b.to(DEV)
+    wp = ops.pack_conv3d_c16_ring_bf16(w.to(DEV))
+    acc = F.conv3d(x.double(), bf(w).double(), None, 1, 1)
+    flags = LF_EPI_LRELU | LF_EPI_PIXELNORM
+    y0, n0 = ops.conv3d_c16_ring_bf16(xd, wp, bd, he, flags, 0)
+    y0b, n0b = ops.conv3d_c16_ring_bf16(xd, wp, bd, he, flags, 0)
+    assert torch.equal(y0, y0b) and torch.equal(n0, n0b)
+    pre = F.leaky_relu(acc * he + b.double().view(1, -1, 1, 1, 1), 0.2)
+    nrm = torch.sqrt((pre ** 2).mean(dim=1, keepdim=True) + 1e-8)
+    torch.testing.assert_close(y0.cpu().double(), pre / nrm, atol=2e-5, rtol=1e-5)
+    torch.testing.assert_close(n0.view(1, D, H, W).cpu().double(), nrm.squeeze(1), atol=1e-5, rtol=1e-5)
+    ya, _ = ops.conv3d_c16_ring_bf16(xd, wp, None, he, 0, 0, addend=addd)
+    torch.testing.assert_close(ya.cpu().double(), acc * he + add.double(), atol=2e-5, rtol=1e-5)
+    # the storage variants (x and the addend hold bf16-representable numbers)
+    cl3 = torch.channels_last_3d
+    for fl, addend, bias in ((0, None, None), (flags, None, bd), (0, addd, None)):
+        ref, nref = ops.conv3d_c16_ring_bf16_io(xd, wp, bias, he, fl, 0, addend=addend)
+        for in16 in (False, True):
+            for out16 in (False, True):
+                for add16 in ((False, True) if addend is not None else (False,)):
+                    xi = xd.to(torch.bfloat16).contiguous(memory_format=cl3) if in16 else xd
+                    ai = (addend.to(torch.bfloat16).contiguous(memory_format=cl3) if add16 else addend) if addend is not None else None
+                    y, nv = ops.conv3d_c16_ring_bf16_io(xi, wp, bias, he, fl, 0, addend=ai, out_bf16=out16)
+                    assert y.dtype == (torch.bfloat16 if out16 else torch.float32)
+                    want = ref.to(torch.bfloat16) if out16 else ref
+                    assert torch.equal(y, want), (fl, in16, out16, add16, (y.float() - want.float()).abs().max().item())
+                    if nref is not None:
+                        assert torch.equal(nv, nref)
 
 
 @pytest.mark.parametrize('shape', [(1, 16, 16, 16, 32), (2, 16, 9, 21, 45), (3, 16, 6, 40, 35), (1, 16, 64, 64, 64)])

@@ -263,3 +263,90 @@ def test_bf16_state_copy_forms(N, D, H, W):
     ops_train.ring_multi(hn, p1, he, [(ra, rz, False)], extra=_lib.LF_RING_EX_RH, o2=rha)
     ops_train.ring_multi(h16, p1, he, [(rb, rz, False)], extra=_lib.LF_RING_EX_RH, e0=hn, o2=rhb)
     assert torch.equal(ua, ub) and torch.equal(ra, rb) and torch.equal(rha, rhb)
+
+
+def _walk_shape():
+    """The smallest volume whose tiles outnumber the launch's workgroups (two per CU) more than twice: 5 x 5 ragged tiles in z
+    and y (D = 9, H = 37) and as many 16-voxel tiles in x as that takes.  A workgroup then walks a range of three or more
+    consecutive tiles (z fastest), the ranges start at every z phase of the five-tile columns, and the walk slides the ring,
+    enters new columns and finishes every tile's epilogue under the next tile's MFMAs."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tx = 4 * cus // 25 + 1                                          # the smallest tx with 25 tx > 4 CUs
+    D, H, W = 9, 37, 16 * tx - 13
+    ntiles = ((D + 1) // 2) * ((H + 7) // 8) * ((W + 15) // 16)
+    assert ntiles > 4 * cus, f'{ntiles} tiles on {cus} CUs: fewer than three tiles per workgroup'
+    return D, H, W
+
+
+def _grid_vol(g, shape, dtype):
+    """Random multiples of 1/4 in [-2, 2] (bf16-exact), channels-last."""
+    v = torch.randint(-8, 9, shape, generator=g).float() / 4
+    return v.cuda().contiguous(memory_format=torch.channels_last_3d).to(dtype)
+
+
+def test_tile_walk_of_three_or_more_tiles_per_workgroup():
+    """Every instantiated family of ring_multi_kernel at the walk shape (_walk_shape: the SHAPES above give every workgroup ONE
+    tile, so they never slide the ring, enter a column or overlap an epilogue with the next tile) against plain torch: fp32
+    conv3d of the bf16-rounded operands, fp32 outputs within atol = rtol = 2e-4, bf16 outputs within one bf16 ulp.
+    Activations and weights are multiples of 1/4 in [-2, 2]: a sum of 432 such products has 15 significant bits, so every fp32
+    partial sum is exact in any order and the reference convolution carries no error of its own -- a relative bound on a bf16
+    result would otherwise fail on the few sums that cancel to nearly zero, whatever the kernel does.  The reference epilogue is
+    evaluated in fp64 (one rounding, like the kernel's fma)."""
+    from latentfusion_amd import _lib, ops, ops_train
+    from latentfusion_amd._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM
+    D, H, W = _walk_shape()
+    g = torch.Generator().manual_seed(21)
+    cl3 = torch.channels_last_3d
+    shape = (1, 16, D, H, W)
+    x = _grid_vol(g, shape, torch.bfloat16)
+    w = [(torch.randint(-8, 9, (16, 16, 3, 3, 3), generator=g).float() / 4).cuda() for _ in range(2)]
+    packs = torch.stack([ops.pack_conv3d_c16_ring_bf16(t) for t in w]).contiguous()
+    p0, p1 = packs[:1].contiguous(), packs[1:].contiguous()
+    he = float((2.0 / (16 * 27)) ** 0.5)
+    he32 = float(torch.tensor(he, dtype=torch.float32))
+    conv = [torch.nn.functional.conv3d(x.float(), t, padding=1).contiguous(memory_format=cl3) for t in w]     # exact
+    add32 = _vol(g, 1, D, H, W, torch.float32)
+    add16 = _vol(g, 1, D, H, W, torch.bfloat16)
+    fma = lambda c, a: (c.double() * he32 + a.double()).float()     # noqa: E731
+    e = lambda b16: ops.empty_cl16(shape, 'cuda', b16)              # noqa: E731
+    # FL = 8: fp32 addend -> fp32
+    y = e(False)
+    ops_train.ring_multi(x, p0, he, [(y, add32, False)])
+    torch.testing.assert_close(y, fma(conv[0], add32), atol=2e-4, rtol=2e-4)
+    # FL = 10: fp32 addend -> bf16;  FL = 11: bf16 addend -> bf16
+    y = e(True)
+    ops_train.ring_multi(x, p1, he, [(y, add32, False)])
+    _close_bf16(y, fma(conv[1], add32))
+    ops_train.ring_multi(x, p0, he, [(y, add16, False)])
+    _close_bf16(y, fma(conv[0], add16))
+    # FL = 6: bf16(bf16(conv) * he) -> bf16, the same sums and roundings as the one-output kernel's
+    ops_train.ring_multi(x, p0, he, [(y, None, True)])
+    _close_bf16(y, (conv[0].to(torch.bfloat16).float() * he32).to(torch.bfloat16))
+    want, _ = ops.conv3d_c16_ring_bf16_io(x, packs[0], None, he, 0, 1, out_bf16=True)
+    assert torch.equal(y, want)
+    # two groups, runtime flags: bf16 addend -> bf16 and fp32 addend -> fp32
+    y0, y1 = e(True), e(False)
+    ops_train.ring_multi(x, packs, he, [(y0, add16, False), (y1, add32, False)])
+    _close_bf16(y0, fma(conv[0], add16))
+    torch.testing.assert_close(y1, fma(conv[1], add32), atol=2e-4, rtol=2e-4)
+    # EX_BLOCK from both input storages: bf16(bf16(conv) * he) + bias, LeakyReLU, PixelNorm (norms stored)
+    bias = (torch.randn(16, generator=g) * 0.3).cuda()
+    pre = torch.nn.functional.leaky_relu((conv[1].to(torch.bfloat16).float() * he32).to(torch.bfloat16).float() + bias.view(1, -1, 1, 1, 1), 0.2)
+    nref = torch.sqrt((pre.double() ** 2).mean(dim=1) + 1e-8)
+    yref = (pre.double() / nref.unsqueeze(1)).float()
+    for xin in (x, x.float()):
+        nrm = torch.empty(D * H * W, device='cuda')
+        ops_train.ring_multi(xin, p1, he, [(y, None, True)], extra=_lib.LF_RING_EX_BLOCK, e0=bias, o2=nrm)
+        _close_bf16(y, yref)
+        torch.testing.assert_close(nrm.view(1, D, H, W), nref.float(), atol=2e-4, rtol=2e-4)
+    # EX_PREV against the rounded data gradient + lf_epilogue_bwd_c16 on the producer's activation, with the bias sums
+    t = torch.nn.functional.leaky_relu(torch.randn(shape, generator=g).cuda().contiguous(memory_format=cl3), 0.2)
+    nrm = torch.sqrt((t * t).mean(dim=1) + 1e-8).reshape(-1).contiguous()
+    act = (t / nrm.view(1, 1, D, H, W)).to(torch.bfloat16).contiguous(memory_format=cl3)
+    out = torch.empty_like(x)
+    gbuf = torch.zeros(16 * 1025, device='cuda')
+    ops_train.ring_multi(x, p0, he, [(out, None, True)], extra=_lib.LF_RING_EX_PREV, e0=act, e1=nrm, o2=gbuf)
+    gy, _ = ops.conv3d_c16_ring_bf16_io(x, packs[0], None, he, 0, 1, out_bf16=True)
+    want, gb = ops_train.epilogue_bwd_c16(gy, act, nrm, LF_EPI_LRELU | LF_EPI_PIXELNORM, True)
+    _close_bf16(out, want)
+    torch.testing.assert_close(gbuf[:16], gb, atol=1e-4 * float(gb.abs().max()) + 1e-6, rtol=2e-3)
