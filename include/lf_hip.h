@@ -337,6 +337,28 @@ int lf_wino_fused_gemm(const float* V, const float* U2, const float* bias, float
                        int dims, int N, int D, int H, int W, int Cin, int Cout, float he, unsigned flags, float slope,
                        void* stream);
 
+/* Row-major GEMM with the Block epilogue in the store, on the same fp32 MFMA (no library GEMM on the hot path):
+ *   y[m][co] = epilogue( he * sum_k x[m][k] * W[co][k] + bias[co] )        m < M, co < Cout, k < K
+ *   epilogue = [LeakyReLU(slope)] ; [PixelNorm over co (eps), norm_out[m] = sqrt(mean_co(y^2) + eps)]
+ * Replaces FactorProjection3d2d.forward (view -> 1x1 conv -> LeakyReLU -> PixelNorm) of modules/geometry.py:744-749 with
+ * Equalized.forward modules/equalized.py:57-64 and PixelNorm modules/__init__.py:14-15 on the ranking path, where it was a
+ * library GEMM + ATen leaky_relu_ + lf_pixelnorm_fwd: one launch, PixelNorm over ALL output channels (lf_conv1x1_fwd stops
+ * at 128, lf_wino_fused_gemm has none).
+ * x: [M][K], row stride K -- the depth-innermost rows LF_OUT_DEPTH_INNER makes the last camera block write (K = D*C,
+ * k = d*C + c).  y: [M][Cout].  bias: [Cout] or NULL.  norm_out: [M], or NULL (ignored without LF_EPI_PIXELNORM).
+ * wpack: [CoutP][K] row-major, wpack[co][k] = W[co][k], rows Cout .. CoutP-1 zero, CoutP = lf_rows_gemm_cout_padded(Cout)
+ * (16, 32, 64, 128, 192 or 256; 0 for a Cout outside the domain).
+ * flags: LF_EPI_LRELU | LF_EPI_PIXELNORM as for lf_conv1x1_fwd.
+ * One workgroup owns 128 rows and all Cout columns of them; the contraction of an output element runs over k in ONE order
+ * that depends on K alone (no split over K, no atomics), so a row's result is bit-identical whatever M it is computed in
+ * and the kernel is run-to-run identical.  Rows >= M are neither read nor written.
+ * Domain: K >= 4, K % 4 == 0; 16 <= Cout <= 256, Cout % 4 == 0; 1 <= M <= 128 * (2^31 - 1) (the workgroup count is 32-bit,
+ * addresses are 64-bit); x, wpack, y 16-byte aligned.  Returns LF_EINVAL for a NULL x / wpack / y, a size or flag outside
+ * that, LF_EALIGN for a misaligned buffer; nothing is launched then. */
+int lf_rows_gemm_cout_padded(int Cout);
+int lf_rows_gemm_epi(const float* x, const float* wpack, const float* bias, float* y, float* norm_out,
+                     long M, int K, int Cout, float he, unsigned flags, float slope, float eps, void* stream);
+
 /* Split-precision ("f16x3") form of the 3-D wide Winograd convolution: the per-frequency products on
  * v_mfma_f32_16x16x32_f16, each fp32 product formed from three f16 products of hi / lo halves
  * (a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi, fp32 accumulation); otherwise the contract of lf_wino_fused_gemm for dims = 3.

@@ -317,6 +317,26 @@ def select_camera_blocks(conv_mode, shapes, C):
     return conv_mode, _Direct16F16x3 if c16 else _WideWinogradF16x3
 
 
+PROJ_KERNELS = ('library', 'mfma')
+
+
+def select_proj_kernel(proj_kernel, default, K, cout):
+    """Resolved `proj_kernel` of a RenderLoopEngine whose factor projection is K = D * C -> cout (K = cout = None: the renderer
+    has no factor projection): None -> `default`; 'mfma' outside lf_rows_gemm_epi's domain is refused, never replaced by the
+    library GEMM.  Pure host logic (tests/test_rows_gemm_pack.py)."""
+    if proj_kernel is None:
+        proj_kernel = default
+    if proj_kernel not in PROJ_KERNELS:
+        raise ValueError(f'proj_kernel {proj_kernel!r}: one of {PROJ_KERNELS}')
+    if proj_kernel == 'mfma':
+        if K is None or cout is None:
+            raise NotImplementedError("proj_kernel 'mfma' needs the 'factor' projection")
+        if not (K >= 4 and K % 4 == 0 and 16 <= cout <= 256 and cout % 4 == 0):
+            raise NotImplementedError(f"proj_kernel 'mfma': lf_rows_gemm_epi takes K % 4 == 0 and 16 <= Cout <= 256, Cout % 4 == 0; "
+                                      f'this projection is K = {K}, Cout = {cout}')
+    return proj_kernel
+
+
 # What a tail forward (camera blocks' output -> projected latent) hands on: zp / pnorm: the projected latent and its PixelNorm
 # factors as buffers (explicit decoder, ranking latent term); feat: the same latent as the autograd decoder / latent term reads
 # it; leaf: the tensor autograd differentiates the 2-D part back to; occ_saved: what the explicit occlusion backward reads.
@@ -339,6 +359,8 @@ class RenderLoopEngine:
     EXPLICIT_DECODER = True          # A/B switch (tools/engine_ab.py): False runs a plain 2-D decoder through autograd like a generic one
     EXPLICIT_OCCLUSION = True        # A/B switch (tools/variant_probe.py): False runs the occlusion module through autograd
     PROJ_GEMM = True                 # wide blocks, ranking only: depth-innermost last block + library GEMM for the factor projection
+    PROJ_KERNEL = 'library'          # what the PROJ_GEMM branch launches when proj_kernel is None: 'library' (addmm + leaky_relu_ +
+                                     # lf_pixelnorm_fwd) or 'mfma' (lf_rows_gemm_epi, one launch)
 
     @staticmethod
     def supports(photographer, loss_weights):
@@ -355,7 +377,7 @@ class RenderLoopEngine:
     FUSE_FORMS = ('fwd',)
     _select_blocks = staticmethod(select_camera_blocks)
 
-    def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None):
+    def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None):
         """conv_mode selects the kernels of the 16->16 camera-block convolutions:
         'fp32'     direct implicit-GEMM on the fp32 MFMA (works for every channel count);
         'winograd' F(2x2x2,3x3x3) minimal filtering, all-fp32 arithmetic (fp32 MFMA + fp32 transforms);
@@ -367,6 +389,12 @@ class RenderLoopEngine:
         All stay within the fp32 kernel's distance of an fp64 reference (tests/test_engine_gpu.py).
         fuse_projection: None = the default (factor projection forward fused into the last block's Winograd launch where the
         shapes allow), False = two launches, ('fwd',) = required.
+        proj_kernel: what the factor projection of a ranking call on wide blocks (PROJ_GEMM) launches: 'library' = the library
+        GEMM + leaky_relu_ + lf_pixelnorm_fwd, 'mfma' = lf_rows_gemm_epi (one launch, fixed K order, no library GEMM on the
+        path); None = PROJ_KERNEL.  'mfma' on a projection outside that kernel's domain raises NotImplementedError.
+        The option only chooses what that branch launches: on 16-channel blocks, the 'sum' projection's or the occlusion
+        module's tail, and on calls with need_grad=True the branch does not run and the option is idle (no pack is built;
+        `proj_rows_pack` is None).
         (Measured-and-rejected variants -- three-term Winograd products, the fused projection backward, hypothesis groups on
         several streams, hipGraph replay -- live in experimental.RenderLoopEngineX.)"""
         self.ph = photographer
@@ -399,7 +427,11 @@ class RenderLoopEngine:
             self.occ = self._plan_occlusion(photographer.occlusion_module)
         cout, pw = C, None
         self.proj = None
-        if photographer.projection_type == 'factor':
+        factor = photographer.projection_type == 'factor'
+        self.proj_kernel = select_proj_kernel(proj_kernel, self.PROJ_KERNEL, D * C if factor else None,
+                                              photographer.projection_block.conv.module.weight.shape[0] if factor else None)
+        self.proj_rows_pack = None
+        if factor:
             pw = photographer.projection_block.conv.module.weight
             cout = pw.shape[0]
             # [D*C][cout], K = d*C + c: the projection as one row-major GEMM over depth-innermost rows (PROJ_GEMM)
@@ -428,6 +460,9 @@ class RenderLoopEngine:
         if 'fwd' in self.fuse_projection:
             self.plan.ride_projection(self.proj_fused[0], self.proj[1], self.proj[2])
         self._wide_factor = self.plan.wide and not self.generic_tail          # (where PROJ_GEMM applies to a ranking call)
+        if self.proj_kernel == 'mfma' and self._wide_factor:
+            # the matrix of proj_rows_t as [cout][K] rows, as lf_rows_gemm_epi reads it (only where that branch can run)
+            self.proj_rows_pack = ops.pack_rows_gemm(pw.detach().reshape(cout, C, D).permute(0, 2, 1).reshape(cout, D * C))
         self.dev = dev
         self._params = list(photographer.parameters())
         self._intr = None                                            # (K, version, gathered): the intrinsics do not change during a loop
@@ -763,13 +798,17 @@ class RenderLoopEngine:
         return gp if gp is not None else ops._epilogue_bwd(ops.cl(g_leaf), tail.zp, tail.pnorm, flags)
 
     def _factor_fwd(self, act, rode, flags, need_grad, proj_gemm, n):
-        """The plain factor projection: ridden along in the last block's launch, the library GEMM of a ranking call on wide blocks,
-        or its own launch."""
+        """The plain factor projection: ridden along in the last block's launch, the row-major GEMM of a ranking call on wide
+        blocks (self.proj_kernel: the library's, or lf_rows_gemm_epi with the epilogue in its store), or its own launch."""
         L = _lib.lib()
         pw, pb, phe, ppack, _ppack_t = self.proj
         cout, S, Cl = pw.shape[0], self.S, self.Cl
         if rode:
             zp, pnorm = rode
+        elif proj_gemm and self.proj_kernel == 'mfma':
+            rows, pnorm = ops.rows_gemm_epilogue(act.view(n * S * S, S * Cl), self.proj_rows_pack, pb, phe, cout, flags,
+                                                 tag='factor_project_fwd')
+            zp = rows.view(n, S, S, cout).permute(0, 3, 1, 2)                # channels-last (n, cout, S, S)
         elif proj_gemm:
             with ops._timed('factor_project_fwd'):
                 x2 = act.view(n * S * S, S * Cl)

@@ -78,7 +78,7 @@ class MultiTargetEngine(RenderLoopEngine):
 
     MAX_ROWS = 65535
 
-    def __init__(self, photographer, z_obj, targets, loss_weights, conv_mode='auto', fuse_projection=None):
+    def __init__(self, photographer, z_obj, targets, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None):
         targets = list(targets)
         if not targets:
             raise ValueError('MultiTargetEngine needs at least one target')
@@ -97,7 +97,8 @@ class MultiTargetEngine(RenderLoopEngine):
         if isinstance(z_obj, (list, tuple)):
             vols, index = distinct_volumes(check_volumes(z_obj, len(targets)))
             z_obj = vols[0]
-        super().__init__(photographer, z_obj, targets[0], loss_weights, conv_mode=conv_mode, fuse_projection=fuse_projection)
+        super().__init__(photographer, z_obj, targets[0], loss_weights, conv_mode=conv_mode, fuse_projection=fuse_projection,
+                         proj_kernel=proj_kernel)
         dev = self.dev
         # several objects: the distinct volumes back to back [K][S][S][S][C], self.z the first of them (a view: no second copy)
         self.zs = self.vol_of = None

@@ -228,6 +228,18 @@ def pack_conv1x1(weight2d):
     return out.contiguous()
 
 
+def pack_rows_gemm(weight2d):
+    """[Cout,K] -> [CoutP][K] row-major, rows Cout.. zero (lf_rows_gemm_epi layout; CoutP = lf_rows_gemm_cout_padded(Cout))."""
+    L = _lib.lib()
+    cout, k = weight2d.shape
+    coutp = L.lf_rows_gemm_cout_padded(cout)
+    if coutp == 0 or cout < 16 or cout % 4 or k < 4 or k % 4:
+        raise ValueError(f'lf_rows_gemm_epi takes 16 <= Cout <= 256, Cout % 4 == 0, K >= 4, K % 4 == 0: got Cout {cout}, K {k}')
+    out = torch.zeros(coutp, k, device=weight2d.device, dtype=torch.float32)
+    out[:cout] = weight2d.detach()
+    return out.contiguous()
+
+
 def amax_buffer(value=None, device='cuda', rows=1):
     """Zeroed max-abs side-channel buffer(s) (rows x LF_AMAX_FLOATS); `value` (a tensor) pre-loads slot 0 of
     row 0, e.g. a maximum computed on the host side of the ABI."""
@@ -923,6 +935,31 @@ def _conv1x1_raw(x_ptr_tensor, wpack, bias, N, P, cin, ksl, xbs, xss, cout, y2d,
     if (flags & LF_EPI_PIXELNORM) and not fuse_pn:
         check(L.lf_pixelnorm_fwd(_ptr(y2d), _ptr(y2d), _ptr(norm), N * P, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
     return norm
+
+
+def rows_gemm_epilogue(x2, wpack, bias, he, cout, flags=LF_EPI_LRELU | LF_EPI_PIXELNORM, tag='rows_gemm_epi'):
+    """y = epilogue(he * x2 @ W^T + bias) over the rows of x2 [M][K] in ONE launch (lf_rows_gemm_epi; wpack = pack_rows_gemm(W)):
+    -> (y [M][cout], norm [M] or None without LF_EPI_PIXELNORM).  Forward only, no autograd: the ranking path's factor
+    projection (engine.RenderLoopEngine, proj_kernel='mfma', which times it under its own stage `tag`)."""
+    L = _lib.lib()
+    _req(x2, 'x2')
+    _req(wpack, 'wpack')
+    if x2.dim() != 2 or not x2.is_contiguous():
+        raise ValueError('x2 must be a contiguous [M][K] matrix')
+    M, K = x2.shape
+    if wpack.dim() != 2 or not wpack.is_contiguous() or tuple(wpack.shape) != (L.lf_rows_gemm_cout_padded(cout), K):
+        raise ValueError(f'wpack {tuple(wpack.shape)} is not pack_rows_gemm of a [{cout}][{K}] weight')
+    if bias is not None:
+        bias = _req(bias.detach(), 'bias').contiguous()
+        if bias.numel() != cout:
+            raise ValueError('bias must hold Cout values')
+    y = torch.empty(M, cout, device=x2.device, dtype=torch.float32)
+    norm = torch.empty(M, device=x2.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
+    with _timed(tag, f'{M}x{K}x{cout}'):
+        check(L.lf_rows_gemm_epi(_ptr(x2), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y),
+                                 _ptr(norm) if norm is not None else None, M, K, cout, he, flags, SLOPE, PN_EPS, _stream()),
+              'lf_rows_gemm_epi')
+    return y, norm
 
 
 class _Conv1x1(torch.autograd.Function):

@@ -65,16 +65,22 @@ def load_schedules_from_config(config):
 
 class PoseEstimator:
     def __init__(self, *, model, ranking_size, loss_weights, loss_func=None, return_camera_history=False,
-                 verbose=False, shard_hypotheses=False, use_engine=True, conv_mode='auto', fuse_projection=None):
+                 verbose=False, shard_hypotheses=False, use_engine=True, conv_mode='auto', fuse_projection=None,
+                 proj_kernel=None):
         """shard_hypotheses (an addition; the reference is single-process): under torch.distributed every rank
         renders and scores only its contiguous slice of the pose hypotheses; the per-hypothesis rows (loss
         [+ camera parameters]) are all-gathered once per iteration (parallel.gather_rows) and every rank ranks the
         full set, so the returned ranking is identical on all ranks and to a one-rank run.  Host-random draws
         (initial hypotheses, GMM samples) are taken from rank 0."""
         self.model = model
-        # use_engine / conv_mode / fuse_projection (additions): the fused render-and-score engine (engine.py) evaluates the
-        # hypotheses when the renderer and the loss are of the kind it sequences; False selects the generic module path
+        # use_engine / conv_mode / fuse_projection / proj_kernel (additions): the fused render-and-score engine (engine.py)
+        # evaluates the hypotheses when the renderer and the loss are of the kind it sequences; False selects the generic module
+        # path.  proj_kernel ('library' / 'mfma' / None = the engine's default): the ranking path's factor projection
+        from ..engine import PROJ_KERNELS
+        if proj_kernel is not None and proj_kernel not in PROJ_KERNELS:
+            raise ValueError(f'proj_kernel {proj_kernel!r}: one of {PROJ_KERNELS} or None')
         self.use_engine, self.conv_mode, self.fuse_projection = use_engine, conv_mode, fuse_projection
+        self.proj_kernel = proj_kernel
         self._engine_cache = None
         self.last_scored_on_engine = False
         self.shard_hypotheses = bool(shard_hypotheses)
@@ -158,8 +164,10 @@ class PoseEstimator:
                    or getattr(self, 'engine_streams', 1) > 1 or getattr(self, 'engine_graph', False))
         if wants_x:                                                # measured-and-rejected variants: experimental.py
             from ..experimental import RenderLoopEngineX
-            return RenderLoopEngineX(ph, z_obj, target_obs, self.loss_weights, conv_mode=self.conv_mode, fuse_projection=fp)
-        return RenderLoopEngine(ph, z_obj, target_obs, self.loss_weights, conv_mode=self.conv_mode, fuse_projection=fp)
+            return RenderLoopEngineX(ph, z_obj, target_obs, self.loss_weights, conv_mode=self.conv_mode, fuse_projection=fp,
+                                     proj_kernel=self.proj_kernel)
+        return RenderLoopEngine(ph, z_obj, target_obs, self.loss_weights, conv_mode=self.conv_mode, fuse_projection=fp,
+                                proj_kernel=self.proj_kernel)
 
     def _ranking_engine(self, z_obj, target_obs):
         """One engine per (object, target) for the ranking-only estimators; the cache keeps both alive, so an address
@@ -784,7 +792,8 @@ class GradientPoseEstimator(PoseEstimator):
                 for b, e in groups:                                  # (whole targets per group)
                     eng = MultiTargetEngine(self.model.photographer, z_obj if z_of is None else z_of[b:e], dev_targets[b:e],
                                             self.loss_weights,
-                                            conv_mode=self.conv_mode, fuse_projection=self.fuse_projection)
+                                            conv_mode=self.conv_mode, fuse_projection=self.fuse_projection,
+                                            proj_kernel=self.proj_kernel)
                     out += self._run_batch(eng, dev_targets[b:e], zoomed[b:e])
                     del eng
                 return out
