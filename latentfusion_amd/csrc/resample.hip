@@ -1,11 +1,10 @@
 // Camera <-> object voxel resampling for gfx950 (trilinear gather / coefficient-gradient
-// reduction / splat).  Replaces F.grid_sample(…, padding_mode='border', align_corners=False) of
+// reduction / float-atomic splat; the deterministic splat is splat.hip).  Replaces F.grid_sample(…, padding_mode='border', align_corners=False) of
 //   ObjectToCameraTransform.forward  latentfusion/modules/geometry.py:669-690
 //   CameraToObjectTransform.forward  latentfusion/modules/geometry.py:625-657
 // The sampling grid is evaluated per voxel from a per-sample coefficient block (see lf_hip.h);
 // volumes are channels-last so that every trilinear tap is one contiguous C-float record.
-#include "lf_common.h"
-#include <type_traits>
+#include "resample_map.h"
 
 namespace {
 
@@ -23,7 +22,6 @@ __device__ __forceinline__ float lattice01(int i, int size, float step) {
   return (i < size / 2) ? step * (float)i : 1.f - step * (float)(size - 1 - i);
 }
 
-struct Steps { float w, h, d; };                              // 1/(W-1), 1/(H-1), 1/(D-1) (0 for size 1)
 
 template <int KIND>
 __device__ __forceinline__ void eval_grid(const float* __restrict__ cf, int x, int y, int z,
@@ -205,7 +203,6 @@ __device__ __forceinline__ f32x4 ldrec(__amdgpu_buffer_rsrc_t rs, u32 off) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0));
 }
 
-typedef __bf16 bf16x4r __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
 template <bool B16>
 __device__ __forceinline__ f32x4 ldrec_t(__amdgpu_buffer_rsrc_t rs, u32 off) {
@@ -325,666 +322,6 @@ int g_bwd_coef_variant = 10;   // lean coefficient gradient: 1 = one sub-tile in
 int g_resample_variant = 3;   // 1 = generic kernels, 2 = lean kernels, 3 = lean + 16-channel gather, 4 = LDS-staged footprint (16 channels;
                               // other shapes as 3) (lf_set_tuning)
 
-// Sample evaluation for the deterministic splats with floating-point contraction OFF: every operation is rounded on its own,
-// so the kernels that must agree with each other -- the bounding-box pass and the tile pass of the tiled form (a corner voxel
-// outside its block's box would be dropped), and the tiled and the atomic form -- get the same corner indices, fractions and
-// weights no matter how the surrounding code is scheduled (with contraction on, the backend fuses multiply-adds per call site).
-struct SplatTap { int x0, y0, z0, x1, y1, z1; float w[8]; };     // w index = z*4 + y*2 + x
-
-template <int KIND>
-__device__ __forceinline__ SplatTap splat_eval(const float* __restrict__ cf, int x, int y, int z, int W, int H, int D, Steps st) {
-#pragma clang fp contract(off)
-  const float a = (x < W / 2) ? st.w * (float)x : 1.f - st.w * (float)(W - 1 - x);
-  const float b = (y < H / 2) ? st.h * (float)y : 1.f - st.h * (float)(H - 1 - y);
-  const float k = (z < D / 2) ? st.d * (float)z : 1.f - st.d * (float)(D - 1 - z);
-  float g[3];
-  if (KIND == LF_MAP_O2C) {
-    const float ak = a * k, bk = b * k;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) g[c] = ((((cf[c] + cf[3 + c] * a) + cf[6 + c] * b) + cf[9 + c] * k) + cf[12 + c] * ak) + cf[15 + c] * bk;
-  } else {
-    const float lx = 2.f * a - 1.f, ly = 2.f * b - 1.f, lz = 2.f * k - 1.f;
-    const float n0 = ((cf[0] * lx + cf[1] * ly) + cf[2] * lz) + cf[3];
-    const float n1 = ((cf[4] * lx + cf[5] * ly) + cf[6] * lz) + cf[7];
-    const float n2 = ((cf[8] * lx + cf[9] * ly) + cf[10] * lz) + cf[11];
-    const float dn = ((cf[12] * lx + cf[13] * ly) + cf[14] * lz) + cf[15];
-    g[0] = n0 / dn;
-    g[1] = n1 / dn;
-    g[2] = n2;
-  }
-  const int size[3] = {W, H, D};
-  int i0[3], i1[3];
-  float t[3];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    float p = ((g[c] + 1.f) * (float)size[c] - 1.f) * 0.5f;         // grid_sampler_unnormalize (align_corners=False)
-    p = fminf(fmaxf(p, 0.f), (float)(size[c] - 1));                 // border clip
-    if (!(p == p)) p = 0.f;                                         // NaN samples voxel 0 (ATen clip semantics)
-    const float f = floorf(p);
-    t[c] = p - f;
-    i0[c] = (int)f;
-    i1[c] = min(i0[c] + 1, size[c] - 1);
-  }
-  SplatTap s;
-  s.x0 = i0[0]; s.y0 = i0[1]; s.z0 = i0[2]; s.x1 = i1[0]; s.y1 = i1[1]; s.z1 = i1[2];
-  const float wx[2] = {1.f - t[0], t[0]}, wy[2] = {1.f - t[1], t[1]}, wz[2] = {1.f - t[2], t[2]};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s.w[i] = (wx[i & 1] * wy[(i >> 1) & 1]) * wz[i >> 2];
-  return s;
-}
-
-// The same evaluation shared by the four lanes of a quad that work on ONE sample (the binned tile pass: a lane quad per list entry,
-// round 6): lane q < 3 evaluates axis q -- its numerator, for the projective axes the denominator and the division, the un-normalise /
-// clip / floor chain -- lane 3 repeats axis 2; three quad broadcasts (v_mov_b32 dpp quad_perm) per value hand every lane all three
-// axes.  Every operation an axis sees is the one splat_eval performs for it, in the same order, contraction off: the same bits, for
-// about 55 % of the instructions (the evaluation was a quarter of the tile pass, profiles/r06_splat_ab.txt).
-template <int CTRL>
-__device__ __forceinline__ int quad_bcast_i(int v) { return __builtin_amdgcn_update_dpp(v, v, CTRL, 0xf, 0xf, false); }
-template <int CTRL>
-__device__ __forceinline__ float quad_bcast_f(float v) { return __int_as_float(quad_bcast_i<CTRL>(__float_as_int(v))); }
-
-template <int KIND>
-__device__ __forceinline__ SplatTap splat_eval_quad(const float* __restrict__ cf, int x, int y, int z, int W, int H, int D, Steps st, int q) {
-#pragma clang fp contract(off)
-  const float a = (x < W / 2) ? st.w * (float)x : 1.f - st.w * (float)(W - 1 - x);
-  const float b = (y < H / 2) ? st.h * (float)y : 1.f - st.h * (float)(H - 1 - y);
-  const float k = (z < D / 2) ? st.d * (float)z : 1.f - st.d * (float)(D - 1 - z);
-  const int c = q < 3 ? q : 2;                                     // this lane's axis
-  float g;
-  if (KIND == LF_MAP_O2C) {
-    const float ak = a * k, bk = b * k;
-    g = ((((cf[c] + cf[3 + c] * a) + cf[6 + c] * b) + cf[9 + c] * k) + cf[12 + c] * ak) + cf[15 + c] * bk;
-  } else {
-    const float lx = 2.f * a - 1.f, ly = 2.f * b - 1.f, lz = 2.f * k - 1.f;
-    const float num = ((cf[4 * c] * lx + cf[4 * c + 1] * ly) + cf[4 * c + 2] * lz) + cf[4 * c + 3];
-    const float dn = ((cf[12] * lx + cf[13] * ly) + cf[14] * lz) + cf[15];
-    g = c < 2 ? num / dn : num;
-  }
-  const int size = c == 0 ? W : (c == 1 ? H : D);
-  float p = ((g + 1.f) * (float)size - 1.f) * 0.5f;               // grid_sampler_unnormalize (align_corners=False)
-  p = fminf(fmaxf(p, 0.f), (float)(size - 1));                    // border clip
-  if (!(p == p)) p = 0.f;                                         // NaN samples voxel 0 (ATen clip semantics)
-  const float f = floorf(p);
-  const float tm = p - f;
-  const int i0m = (int)f;
-  const int i1m = min(i0m + 1, size - 1);
-  SplatTap s;
-  s.x0 = quad_bcast_i<0x00>(i0m); s.y0 = quad_bcast_i<0x55>(i0m); s.z0 = quad_bcast_i<0xaa>(i0m);
-  s.x1 = quad_bcast_i<0x00>(i1m); s.y1 = quad_bcast_i<0x55>(i1m); s.z1 = quad_bcast_i<0xaa>(i1m);
-  const float t0 = quad_bcast_f<0x00>(tm), t1 = quad_bcast_f<0x55>(tm), t2 = quad_bcast_f<0xaa>(tm);
-  const float wx[2] = {1.f - t0, t0}, wy[2] = {1.f - t1, t1}, wz[2] = {1.f - t2, t2};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) s.w[i] = (wx[i & 1] * wy[(i >> 1) & 1]) * wz[i >> 2];
-  return s;
-}
-
-// ---- deterministic splat: the same scatter, accumulated in 64-bit fixed point ----------------------------------
-// Float atomics make the result depend on the order in which the hardware retires them.  Integer addition is
-// associative, so accumulating round(contribution * 2^K) with 64-bit integer atomics gives bit-identical results
-// for every execution order; K is chosen from max|gout| so that 2^24 contributions (every output voxel of every
-// sample landing on ONE source voxel -- border clamping can do that) cannot overflow: the quantum is 2^-38 of the
-// largest gradient, finer than fp32's own resolution of any sum it could be added to.
-__global__ void __launch_bounds__(256) absmax_kernel(const float* __restrict__ x, long n, unsigned* __restrict__ out) {
-  float m = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) m = fmaxf(m, fabsf(x[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m > 0.f && m < 3.0e38f) atomicMax(out, __float_as_uint(m));   // max is order-independent
-}
-
-// (n a multiple of 16 and x 16-byte aligned: channels-last 16-channel records; a lane reads 8 values per load)
-__global__ void __launch_bounds__(256) absmax_bf16_kernel(const __bf16* __restrict__ x, long n, unsigned* __restrict__ out) {
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  float m = 0.f;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n / 8; i += (long)gridDim.x * 256) {
-    const u32x4 r = ((const u32x4*)x)[i];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {                                  // |bf16| as fp32: the 16 bits shifted into the high half, sign cleared
-      m = fmaxf(m, __uint_as_float((r[k] << 16) & 0x7fffffffu));
-      m = fmaxf(m, __uint_as_float(r[k] & 0x7fff0000u));
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m > 0.f && m < 3.0e38f) atomicMax(out, __float_as_uint(m));
-}
-
-__device__ __forceinline__ float fixed_scale(const unsigned* amax) {
-  const float am = __uint_as_float(*amax);
-  if (!(am > 0.f)) return 1.f;
-  int ex;
-  frexpf(am, &ex);                                               // am = m * 2^ex, m in [0.5, 1)
-  // |contribution| * scale < 2^38; the exponent is capped so that tiny gradients (max|g| < 2^-88) keep a FINITE scale
-  // (2^126: they then simply use fewer of the 64 bits) instead of inf * 0 = NaN
-  return ldexpf(1.f, min(38 - ex, 126));
-}
-
-// round-to-nearest-even of v (|v| < 2^39) as a 64-bit integer, in 8 VALU instructions instead of the ~20 of the generic
-// float -> int64 conversion (half of the tiled kernel's arithmetic): r = rint(v) is an integer-valued float; its value
-// splits exactly into hi * 2^24 + lo with lo in [0, 2^24), both exact in fp32 and in range of the 32-bit converts.
-#ifndef LF_FIXED_MAGIC
-#define LF_FIXED_MAGIC 1
-#endif
-__device__ __forceinline__ unsigned long long fixed_round(float v) {
-#if LF_FIXED_MAGIC
-  // round 6: the same integer in 3 instructions.  v is exact in fp64; adding 1.5 * 2^52 leaves a double in [2^52, 2^53) whose
-  // unit in the last place is 1, so the fp64 add itself rounds v to the nearest integer (ties to even, the mode of rintf) and
-  // the mantissa field then holds 2^51 + that integer.  Subtracting the bit pattern of the constant (its low word is zero: one
-  // 32-bit add on the high word) leaves the integer in two's complement.
-  const double d = (double)v + 6755399441055744.0;
-  return (unsigned long long)__double_as_longlong(d) - 0x4338000000000000ull;
-#endif
-  const float r = __builtin_rintf(v);
-  const float hi = __builtin_floorf(r * 5.9604644775390625e-08f);          // 2^-24
-  const float lo = __builtin_fmaf(hi, -16777216.f, r);
-  const int hi_i = (int)hi;
-  const unsigned lo_u = (unsigned)lo;
-  return ((unsigned long long)(unsigned)(hi_i >> 8) << 32) | (unsigned)(((unsigned)hi_i << 24) | lo_u);
-}
-
-template <int KIND>
-__global__ void __launch_bounds__(256) resample_bwd_vol_fixed_kernel(
-    const float* __restrict__ gout, const float* __restrict__ coef, unsigned long long* __restrict__ acc,
-    long acc_bstride, const unsigned* __restrict__ amax, int N, int D, int H, int W, int C, Steps st) {
-  const long per_sample = (long)D * H * W * C;
-  const int n = blockIdx.y;
-  const float* cf = coef + (long)n * LF_MAP_COEFS;
-  const float scale = fixed_scale(amax);
-  for (long idx = (long)blockIdx.x * blockDim.x + threadIdx.x; idx < per_sample; idx += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(idx % C);
-    long v = idx / C;
-    const int x = (int)(v % W); v /= W;
-    const int y = (int)(v % H);
-    const int z = (int)(v / H);
-    const SplatTap t = splat_eval<KIND>(cf, x, y, z, W, H, D, st);
-    const float go = gout[(long)n * per_sample + idx] * scale;   // exact: power-of-two scale
-    unsigned long long* base = acc + (long)n * acc_bstride + c;
-    const long sW = C, sH = (long)W * C, sD = (long)H * W * C;
-#define SPLAT(Z, Y, X, WI) atomicAdd(base + (Z) * sD + (Y) * sH + (X) * sW, (unsigned long long)__float2ll_rn(go * t.w[WI]))
-    SPLAT(t.z0, t.y0, t.x0, 0); SPLAT(t.z0, t.y0, t.x1, 1);
-    SPLAT(t.z0, t.y1, t.x0, 2); SPLAT(t.z0, t.y1, t.x1, 3);
-    SPLAT(t.z1, t.y0, t.x0, 4); SPLAT(t.z1, t.y0, t.x1, 5);
-    SPLAT(t.z1, t.y1, t.x0, 6); SPLAT(t.z1, t.y1, t.x1, 7);
-#undef SPLAT
-  }
-}
-
-__global__ void __launch_bounds__(256) fixed_to_float_kernel(const long long* __restrict__ acc, const unsigned* __restrict__ amax,
-                                                            float* __restrict__ out, long n) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  out[i] = (float)((double)acc[i] * (1.0 / (double)fixed_scale(amax)));   // (the scale is a power of two: its reciprocal is exact)
-}
-
-// ---- the same sums without global atomics (C == 16): every SOURCE tile is owned by one workgroup ---------------------
-// The fixed-point scatter above is bound by the L2's atomic units (2.1e9 64-bit atomics per 8 x 128^3 x 16 launch: 16-19 ms,
-// a quarter of a training step).  Integer addition being associative, the same totals can be formed in any grouping:
-//   pass 1  one wave per 4x4x4 block of OUTPUT voxels: bounding box of the (clamped) corner voxels its samples touch;
-//   pass 2  one workgroup per 4x8x8 tile of SOURCE voxels: 64-bit accumulators for the tile in LDS (32 KB); it culls the
-//           output blocks in two levels (boxes of 16^3 super-blocks, then the 64 block boxes of those that overlap; a
-//           ballot per 64 boxes, every wave redundantly: no exchange, no barriers), re-evaluates the
-//           samples of the blocks that touch it and adds the contributions that land inside the tile with LDS atomics;
-//           border clamping needs no special case (the boxes are boxes of clamped indices); with one volume shared by all
-//           samples (vol_n == 1) the workgroup walks all samples, so their contributions meet in the same accumulators;
-//           finally the tile is converted and written with plain stores.
-// Same quantisation, same integer totals, same conversion => bit-identical to the atomic kernel.
-constexpr int STZ = 4, STY = 8, STX = 8;                          // source tile owned by a workgroup: 256 voxels
-#ifndef SACC
-#define SACC 17                                                   // 64-bit accumulators per voxel record (16 + padding)
-#endif
-
-template <int KIND>
-__global__ void __launch_bounds__(256) splat_bbox_kernel(const float* __restrict__ coef, uint3* __restrict__ bbox, int nblk, int nbx,
-                                                         int nby, int D, int H, int W, Steps st) {
-  const int lane = threadIdx.x & 63;
-  const int blk = blockIdx.x * 4 + (threadIdx.x >> 6), n = blockIdx.y;
-  if (blk >= nblk) return;                                        // (wave-uniform)
-  const int bx = blk % nbx, by = (blk / nbx) % nby, bz = blk / (nbx * nby);
-  const int x = bx * 4 + (lane & 3), y = by * 4 + ((lane >> 2) & 3), z = bz * 4 + (lane >> 4);
-  const bool live = x < W && y < H && z < D;
-  const SplatTap t = splat_eval<KIND>(coef + (long)n * LF_MAP_COEFS, live ? x : 0, live ? y : 0, live ? z : 0, W, H, D, st);
-  int lo[3] = {live ? t.x0 : 0x7fff, live ? t.y0 : 0x7fff, live ? t.z0 : 0x7fff};
-  int hi[3] = {live ? t.x1 : -1, live ? t.y1 : -1, live ? t.z1 : -1};
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      lo[c] = min(lo[c], __shfl_xor(lo[c], o, 64));
-      hi[c] = max(hi[c], __shfl_xor(hi[c], o, 64));
-    }
-  if (lane == 0)                                                  // (an empty block: lo = 0x7fff > hi = 0xffff as signed 16 bit = -1)
-    bbox[(long)n * nblk + blk] = make_uint3((unsigned)lo[0] | ((unsigned)(hi[0] & 0xffff) << 16), (unsigned)lo[1] | ((unsigned)(hi[1] & 0xffff) << 16),
-                                            (unsigned)lo[2] | ((unsigned)(hi[2] & 0xffff) << 16));
-}
-
-// union of the boxes of the 4x4x4 blocks of a super-block (16^3 output voxels): one wave per super-block
-__global__ void __launch_bounds__(256) splat_bbox2_kernel(const uint3* __restrict__ bbox, uint3* __restrict__ sbox, int nblk, int nsb,
-                                                          int nbx, int nby, int nbz, int nsx, int nsy) {
-  const int lane = threadIdx.x & 63;
-  const int sb = blockIdx.x * 4 + (threadIdx.x >> 6), n = blockIdx.y;
-  if (sb >= nsb) return;                                          // (wave-uniform)
-  const int bx = (sb % nsx) * 4 + (lane & 3), by = ((sb / nsx) % nsy) * 4 + ((lane >> 2) & 3), bz = (sb / (nsx * nsy)) * 4 + (lane >> 4);
-  int lo[3] = {0x7fff, 0x7fff, 0x7fff}, hi[3] = {-1, -1, -1};
-  if (bx < nbx && by < nby && bz < nbz) {
-    const uint3 r = bbox[(long)n * nblk + ((long)bz * nby + by) * nbx + bx];
-    lo[0] = (short)(r.x & 0xffff); hi[0] = (short)(r.x >> 16);
-    lo[1] = (short)(r.y & 0xffff); hi[1] = (short)(r.y >> 16);
-    lo[2] = (short)(r.z & 0xffff); hi[2] = (short)(r.z >> 16);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      lo[c] = min(lo[c], __shfl_xor(lo[c], o, 64));
-      hi[c] = max(hi[c], __shfl_xor(hi[c], o, 64));
-    }
-  if (lane == 0)
-    sbox[(long)n * nsb + sb] = make_uint3((unsigned)(lo[0] & 0xffff) | ((unsigned)(hi[0] & 0xffff) << 16),
-                                          (unsigned)(lo[1] & 0xffff) | ((unsigned)(hi[1] & 0xffff) << 16),
-                                          (unsigned)(lo[2] & 0xffff) | ((unsigned)(hi[2] & 0xffff) << 16));
-}
-
-template <int KIND, int IO = 0>                                   // IO: bit 0 -- gout, bit 1 -- gvol stored as bf16 records
-__global__ void __launch_bounds__(256) splat_tile_kernel(const float* __restrict__ gout, const float* __restrict__ coef,
-                                                         const uint3* __restrict__ bbox, const uint3* __restrict__ sbox,
-                                                         const unsigned* __restrict__ amax, float* __restrict__ gvol, int vol_n, int N,
-                                                         int nblk, int nsb, int nbx, int nby, int nbz, int nsx, int nsy, int ntx, int nty,
-                                                         int D, int H, int W, Steps st) {
-  __shared__ unsigned long long acc[STZ * STY * STX * SACC];       // 34 KB: records padded to 17 (an 128-byte stride puts the
-                                                                   // 16 voxels of an atomic instruction on two sets of banks)
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int tile = blockIdx.x;
-  const int tx0 = (tile % ntx) * STX, ty0 = ((tile / ntx) % nty) * STY, tz0 = (tile / (ntx * nty)) * STZ;
-  for (int i = tid; i < STZ * STY * STX * SACC; i += 256) acc[i] = 0ull;
-  const float scale = fixed_scale(amax);
-  const long nvox = (long)D * H * W;
-  const int q = tid & 3, v = tid >> 2;                             // lane quad = one output voxel of the block, 4 channels each
-  const int px = v & 3, py = (v >> 2) & 3, pz = v >> 4;
-  const int n_first = vol_n == 1 ? 0 : blockIdx.y, n_last = vol_n == 1 ? N : blockIdx.y + 1;
-  auto overlaps = [&](const uint3 r) {
-    const int x0 = (short)(r.x & 0xffff), x1 = (short)(r.x >> 16), y0 = (short)(r.y & 0xffff), y1 = (short)(r.y >> 16),
-              z0 = (short)(r.z & 0xffff), z1 = (short)(r.z >> 16);
-    return x0 < tx0 + STX && x1 >= tx0 && y0 < ty0 + STY && y1 >= ty0 && z0 < tz0 + STZ && z1 >= tz0;
-  };
-  __syncthreads();
-  // Two-level culling, done redundantly by every wave (same data -> same masks -> same walk; no LDS exchange, no barriers:
-  // the LDS atomics commute): 64 super-block boxes per test, then the 64 block boxes of a super-block that overlaps the tile.
-  for (int n = n_first; n < n_last; ++n) {
-    const float* cf = coef + (long)n * LF_MAP_COEFS;
-    const float* gs = (const float*)((const char*)gout + (long)n * nvox * ((IO & 1) ? 32 : 64));
-    const uint3* bb = bbox + (long)n * nblk;
-    const uint3* sbb = sbox + (long)n * nsb;
-    for (int sbase = 0; sbase < nsb; sbase += 64) {
-      unsigned long long sm = __ballot(sbase + lane < nsb && overlaps(sbb[min(sbase + lane, nsb - 1)]));
-      while (sm) {
-        const int sbit = __builtin_ctzll(sm);
-        sm &= sm - 1;
-        const int sb = sbase + sbit;
-        const int cbx = (sb % nsx) * 4 + (lane & 3), cby = ((sb / nsx) % nsy) * 4 + ((lane >> 2) & 3), cbz = (sb / (nsx * nsy)) * 4 + (lane >> 4);
-        const bool cok = cbx < nbx && cby < nby && cbz < nbz;
-        const long cid = ((long)cbz * nby + cby) * nbx + cbx;
-        unsigned long long cm = __ballot(cok && overlaps(bb[cok ? cid : 0]));
-        while (cm) {
-          const int cbit = __builtin_ctzll(cm);
-          cm &= cm - 1;
-          const int bx = (sb % nsx) * 4 + (cbit & 3), by = ((sb / nsx) % nsy) * 4 + ((cbit >> 2) & 3), bz = (sb / (nsx * nsy)) * 4 + (cbit >> 4);
-          const int x = bx * 4 + px, y = by * 4 + py, z = bz * 4 + pz;
-          if (x < W && y < H && z < D) {
-            const SplatTap t = splat_eval<KIND>(cf, x, y, z, W, H, D, st);
-            f32x4 g4;
-            if constexpr ((IO & 1) != 0)
-              g4 = __builtin_convertvector(*(const bf16x4r*)((const char*)gs + (((long)z * H + y) * W + x) * 32 + q * 8), f32x4);
-            else
-              g4 = *(const f32x4*)(gs + (((long)z * H + y) * W + x) * 16 + q * 4);
-#define SPLAT_T(Z, Y, X, WI) do { \
-              const int lz_ = (Z) - tz0, ly_ = (Y) - ty0, lx_ = (X) - tx0; \
-              if ((unsigned)lz_ < (unsigned)STZ && (unsigned)ly_ < (unsigned)STY && (unsigned)lx_ < (unsigned)STX) { \
-                unsigned long long* d_ = acc + ((lz_ * STY + ly_) * STX + lx_) * SACC + q * 4; \
-                _Pragma("unroll") for (int e = 0; e < 4; ++e) atomicAdd(d_ + e, fixed_round((g4[e] * scale) * t.w[WI])); \
-              } } while (0)
-            SPLAT_T(t.z0, t.y0, t.x0, 0); SPLAT_T(t.z0, t.y0, t.x1, 1);
-            SPLAT_T(t.z0, t.y1, t.x0, 2); SPLAT_T(t.z0, t.y1, t.x1, 3);
-            SPLAT_T(t.z1, t.y0, t.x0, 4); SPLAT_T(t.z1, t.y0, t.x1, 5);
-            SPLAT_T(t.z1, t.y1, t.x0, 6); SPLAT_T(t.z1, t.y1, t.x1, 7);
-#undef SPLAT_T
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  // the tile: one thread per voxel, 16 channels = 4 float4 stores
-  const int lx = tid % STX, ly = (tid / STX) % STY, lz = tid / (STX * STY);
-  const int x = tx0 + lx, y = ty0 + ly, z = tz0 + lz;
-  if (x < W && y < H && z < D) {
-    constexpr int OREC = (IO & 2) ? 32 : 64;
-    char* dst = (char*)gvol + ((vol_n == 1 ? 0 : (long)blockIdx.y * nvox) + (((long)z * H + y) * W + x)) * OREC;
-    const double inv = 1.0 / (double)scale;                       // exact: the scale is a power of two (2^-90 .. 2^126)
-#pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4) {
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (float)((double)(long long)acc[tid * SACC + c4 * 4 + e] * inv);
-      if constexpr ((IO & 2) != 0) *(bf16x4r*)(dst + c4 * 8) = __builtin_convertvector(o, bf16x4r);
-      else *(f32x4*)(dst + c4 * 16) = o;
-    }
-  }
-}
-
-// ---- binned form of the same sums (round 5: the camera -> object splat of the training step, a volume per sample, and the
-// object -> camera one, all samples into one volume).  The tile form above finds the output voxels that touch a source tile by culling boxes: at 128^3 a workgroup
-// walks 512 super-block boxes and then re-evaluates 40-75 blocks of 64 samples of which a tenth lands in its tile (12.4 ms for
-// 32 views, the largest kernel of the step).  Here the output voxels are BINNED by the source tiles their corners touch first
-// (count, scan, fill: 1.6 list entries per voxel on average, 8 at most), and a tile's workgroup evaluates exactly its list:
-//   bin<FILL = false>  per output voxel: the <= 8 distinct tiles of its corner voxels, one wave-aggregated atomic add per tile
-//                      and wave on the tile's counter;
-//   scan               exclusive prefix of a sample's tile counters;
-//   bin<FILL = true>   the same walk, now storing the voxel (z << 20 | y << 10 | x) at offset[tile] + slot;
-//   binned tile        64-bit LDS accumulators as above, one LANE per list entry (all 16 channels), conversion and store as above.
-// The order of a list depends on the atomics; the integer sums do not: bit-identical to the other two forms.
-template <int KIND, bool FILL>
-__global__ void __launch_bounds__(256) splat_bin_kernel(const float* __restrict__ coef, unsigned* __restrict__ cnt,
-                                                        const unsigned* __restrict__ off, unsigned* __restrict__ list, int n0, long nvox,
-                                                        long cap, int ntiles, int ntx, int nty, int D, int H, int W, Steps st) {
-  const int lane = threadIdx.x & 63;
-  const int nl = blockIdx.y;                                       // sample within the chunk
-  // a wave takes a 4x4x4 block of output voxels: its samples land in one or two tiles per axis (a row of 64 voxels would
-  // cross four to eight), so the aggregation loop below runs once or twice per corner combination
-  const int nbx = (W + 3) >> 2, nby = (H + 3) >> 2, nbz = (D + 3) >> 2;
-  const long blk = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const bool wave_live = blk < (long)nbx * nby * nbz;
-  const long bq = wave_live ? blk : 0;
-  const int x = (int)(bq % nbx) * 4 + (lane & 3), y = (int)((bq / nbx) % nby) * 4 + ((lane >> 2) & 3), z = (int)(bq / ((long)nbx * nby)) * 4 + (lane >> 4);
-  const bool live = wave_live && x < W && y < H && z < D;
-  const SplatTap t = splat_eval<KIND>(coef + (long)(n0 + nl) * LF_MAP_COEFS, min(x, W - 1), min(y, H - 1), min(z, D - 1), W, H, D, st);
-  const int tx[2] = {t.x0 / STX, t.x1 / STX}, ty[2] = {t.y0 / STY, t.y1 / STY}, tz[2] = {t.z0 / STZ, t.z1 / STZ};
-  unsigned* c = cnt + (long)nl * ntiles;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int kx = k & 1, ky = (k >> 1) & 1, kz = k >> 2;
-    // a combination is a NEW tile iff every axis it takes the upper corner on really changes tile there
-    const bool act = live && (!kx || tx[1] != tx[0]) && (!ky || ty[1] != ty[0]) && (!kz || tz[1] != tz[0]);
-    const int tile = (tz[kz] * nty + ty[ky]) * ntx + tx[kx];
-    unsigned long long todo = __ballot(act);
-    while (todo) {                                                 // (wave-uniform loop: one atomic per distinct tile and wave)
-      const int leader = __builtin_ctzll(todo);
-      const int lt = __shfl(tile, leader, 64);
-      const unsigned long long same = __ballot(act && tile == lt);
-      unsigned base = 0;
-      if (lane == leader) base = atomicAdd(c + lt, (unsigned)__builtin_popcountll(same));
-      if (FILL) {
-        base = __shfl(base, leader, 64);
-        if (act && tile == lt) {
-          const unsigned slot = base + (unsigned)__builtin_popcountll(same & ((1ull << lane) - 1ull));
-          list[(long)nl * cap + off[(long)nl * ntiles + lt] + slot] = ((unsigned)z << 20) | ((unsigned)y << 10) | (unsigned)x;
-        }
-      }
-      todo &= ~same;
-    }
-  }
-}
-
-// exclusive prefix sums of each sample's tile counters (one workgroup per sample)
-__global__ void __launch_bounds__(256) splat_scan_kernel(const unsigned* __restrict__ cnt, unsigned* __restrict__ off, int ntiles) {
-  __shared__ unsigned part[256];
-  const unsigned* c = cnt + (long)blockIdx.x * ntiles;
-  unsigned* o = off + (long)blockIdx.x * ntiles;
-  const int per = (ntiles + 255) / 256, b = threadIdx.x * per, e = min(b + per, ntiles);
-  unsigned sum = 0;
-  for (int i = b; i < e; ++i) sum += c[i];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned run = 0;
-    for (int i = 0; i < 256; ++i) { const unsigned p = part[i]; part[i] = run; run += p; }
-  }
-  __syncthreads();
-  unsigned run = part[threadIdx.x];
-  for (int i = b; i < e; ++i) { o[i] = run; run += c[i]; }
-}
-
-// threads per source tile: 512 = eight waves share the tile's accumulators, 32 waves per CU at four resident workgroups (LDS-bound
-// residency): 2.39 -> 2.34 ms (training geometry), 2.06 -> 1.93 ms (one shared volume), 3.25 -> 3.14 ms (wide) against 256
-#ifndef SBT_THREADS
-#define SBT_THREADS 512
-#endif
-template <int KIND, int IO>
-__global__ void __launch_bounds__(SBT_THREADS) splat_binned_tile_kernel(const float* __restrict__ gout, const float* __restrict__ coef,
-                                                                const unsigned* __restrict__ cnt, const unsigned* __restrict__ off,
-                                                                const unsigned* __restrict__ list, const unsigned* __restrict__ amax,
-                                                                float* __restrict__ gvol, int n0, int m, int shared, long nvox, long cap,
-                                                                int ntiles, int ntx, int nty, int D, int H, int W, Steps st) {
-  __shared__ unsigned long long acc[STZ * STY * STX * SACC];
-  const int tid = threadIdx.x;
-  const int tile = blockIdx.x;
-  // a volume per sample: blockIdx.y is the sample; one volume shared by the m samples: the workgroup walks their m lists
-  const int nl_first = shared ? 0 : (int)blockIdx.y, nl_last = shared ? m : (int)blockIdx.y + 1;
-  const long n_out = shared ? 0 : n0 + (long)blockIdx.y;
-  const int tx0 = (tile % ntx) * STX, ty0 = ((tile / ntx) % nty) * STY, tz0 = (tile / (ntx * nty)) * STZ;
-  unsigned total = 0;
-  for (int nl = nl_first; nl < nl_last; ++nl) total |= cnt[(long)nl * ntiles + tile];
-  if (total == 0) {
-    if (tid >= STZ * STY * STX) return;                            // nothing lands here (more than half of the camera volume's tiles
-    const int lx = tid % STX, ly = (tid / STX) % STY, lz = tid / (STX * STY);   // when the object fills part of it): zeros, no LDS pass
-    const int x = tx0 + lx, y = ty0 + ly, z = tz0 + lz;
-    if (x < W && y < H && z < D) {
-      constexpr int OREC = (IO & 2) ? 32 : 64;
-      f32x4* dst = (f32x4*)((char*)gvol + (n_out * nvox + (((long)z * H + y) * W + x)) * OREC);
-#pragma unroll
-      for (int k = 0; k < OREC / 16; ++k) dst[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    return;
-  }
-  for (int i = tid; i < STZ * STY * STX * SACC; i += SBT_THREADS) acc[i] = 0ull;
-  const float scale = fixed_scale(amax);
-  __syncthreads();
-  // a lane quad per list entry, four channels each (as the tile form: the lanes of one atomic instruction then spread over 16
-  // records x 4 slots; one lane per entry measured 2.7x slower -- clamped samples pile up on border voxels and 64 lanes on one
-  // address serialise); corners of weight zero (the far corner on an axis a sample was clamped on) add nothing and are skipped
-  const int q = tid & 3;
-  for (int nl = nl_first; nl < nl_last; ++nl) {
-    const float* cf = coef + (long)(n0 + nl) * LF_MAP_COEFS;
-    const char* gs = (const char*)gout + (long)(n0 + nl) * nvox * ((IO & 1) ? 32 : 64);
-    const unsigned count = cnt[(long)nl * ntiles + tile];
-    const unsigned* mine = list + (long)nl * cap + off[(long)nl * ntiles + tile];
-    // two list entries ahead, one gradient record ahead (round 6): the chain list word -> record address -> record is two HBM / L2
-    // latencies long and a workgroup holds only four waves; with the loads of the next entries in flight behind the arithmetic of
-    // this one the pass is no longer latency-bound (tools/splat_ab.py)
-    typedef typename std::conditional<(IO & 1) != 0, bf16x4r, f32x4>::type graw_t;
-    auto g_of = [&](unsigned pk_) -> graw_t {
-      const long v_ = ((long)(pk_ >> 20) * H + (long)((pk_ >> 10) & 1023u)) * W + (long)(pk_ & 1023u);
-      return *(const graw_t*)(gs + v_ * ((IO & 1) ? 32 : 64) + q * ((IO & 1) ? 8 : 16));
-    };
-    const unsigned i0 = tid >> 2;
-    unsigned pk1 = i0 < count ? mine[i0] : 0u, pk2 = i0 + SBT_THREADS / 4 < count ? mine[i0 + SBT_THREADS / 4] : 0u;
-    graw_t gnext = g_of(pk1);
-    constexpr unsigned EPI = SBT_THREADS / 4;                      // entries per iteration of the workgroup
-    for (unsigned i = i0; i < count; i += EPI) {
-      const unsigned pk = pk1;                                      // z << 20 | y << 10 | x
-      const graw_t graw = gnext;
-      pk1 = pk2;
-      if (i + EPI < count) gnext = g_of(pk1);
-      pk2 = i + 2 * EPI < count ? mine[i + 2 * EPI] : 0u;
-      const int x = (int)(pk & 1023u), y = (int)((pk >> 10) & 1023u), z = (int)(pk >> 20);
-      const SplatTap t = splat_eval_quad<KIND>(cf, x, y, z, W, H, D, st, q);   // (the quad's lanes are all live or all past the list's end)
-      f32x4 g4;
-      if constexpr ((IO & 1) != 0) g4 = __builtin_convertvector(graw, f32x4);
-      else g4 = graw;
-      g4 = g4 * scale;
-#define SPLAT_B(Z, Y, X, WI) do { \
-        const int lz_ = (Z) - tz0, ly_ = (Y) - ty0, lx_ = (X) - tx0; \
-        if (t.w[WI] != 0.f && (unsigned)lz_ < (unsigned)STZ && (unsigned)ly_ < (unsigned)STY && (unsigned)lx_ < (unsigned)STX) { \
-          unsigned long long* d_ = acc + ((lz_ * STY + ly_) * STX + lx_) * SACC + q * 4; \
-          _Pragma("unroll") for (int e = 0; e < 4; ++e) atomicAdd(d_ + e, fixed_round(g4[e] * t.w[WI])); \
-        } } while (0)
-      SPLAT_B(t.z0, t.y0, t.x0, 0); SPLAT_B(t.z0, t.y0, t.x1, 1);
-      SPLAT_B(t.z0, t.y1, t.x0, 2); SPLAT_B(t.z0, t.y1, t.x1, 3);
-      SPLAT_B(t.z1, t.y0, t.x0, 4); SPLAT_B(t.z1, t.y0, t.x1, 5);
-      SPLAT_B(t.z1, t.y1, t.x0, 6); SPLAT_B(t.z1, t.y1, t.x1, 7);
-#undef SPLAT_B
-    }
-  }
-  __syncthreads();
-  const int lx = tid % STX, ly = (tid / STX) % STY, lz = tid / (STX * STY);
-  const int x = tx0 + lx, y = ty0 + ly, z = tz0 + lz;
-  if (tid < STZ * STY * STX && x < W && y < H && z < D) {
-    constexpr int OREC = (IO & 2) ? 32 : 64;
-    char* dst = (char*)gvol + (n_out * nvox + (((long)z * H + y) * W + x)) * OREC;
-    const double inv = 1.0 / (double)scale;                       // exact: the scale is a power of two (2^-90 .. 2^126)
-#pragma unroll
-    for (int c4 = 0; c4 < 4; ++c4) {
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (float)((double)(long long)acc[tid * SACC + c4 * 4 + e] * inv);
-      if constexpr ((IO & 2) != 0) *(bf16x4r*)(dst + c4 * 8) = __builtin_convertvector(o, bf16x4r);
-      else *(f32x4*)(dst + c4 * 16) = o;
-    }
-  }
-}
-
-// ---- round 6 A/B (NOT the default: lf_set_tuning(4, 4)): the binned tile pass with ONE LANE PER CHANNEL (16 lanes per entry) ------
-// tools/ub/lds_atomic2.hip: 64-bit LDS atomics retire at 8-9 lane-atomics per clock and CU whatever the shape of the access -- as
-// long as the lanes of one instruction do not meet on an address.  The quad-per-entry form above puts 16 list entries into one
-// instruction; neighbouring entries come from one 4x4x4 block of output voxels and land on the same few source voxels, clamped
-// samples pile up on border records: on ONE record it falls to 2.0 per clock.  With 16 lanes per entry an instruction covers
-// 4 entries x 128 contiguous bytes, which the LDS serves at 8.0 per clock even when all four are the SAME record.  To keep the
-// arithmetic per entry from growing 4x with the lanes, a wave works in two phases per 64 entries: (A) lane-per-entry: list word,
-// the sample's gradient record, splat_eval, in-tile test -> a table in LDS (8 weights, 8 record numbers or 0xffff, the record);
-// (B) 16 lanes per entry read their entry's row (broadcast reads) and issue the 8 adds.  Same quantisation, same integer totals,
-// same conversion => bit-identical to the other forms.
-// MEASURED (profiles/r06_splat_ab.txt, 8 x 128^3 x 16, training geometry): 2.82 ms against 2.50 ms of the quad form before its
-// loads were pipelined (2.36 after).  Ablations of THIS kernel: without the atomics -0.30 ms, without splat_eval -0.42 ms, without
-// the conversion -0.07 ms of 1.9 ms: the atomics were never the bound -- the dependent loads (list word -> record) and the
-// per-entry arithmetic at four waves per workgroup are; which is what the pipelined loads in the quad form address.
-template <int KIND, int IO>
-__global__ void __launch_bounds__(256) splat_binned_tile16_kernel(const float* __restrict__ gout, const float* __restrict__ coef,
-                                                                  const unsigned* __restrict__ cnt, const unsigned* __restrict__ off,
-                                                                  const unsigned* __restrict__ list, const unsigned* __restrict__ amax,
-                                                                  float* __restrict__ gvol, int n0, int m, int shared, long nvox, long cap,
-                                                                  int ntiles, int ntx, int nty, int D, int H, int W, Steps st) {
-  constexpr bool IN16 = (IO & 1) != 0, OUT16 = (IO & 2) != 0;
-  constexpr int NREC = STZ * STY * STX, GREC = IN16 ? 32 : 64;
-  typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-  __shared__ unsigned long long acc[NREC * 16];                    // 32 KB: record stride 128 B (the shape is conflict-free as it is)
-  __shared__ __attribute__((aligned(16))) float tw[4][64][8];      // per wave and entry: the 8 corner weights
-  __shared__ __attribute__((aligned(16))) unsigned short tr[4][64][8];   // the 8 records (0xffff: outside the tile or weight zero)
-  __shared__ __attribute__((aligned(16))) unsigned char tg[4][64][GREC]; // the sample's 16-channel gradient record as stored
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, grp = lane >> 4, ch = lane & 15;
-  const int tile = blockIdx.x;
-  const int nl_first = shared ? 0 : (int)blockIdx.y, nl_last = shared ? m : (int)blockIdx.y + 1;
-  const long n_out = shared ? 0 : n0 + (long)blockIdx.y;
-  const int tx0 = (tile % ntx) * STX, ty0 = ((tile / ntx) % nty) * STY, tz0 = (tile / (ntx * nty)) * STZ;
-  constexpr int OREC = OUT16 ? 32 : 64;
-  unsigned total = 0;
-  for (int nl = nl_first; nl < nl_last; ++nl) total |= cnt[(long)nl * ntiles + tile];
-  if (total == 0) {
-    const int lx = tid % STX, ly = (tid / STX) % STY, lz = tid / (STX * STY);
-    const int x = tx0 + lx, y = ty0 + ly, z = tz0 + lz;
-    if (x < W && y < H && z < D) {
-      f32x4* dst = (f32x4*)((char*)gvol + (n_out * nvox + (((long)z * H + y) * W + x)) * OREC);
-#pragma unroll
-      for (int k = 0; k < OREC / 16; ++k) dst[k] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-    return;
-  }
-  for (int i = tid; i < NREC * 16; i += 256) acc[i] = 0ull;
-  const float scale = fixed_scale(amax);
-  __syncthreads();
-  for (int nl = nl_first; nl < nl_last; ++nl) {
-    const float* cf = coef + (long)(n0 + nl) * LF_MAP_COEFS;
-    const char* gs = (const char*)gout + (long)(n0 + nl) * nvox * GREC;
-    const unsigned count = cnt[(long)nl * ntiles + tile];
-    const unsigned* mine = list + (long)nl * cap + off[(long)nl * ntiles + tile];
-    for (unsigned b0 = (unsigned)wv * 64u; b0 < count; b0 += 256u) {
-      // ---- phase A: lane = list entry
-      if (b0 + lane < count) {
-        const unsigned pk = mine[b0 + lane];                        // z << 20 | y << 10 | x
-        const int x = (int)(pk & 1023u), y = (int)((pk >> 10) & 1023u), z = (int)(pk >> 20);
-        const u32x4* src = (const u32x4*)(gs + (((long)z * H + y) * W + x) * GREC);
-        u32x4 rec[GREC / 16];
-#pragma unroll
-        for (int k = 0; k < GREC / 16; ++k) rec[k] = src[k];
-        const SplatTap t = splat_eval<KIND>(cf, x, y, z, W, H, D, st);
-        const int lz[2] = {t.z0 - tz0, t.z1 - tz0}, ly[2] = {t.y0 - ty0, t.y1 - ty0}, lx[2] = {t.x0 - tx0, t.x1 - tx0};
-        unsigned r16[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-          const int cz = lz[c >> 2], cy = ly[(c >> 1) & 1], cx = lx[c & 1];
-          const bool in = t.w[c] != 0.f && (unsigned)cz < (unsigned)STZ && (unsigned)cy < (unsigned)STY && (unsigned)cx < (unsigned)STX;
-          r16[c] = in ? (unsigned)((cz * STY + cy) * STX + cx) : 0xffffu;
-        }
-        *(f32x4*)&tw[wv][lane][0] = (f32x4){t.w[0], t.w[1], t.w[2], t.w[3]};
-        *(f32x4*)&tw[wv][lane][4] = (f32x4){t.w[4], t.w[5], t.w[6], t.w[7]};
-        *(u32x4*)&tr[wv][lane][0] = (u32x4){r16[0] | (r16[1] << 16), r16[2] | (r16[3] << 16), r16[4] | (r16[5] << 16), r16[6] | (r16[7] << 16)};
-#pragma unroll
-        for (int k = 0; k < GREC / 16; ++k) *(u32x4*)&tg[wv][lane][k * 16] = rec[k];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      // ---- phase B: 16 lanes = the channels of one entry, four entries per instruction
-      const int nb = (int)min(64u, count - b0);
-#pragma unroll 4
-      for (int j = 0; j < 16; ++j) {
-        const int e = j * 4 + grp;
-        if (e < nb) {
-          const f32x4 w0 = *(const f32x4*)&tw[wv][e][0], w1 = *(const f32x4*)&tw[wv][e][4];
-          const u32x4 r4 = *(const u32x4*)&tr[wv][e][0];
-          float g;
-          if constexpr (IN16) g = __uint_as_float((unsigned)(*(const unsigned short*)&tg[wv][e][ch * 2]) << 16);
-          else g = *(const float*)&tg[wv][e][ch * 4];
-          g = g * scale;
-          const float w8[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            const unsigned r = (r4[c >> 1] >> (16 * (c & 1))) & 0xffffu;
-            if (r != 0xffffu) atomicAdd(acc + r * 16 + ch, fixed_round(g * w8[c]));
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();                             // (the table is rewritten by the next batch)
-    }
-  }
-  __syncthreads();
-  // conversion and store, 16 lanes per record (a record's 128 bytes in one access; four x-neighbours per instruction)
-  const double inv = 1.0 / (double)scale;                       // exact: the scale is a power of two (2^-90 .. 2^126)
-#pragma unroll 4
-  for (int j = 0; j < 16; ++j) {
-    const int r = wv * 64 + j * 4 + grp;
-    const int lx = r % STX, ly = (r / STX) % STY, lz = r / (STX * STY);
-    const int x = tx0 + lx, y = ty0 + ly, z = tz0 + lz;
-    if (x < W && y < H && z < D) {
-      char* dst = (char*)gvol + (n_out * nvox + (((long)z * H + y) * W + x)) * OREC;
-      const float o = (float)((double)(long long)acc[r * 16 + ch] * inv);
-      if constexpr (OUT16) ((__bf16*)dst)[ch] = __builtin_convertvector((f32x4){o, o, o, o}, bf16x4r)[0];
-      else ((float*)dst)[ch] = o;
-    }
-  }
-}
-
-// samples per pass of the binned form: the lists are sized for the worst case (8 entries per voxel), 512 MB at most
-int g_splat_chunk_cap = 0;                                        // lf_set_tuning key 6: samples per pass at most (0 = by memory only)
-inline int splat_bin_chunk(int N, long nvox) {
-  long cv = (512L << 20) / (nvox * 32);
-  if (cv < 1) cv = 1;
-  if (g_splat_chunk_cap > 0 && cv > g_splat_chunk_cap) cv = g_splat_chunk_cap;
-  return (int)(cv < N ? cv : N);
-}
-
-int g_splat_variant = 2;      // deterministic splat (lf_set_tuning key 4): 1 = global 64-bit atomics, 2 = source tiles in LDS (C == 16;
-                              // lf_resample3d_bwd_vol_det_io: binned lists, a lane quad per list entry), 3 = as 2 without the binned form,
-                              // 4 = as 2 with 16 lanes per list entry (round-6 A/B: slower)
-
-bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
-
-Steps make_steps(int D, int H, int W) {
-  Steps st;
-  st.w = W > 1 ? 1.0f / (float)(W - 1) : 0.f;
-  st.h = H > 1 ? 1.0f / (float)(H - 1) : 0.f;
-  st.d = D > 1 ? 1.0f / (float)(D - 1) : 0.f;
-  return st;
-}
-
 }  // namespace
 
 // Shape rules and launch geometry of the gather, shared by lf_resample3d_fwd and lf_resample3d_fwd_indexed.  With 16 channels
@@ -1012,12 +349,6 @@ static int fwd_plan(const float* vol, const float* out, int N, int D, int H, int
   return 0;
 }
 
-// KERNEL<LF_MAP_O2C> or KERNEL<LF_MAP_C2O> by `kind`, 256 threads, on stream s
-#define LAUNCH_BY_KIND(KERNEL, GRID, ...)                                                                   \
-  do {                                                                                                      \
-    if (kind == LF_MAP_O2C) hipLaunchKernelGGL((KERNEL<LF_MAP_O2C>), GRID, dim3(256), 0, s, __VA_ARGS__);   \
-    else                    hipLaunchKernelGGL((KERNEL<LF_MAP_C2O>), GRID, dim3(256), 0, s, __VA_ARGS__);   \
-  } while (0)
 extern "C" int lf_resample3d_fwd(const float* vol, int vol_n, const float* coef, int kind, float* out,
                                  int N, int D, int H, int W, int C, void* stream) {
   lf_clear_error();
@@ -1202,7 +533,6 @@ extern "C" int lf_resample3d_fwd_indexed(const float* vol, int vol_n, const int*
   }
   return lf_launch_status();
 }
-#undef LAUNCH_BY_KIND
 
 extern "C" size_t lf_resample3d_bwd_coef_indexed_scratch_bytes(int N, int part_n, int D, int H, int W) {
   if (N <= 0 || part_n <= 0) return 0;
@@ -1262,24 +592,16 @@ extern "C" int lf_debug_stage_ts(void* dst) {                      // experiment
 }
 #endif
 
-// Tuning / A-B switch (not part of the functional interface): key 1 = resampler variant (1 generic, 2 lean, 3 lean + 16-channel gather).
-// Returns the previous value, or LF_EINVAL for an unknown key.
+// Tuning / A-B switch (not part of the functional interface): key 1 = resampler variant (1 generic, 2 lean, 3 lean + 16-channel
+// gather, 4 LDS-staged footprint, 5 per-voxel dedup gather).  Returns the previous value, or LF_EINVAL for an unknown key.
 extern "C" int lf_set_tuning(int key, int value) {
   if (key == 1) {
     const int prev = g_resample_variant;
     if (value >= 1 && value <= 5) g_resample_variant = value;
     return prev;
   }
-  if (key == 4) {
-    const int prev = g_splat_variant;
-    if (value >= 1 && value <= 4) g_splat_variant = value;
-    return prev;
-  }
-  if (key == 6) {
-    const int prev = g_splat_chunk_cap;
-    if (value >= 0) g_splat_chunk_cap = value;
-    return prev;
-  }
+  if (key == 4) return lf_internal_splat_set_variant(value);        // deterministic splat: form 1..4
+  if (key == 6) return lf_internal_splat_set_chunk_cap(value);      // binned splat: samples per pass at most, 0 = by memory only
   if (key == 3) return lf_internal_fused_set_cfg(value);            // fused wide-conv GEMM: workgroup shape 0..3, -1 = by shape
   if (key == 7) return lf_internal_wino_set_pack(value);            // fp32 Winograd 16-channel kernels: 1 = packed transforms (default), 0 = scalar
   if (key == 5) return lf_internal_ring_bf16_set_wgs(value);        // bf16 ring convolution: resident workgroups per CU
@@ -1289,72 +611,6 @@ extern "C" int lf_set_tuning(int key, int value) {
     return prev;
   }
   return LF_EINVAL;
-}
-
-// Deterministic form of lf_resample3d_bwd_vol (no float atomics): see resample_bwd_vol_fixed_kernel.  gvol is
-// overwritten (no zero-initialisation needed).  scratch: lf_resample3d_bwd_vol_det_scratch_bytes(...) bytes.
-extern "C" size_t lf_resample3d_bwd_vol_det_scratch_bytes(int vol_n, int D, int H, int W, int C) {
-  if (vol_n <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
-  return (size_t)vol_n * D * H * W * C * sizeof(long long) + 256;
-}
-
-extern "C" int lf_resample3d_bwd_vol_det(const float* gout, const float* coef, int kind, float* gvol, int vol_n, void* scratch,
-                                         size_t scratch_bytes, int N, int D, int H, int W, int C, void* stream) {
-  lf_clear_error();
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0) return LF_EINVAL;
-  if ((vol_n != 1 && vol_n != N) || (kind != LF_MAP_O2C && kind != LF_MAP_C2O)) return LF_EINVAL;
-  const long items = (long)D * H * W * C, total = items * vol_n;
-  if (scratch == nullptr || scratch_bytes < lf_resample3d_bwd_vol_det_scratch_bytes(vol_n, D, H, W, C)) return LF_ENOSPC;
-  if ((((uintptr_t)scratch) & 7u) != 0) return LF_EALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const long ng = items * N;
-  const int nbx = (W + 3) / 4, nby = (H + 3) / 4, nbz = (D + 3) / 4;
-  const long nblk = (long)nbx * nby * nbz;
-  const int ntx = (W + STX - 1) / STX, nty = (H + STY - 1) / STY, ntz = (D + STZ - 1) / STZ;
-  const int nsx = (nbx + 3) / 4, nsy = (nby + 3) / 4, nsz = (nbz + 3) / 4, nsb = nsx * nsy * nsz;
-  if (g_splat_variant >= 2 && C == 16 && lf_aligned16(gout) && lf_aligned16(gvol) && D < 0x7fff && H < 0x7fff && W < 0x7fff &&
-      nblk < 0x7fffffffL / 4 && (long)ntx * nty * ntz < 0x7fffffffL && N <= 65535 &&
-      scratch_bytes >= 256 + (size_t)N * (nblk + nsb) * sizeof(uint3)) {
-    // tiled form: scratch = [amax (256 B)] [block boxes: N x blocks x 12 B] [super-block boxes: N x super-blocks x 12 B]
-    unsigned* amax = (unsigned*)scratch;
-    uint3* bbox = (uint3*)((char*)scratch + 256);
-    uint3* sbox = bbox + (size_t)N * nblk;
-    hipError_t e = hipMemsetAsync(scratch, 0, 256, s);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)min((ng + 255) / 256, 4096L)), dim3(256), 0, s, gout, ng, amax);
-    const Steps stp = make_steps(D, H, W);
-    const dim3 gb((unsigned)((nblk + 3) / 4), (unsigned)N), gs2((unsigned)((nsb + 3) / 4), (unsigned)N),
-        gt((unsigned)((long)ntx * nty * ntz), (unsigned)vol_n);
-    if (kind == LF_MAP_O2C)
-      hipLaunchKernelGGL((splat_bbox_kernel<LF_MAP_O2C>), gb, dim3(256), 0, s, coef, bbox, (int)nblk, nbx, nby, D, H, W, stp);
-    else
-      hipLaunchKernelGGL((splat_bbox_kernel<LF_MAP_C2O>), gb, dim3(256), 0, s, coef, bbox, (int)nblk, nbx, nby, D, H, W, stp);
-    hipLaunchKernelGGL(splat_bbox2_kernel, gs2, dim3(256), 0, s, bbox, sbox, (int)nblk, nsb, nbx, nby, nbz, nsx, nsy);
-    if (kind == LF_MAP_O2C)
-      hipLaunchKernelGGL((splat_tile_kernel<LF_MAP_O2C>), gt, dim3(256), 0, s, gout, coef, bbox, sbox, amax, gvol, vol_n, N, (int)nblk, nsb,
-                         nbx, nby, nbz, nsx, nsy, ntx, nty, D, H, W, stp);
-    else
-      hipLaunchKernelGGL((splat_tile_kernel<LF_MAP_C2O>), gt, dim3(256), 0, s, gout, coef, bbox, sbox, amax, gvol, vol_n, N, (int)nblk, nsb,
-                         nbx, nby, nbz, nsx, nsy, ntx, nty, D, H, W, stp);
-    return lf_launch_status();
-  }
-  unsigned long long* acc = (unsigned long long*)scratch;
-  unsigned* amax = (unsigned*)((char*)scratch + (size_t)total * sizeof(long long));
-  hipError_t e = hipMemsetAsync(scratch, 0, (size_t)total * sizeof(long long) + 256, s);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)min((ng + 255) / 256, 4096L)), dim3(256), 0, s, gout, ng, amax);
-  int st = lf_launch_status();
-  if (st) return st;
-  const long bstride = vol_n == 1 ? 0 : items;
-  dim3 grid((unsigned)min((items + 255) / 256, (long)65535 * 16), N), block(256);
-  if (kind == LF_MAP_O2C)
-    hipLaunchKernelGGL((resample_bwd_vol_fixed_kernel<LF_MAP_O2C>), grid, block, 0, s, gout, coef, acc, bstride, amax, N, D, H, W, C, make_steps(D, H, W));
-  else
-    hipLaunchKernelGGL((resample_bwd_vol_fixed_kernel<LF_MAP_C2O>), grid, block, 0, s, gout, coef, acc, bstride, amax, N, D, H, W, C, make_steps(D, H, W));
-  st = lf_launch_status();
-  if (st) return st;
-  hipLaunchKernelGGL(fixed_to_float_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const long long*)acc, amax, gvol, total);
-  return lf_launch_status();
 }
 
 // ---- storage-type variants for the training step's bf16 storage policy (16-channel volumes only) ----
@@ -1375,117 +631,5 @@ extern "C" int lf_resample3d_fwd_io(const void* vol, int vol_n, const float* coe
       {resample_fwd_c16_kernel<LF_MAP_O2C, 0>, resample_fwd_c16_kernel<LF_MAP_O2C, 1>, resample_fwd_c16_kernel<LF_MAP_O2C, 2>, resample_fwd_c16_kernel<LF_MAP_O2C, 3>},
       {resample_fwd_c16_kernel<LF_MAP_C2O, 0>, resample_fwd_c16_kernel<LF_MAP_C2O, 1>, resample_fwd_c16_kernel<LF_MAP_C2O, 2>, resample_fwd_c16_kernel<LF_MAP_C2O, 3>}};
   hipLaunchKernelGGL(kerns[kind == LF_MAP_O2C ? 0 : 1][io], g4, block, 0, (hipStream_t)stream, (const float*)vol, bstride, coef, (float*)out, D, H, W, nbz4, st);
-  return lf_launch_status();
-}
-
-// scratch: the tile form: [amax (256 B)] [block boxes] [super-block boxes] (a few MB); the binned form: [amax (256 B)]
-// [counters | cursors | offsets: 3 x chunk x tiles u32] [lists: chunk x voxels x 8 u32], chunk = samples per pass (lists of at
-// most 512 MB)
-static bool splat_binned_ok(int vol_n, int N, int D, int H, int W) {
-  if (g_splat_variant == 3 || W > 1024 || H > 1024 || D > 4096) return false;
-  // a volume per sample: passes of `chunk` samples; one shared volume: its tile accumulators live for ONE pass, all samples in it
-  return vol_n == N || splat_bin_chunk(N, (long)D * H * W) == N;
-}
-
-extern "C" size_t lf_resample3d_bwd_vol_det_io_scratch_bytes(int vol_n, int N, int D, int H, int W) {
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
-  const long nbx = (W + 3) / 4, nby = (H + 3) / 4, nbz = (D + 3) / 4;
-  const long nsb = ((nbx + 3) / 4) * ((nby + 3) / 4) * ((nbz + 3) / 4);
-  const size_t boxes = 256 + (size_t)N * (size_t)(nbx * nby * nbz + nsb) * sizeof(uint3);
-  const long nvox = (long)D * H * W;
-  const long nt = (long)((W + STX - 1) / STX) * ((H + STY - 1) / STY) * ((D + STZ - 1) / STZ);
-  const long cv = splat_bin_chunk(N, nvox);
-  const size_t lists = 256 + (size_t)(3 * cv * nt * 4) + (size_t)(cv * nvox * 32);
-  // (sized for either form: lf_set_tuning may switch between them after the caller asked)
-  return boxes > lists ? boxes : lists;
-}
-
-extern "C" int lf_resample3d_bwd_vol_det_io(const void* gout, const float* coef, int kind, void* gvol, int vol_n, void* scratch,
-                                            size_t scratch_bytes, int N, int D, int H, int W, int io, void* stream) {
-  lf_clear_error();
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || io < 0 || io > 3) return LF_EINVAL;
-  if ((vol_n != 1 && vol_n != N) || (kind != LF_MAP_O2C && kind != LF_MAP_C2O)) return LF_EINVAL;
-  if (scratch == nullptr || scratch_bytes < lf_resample3d_bwd_vol_det_io_scratch_bytes(vol_n, N, D, H, W)) return LF_ENOSPC;
-  if ((((uintptr_t)scratch) & 7u) != 0 || !lf_aligned16(gout) || !lf_aligned16(gvol)) return LF_EALIGN;
-  hipStream_t s = (hipStream_t)stream;
-  const long ng = (long)D * H * W * 16 * N;
-  if (splat_binned_ok(vol_n, N, D, H, W)) {
-    // binned form (list entries pack z | y | x into 12 + 10 + 10 bits)
-    const long nvox = (long)D * H * W;
-    const int ntx = (W + STX - 1) / STX, nty = (H + STY - 1) / STY, ntz = (D + STZ - 1) / STZ;
-    const long nt = (long)ntx * nty * ntz;
-    if (nvox >= 0xffffffffL || nt >= 0x7fffffffL || N > 65535) return LF_EINVAL;
-    const int cv = splat_bin_chunk(N, nvox);
-    const long cap = nvox * 8;
-    unsigned* amax = (unsigned*)scratch;
-    unsigned* cnt = (unsigned*)((char*)scratch + 256);
-    unsigned* cur = cnt + (size_t)cv * nt;
-    unsigned* off = cur + (size_t)cv * nt;
-    unsigned* list = off + (size_t)cv * nt;
-    hipError_t e = hipMemsetAsync(scratch, 0, 256, s);
-    if (e != hipSuccess) return (int)e;
-    if (io & 1) hipLaunchKernelGGL(absmax_bf16_kernel, dim3((unsigned)min((ng + 255) / 256, 4096L)), dim3(256), 0, s, (const __bf16*)gout, ng, amax);
-    else hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)min((ng + 255) / 256, 4096L)), dim3(256), 0, s, (const float*)gout, ng, amax);
-    const Steps stp = make_steps(D, H, W);
-    typedef void (*tile_t)(const float*, const float*, const unsigned*, const unsigned*, const unsigned*, const unsigned*, float*, int, int,
-                           int, long, long, int, int, int, int, int, int, Steps);
-    static const tile_t tiles[2][4] = {
-        {splat_binned_tile_kernel<LF_MAP_O2C, 0>, splat_binned_tile_kernel<LF_MAP_O2C, 1>, splat_binned_tile_kernel<LF_MAP_O2C, 2>,
-         splat_binned_tile_kernel<LF_MAP_O2C, 3>},
-        {splat_binned_tile_kernel<LF_MAP_C2O, 0>, splat_binned_tile_kernel<LF_MAP_C2O, 1>, splat_binned_tile_kernel<LF_MAP_C2O, 2>,
-         splat_binned_tile_kernel<LF_MAP_C2O, 3>}};
-    static const tile_t tiles16[2][4] = {
-        {splat_binned_tile16_kernel<LF_MAP_O2C, 0>, splat_binned_tile16_kernel<LF_MAP_O2C, 1>, splat_binned_tile16_kernel<LF_MAP_O2C, 2>,
-         splat_binned_tile16_kernel<LF_MAP_O2C, 3>},
-        {splat_binned_tile16_kernel<LF_MAP_C2O, 0>, splat_binned_tile16_kernel<LF_MAP_C2O, 1>, splat_binned_tile16_kernel<LF_MAP_C2O, 2>,
-         splat_binned_tile16_kernel<LF_MAP_C2O, 3>}};
-    for (int n0 = 0; n0 < N; n0 += cv) {
-      const int m = min(cv, N - n0);
-      e = hipMemsetAsync(cnt, 0, (size_t)2 * cv * nt * 4, s);
-      if (e != hipSuccess) return (int)e;
-      const dim3 gbin((unsigned)(((long)((W + 3) / 4) * ((H + 3) / 4) * ((D + 3) / 4) + 3) / 4), (unsigned)m);
-      if (kind == LF_MAP_O2C) {
-        hipLaunchKernelGGL((splat_bin_kernel<LF_MAP_O2C, false>), gbin, dim3(256), 0, s, coef, cnt, off, list, n0, nvox, cap, (int)nt, ntx, nty, D, H, W, stp);
-        hipLaunchKernelGGL(splat_scan_kernel, dim3((unsigned)m), dim3(256), 0, s, cnt, off, (int)nt);
-        hipLaunchKernelGGL((splat_bin_kernel<LF_MAP_O2C, true>), gbin, dim3(256), 0, s, coef, cur, off, list, n0, nvox, cap, (int)nt, ntx, nty, D, H, W, stp);
-      } else {
-        hipLaunchKernelGGL((splat_bin_kernel<LF_MAP_C2O, false>), gbin, dim3(256), 0, s, coef, cnt, off, list, n0, nvox, cap, (int)nt, ntx, nty, D, H, W, stp);
-        hipLaunchKernelGGL(splat_scan_kernel, dim3((unsigned)m), dim3(256), 0, s, cnt, off, (int)nt);
-        hipLaunchKernelGGL((splat_bin_kernel<LF_MAP_C2O, true>), gbin, dim3(256), 0, s, coef, cur, off, list, n0, nvox, cap, (int)nt, ntx, nty, D, H, W, stp);
-      }
-      const int shared = vol_n == 1 && N > 1;
-      hipLaunchKernelGGL((g_splat_variant == 4 ? tiles16 : tiles)[kind == LF_MAP_O2C ? 0 : 1][io], dim3((unsigned)nt, (unsigned)(shared ? 1 : m)), dim3(g_splat_variant == 4 ? 256 : SBT_THREADS), 0, s, (const float*)gout,
-                         coef, cnt, off, list, amax, (float*)gvol, n0, m, shared, nvox, cap, (int)nt, ntx, nty, D, H, W, stp);
-    }
-    return lf_launch_status();
-  }
-  const int nbx = (W + 3) / 4, nby = (H + 3) / 4, nbz = (D + 3) / 4;
-  const long nblk = (long)nbx * nby * nbz;
-  const int ntx = (W + STX - 1) / STX, nty = (H + STY - 1) / STY, ntz = (D + STZ - 1) / STZ;
-  const int nsx = (nbx + 3) / 4, nsy = (nby + 3) / 4, nsz = (nbz + 3) / 4, nsb = nsx * nsy * nsz;
-  if (!(D < 0x7fff && H < 0x7fff && W < 0x7fff && nblk < 0x7fffffffL / 4 && (long)ntx * nty * ntz < 0x7fffffffL && N <= 65535 &&
-        scratch_bytes >= 256 + (size_t)N * (nblk + nsb) * sizeof(uint3))) return LF_EINVAL;
-  unsigned* amax = (unsigned*)scratch;
-  uint3* bbox = (uint3*)((char*)scratch + 256);
-  uint3* sbox = bbox + (size_t)N * nblk;
-  hipError_t e = hipMemsetAsync(scratch, 0, 256, s);
-  if (e != hipSuccess) return (int)e;
-  if (io & 1) hipLaunchKernelGGL(absmax_bf16_kernel, dim3((unsigned)min((ng + 255) / 256, 4096L)), dim3(256), 0, s, (const __bf16*)gout, ng, amax);
-  else hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)min((ng + 255) / 256, 4096L)), dim3(256), 0, s, (const float*)gout, ng, amax);
-  const Steps stp = make_steps(D, H, W);
-  const dim3 gb((unsigned)((nblk + 3) / 4), (unsigned)N), gs2((unsigned)((nsb + 3) / 4), (unsigned)N),
-      gt((unsigned)((long)ntx * nty * ntz), (unsigned)vol_n);
-  if (kind == LF_MAP_O2C)
-    hipLaunchKernelGGL((splat_bbox_kernel<LF_MAP_O2C>), gb, dim3(256), 0, s, coef, bbox, (int)nblk, nbx, nby, D, H, W, stp);
-  else
-    hipLaunchKernelGGL((splat_bbox_kernel<LF_MAP_C2O>), gb, dim3(256), 0, s, coef, bbox, (int)nblk, nbx, nby, D, H, W, stp);
-  hipLaunchKernelGGL(splat_bbox2_kernel, gs2, dim3(256), 0, s, bbox, sbox, (int)nblk, nsb, nbx, nby, nbz, nsx, nsy);
-  typedef void (*kern_t)(const float*, const float*, const uint3*, const uint3*, const unsigned*, float*, int, int, int, int, int, int, int,
-                         int, int, int, int, int, int, int, Steps);
-  static const kern_t kerns[2][4] = {
-      {splat_tile_kernel<LF_MAP_O2C, 0>, splat_tile_kernel<LF_MAP_O2C, 1>, splat_tile_kernel<LF_MAP_O2C, 2>, splat_tile_kernel<LF_MAP_O2C, 3>},
-      {splat_tile_kernel<LF_MAP_C2O, 0>, splat_tile_kernel<LF_MAP_C2O, 1>, splat_tile_kernel<LF_MAP_C2O, 2>, splat_tile_kernel<LF_MAP_C2O, 3>}};
-  hipLaunchKernelGGL(kerns[kind == LF_MAP_O2C ? 0 : 1][io], gt, dim3(256), 0, s, (const float*)gout, coef, bbox, sbox, amax, (float*)gvol, vol_n, N,
-                     (int)nblk, nsb, nbx, nby, nbz, nsx, nsy, ntx, nty, D, H, W, stp);
   return lf_launch_status();
 }

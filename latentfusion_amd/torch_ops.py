@@ -2,7 +2,7 @@
 with the dispatcher so that the reference's modules can call them like any ATen op.  Importing this module defines the
 namespace `lf`; each operator is implemented by the autograd function of ops.py / engine.py that wraps the C entry point
 (registered as CompositeImplicitAutograd: the dispatcher runs that implementation and autograd differentiates through it, so
-`torch.ops.lf.o2c(vol, coef).sum().backward()` launches lf_resample3d_bwd_coef / lf_resample3d_bwd_vol_det).  No CPU kernel is
+`torch.ops.lf.o2c(vol, coef).sum().backward()` launches lf_resample3d_bwd_coef of csrc/resample.hip and lf_resample3d_bwd_vol_det of csrc/splat.hip).  No CPU kernel is
 registered: the operators raise LFHipError on host tensors, like the wrappers they call.
 
     import latentfusion_amd.torch_ops

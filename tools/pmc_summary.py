@@ -68,7 +68,7 @@ TRAIN_KERNELS = collections.OrderedDict([
 SPLIT = {'conv3d_c16_wino_kernel': (('forward form', 2 * 8 * 16 * 128 ** 3 * 4 + 8 * 128 ** 3 * 4),
                                     ('data-gradient form + fused previous-layer backward', 3 * 8 * 16 * 128 ** 3 * 4 + 8 * 128 ** 3 * 4))}
 SOURCES = ['conv_wino.hip', 'conv.hip', 'conv_split.hip', 'resample.hip', 'pointwise.hip', 'reduce.hip']
-TRAIN_SOURCES = ['conv_split.hip', 'wgrad.hip', 'resample.hip', 'pointwise.hip', 'gru.hip', 'conv_gru.hip', 'lift_mfma.hip', 'ring_tile.h', 'pw16.hip']
+TRAIN_SOURCES = ['conv_split.hip', 'wgrad.hip', 'resample.hip', 'splat.hip', 'pointwise.hip', 'gru.hip', 'conv_gru.hip', 'lift_mfma.hip', 'ring_tile.h', 'pw16.hip']
 # --cfg3: the released architecture's kernels inside the cross_entropy_linemod loop (tools/pmc_collect_cfg3.sh over
 # tools/cfg3_probe.py; no calibration copy in that run: FETCH_SIZE x 2, WRITE_SIZE x 1 as calibrated in the other two)
 CFG3_KERNELS = collections.OrderedDict([

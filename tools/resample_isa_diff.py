@@ -4,10 +4,13 @@ Compiles resample.hip of a parent revision (git archive) and of the working tree
 library's flags, disassembles both, and diffs every kernel symbol the parent's code object holds, instruction by
 instruction (addresses dropped, encodings kept).  Kernels that only the working tree has are listed, not compared.
 
-    python tools/resample_isa_diff.py [--rev HEAD] [--out profiles/resample_indexed_isa.txt] [--src FILE.hip ...]
+    python tools/resample_isa_diff.py [--rev HEAD] [--out profiles/resample_indexed_isa.txt] [--src FILE.hip[=PARENT.hip] ...]
 
 --src names other files of csrc/ (each with its per-file flags of csrc/build.py), e.g. the wide Winograd family
-(profiles/wide_wino_shared_isa.txt: --src wino_fused.hip wino_fused_f16x3.hip wino_gemm.hip).
+(profiles/wide_wino_shared_isa.txt: --src wino_fused.hip wino_fused_f16x3.hip wino_gemm.hip).  FILE.hip=PARENT.hip says
+that the tree's FILE.hip holds kernels that the parent kept in PARENT.hip: the tree files that name one parent file are
+taken together, so a kernel that moved is compared with the parent's instead of being listed as new
+(profiles/splat_split_isa.txt: --src resample.hip splat.hip=resample.hip).
 
 The kernels that exist as a plain and an indexed form are written once (csrc/resample_gather.inc, included twice by
 resample.hip) and keep their names, so a change to that file is checked here like any other: every symbol of both forms
@@ -51,7 +54,8 @@ def disassemble(tree, workdir, tag, src='resample.hip'):
         m = re.match(r'^[0-9a-f]*\s*<(.+)>:$', line)
         if m:
             cur = syms.setdefault(m.group(1), [])
-        elif cur is not None and line.strip():
+        elif cur is not None and line.strip() not in ('', '...'):
+            # ('...' is elided zero padding behind a symbol: it depends on what follows the kernel in its file, not on the kernel)
             # "\tinsn operands   // 000000020C10: BF88003C <sym+0x104>": the address goes, the encoding and the target stay
             cur.append(re.sub(r'//\s*[0-9A-Fa-f]+:', '//', line).rstrip())
     return syms
@@ -70,11 +74,17 @@ def main():
         os.makedirs(parent)
         ar = subprocess.run(['git', '-C', ROOT, 'archive', a.rev, 'latentfusion_amd/csrc', 'include'], check=True, stdout=subprocess.PIPE)
         subprocess.run(['tar', '-x', '-C', parent], input=ar.stdout, check=True)
-        for src in a.src:
-            old = disassemble(parent, tmp, 'parent', src)
-            new = disassemble(ROOT, tmp, 'tree', src)
-            lines += [f'# {os.path.join(CSRC, src)}: kernel symbols of revision {rev} against the working tree, gfx950, flags '
-                      f'{" ".join(hip_build.FLAGS + hip_build.EXTRA.get(src, []))}', '# symbol: instructions (parent / tree)']
+        origin = {}                                       # parent file -> the tree files that hold its kernels now
+        for item in a.src:
+            src, _, old_src = item.partition('=')
+            origin.setdefault(old_src or src, []).append(src)
+        for old_src, srcs in origin.items():
+            old = disassemble(parent, tmp, 'parent', old_src)
+            new = {}
+            for src in srcs:
+                new.update(disassemble(ROOT, tmp, 'tree', src))
+            lines += [f'# {os.path.join(CSRC, old_src)}: kernel symbols of revision {rev} against {", ".join(srcs)} of the working tree, gfx950, '
+                      f'flags {" ".join(hip_build.FLAGS + hip_build.EXTRA.get(old_src, []))}', '# symbol: instructions (parent / tree)']
             for name in sorted(old):
                 lines.append(f'#   {name}: {len(old[name])} / {len(new.get(name, []))}')
                 diff += list(difflib.unified_diff(old[name], new.get(name, []), 'parent:' + name, 'tree:' + name, lineterm='', n=2))
