@@ -337,6 +337,22 @@ int lf_wino_fused_gemm(const float* V, const float* U2, const float* bias, float
                        int dims, int N, int D, int H, int W, int Cin, int Cout, float he, unsigned flags, float slope,
                        void* stream);
 
+/* The same over N samples taken as N / part_n parts of part_n consecutive samples, with the frequency split that a launch of
+ * ONE part chooses (lf_resample3d_bwd_coef_part is the precedent): every output value is formed by exactly the operations,
+ * in exactly the order, of lf_wino_fused_gemm called on its part alone with N = part_n and the same other arguments, whatever
+ * N is -- so the multi-target pose loop's T x part_n rows reproduce T single-target loops bit for bit.  The frequency split
+ * is the only thing lf_wino_fused_gemm takes from the batch that changes a bit (it groups the F frequency contributions into
+ * the partial sums the finish launch adds); the workgroup shape, which does not, still follows the whole batch, and so do the
+ * grid, the scratch and the finish: one GEMM launch plus at most one finish launch.  A shape forced with lf_set_tuning(3, v)
+ * counts for the part as for the batch.  part_n = N issues exactly the launches of lf_wino_fused_gemm.
+ * Returns LF_EINVAL for part_n <= 0 or N % part_n != 0, otherwise as lf_wino_fused_gemm, with
+ * scratch: lf_wino_fused_scratch_bytes_part(...) bytes (>= lf_wino_fused_scratch_bytes, equal at part_n = N; 0 for bad
+ * arguments); nothing is launched on an error. */
+size_t lf_wino_fused_scratch_bytes_part(int dims, int N, int D, int H, int W, int Cout, int part_n);
+int lf_wino_fused_gemm_part(const float* V, const float* U2, const float* bias, float* y, void* scratch, size_t scratch_bytes,
+                            int dims, int N, int D, int H, int W, int Cin, int Cout, float he, unsigned flags, float slope,
+                            int part_n, void* stream);
+
 /* Row-major GEMM with the Block epilogue in the store, on the same fp32 MFMA (no library GEMM on the hot path):
  *   y[m][co] = epilogue( he * sum_k x[m][k] * W[co][k] + bias[co] )        m < M, co < Cout, k < K
  *   epilogue = [LeakyReLU(slope)] ; [PixelNorm over co (eps), norm_out[m] = sqrt(mean_co(y^2) + eps)]

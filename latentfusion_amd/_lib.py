@@ -72,6 +72,8 @@ SIGNATURES = {
     'lf_wino_fused_cout_padded': (c_int, [c_int]),
     'lf_wino_fused_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
     'lf_wino_fused_gemm': (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_uint, c_float, P]),
+    'lf_wino_fused_scratch_bytes_part': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    'lf_wino_fused_gemm_part': (c_int, [P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_uint, c_float, c_int, P]),
     'lf_rows_gemm_cout_padded': (c_int, [c_int]),
     'lf_rows_gemm_epi': (c_int, [P, P, P, P, P, c_long, c_int, c_int, c_float, c_uint, c_float, c_float, P]),
     'lf_wino_f16x3_cin_padded': (c_int, [c_int]),

@@ -155,38 +155,46 @@ int pick_fused_cfg(int dims, long T, int CoutP) {
 // workgroups wanted before a launch stops splitting over the frequencies: two (4-wave) / one (8-wave) resident per CU
 long fused_want(int cfg) { return kCfg[cfg].waves == 4 ? 512 : 256; }
 
-}  // namespace
+// The launch plan of N samples whose frequency split is the one a launch of part_n samples chooses (part_n = N: the plain
+// plan).  The split decides how the F frequency contributions of an output value are grouped into partial sums, so it alone
+// ties a sample's rounding to the batch it shares a launch with; the workgroup shape does not change a bit and follows the
+// whole batch, as do the grid and the finish launch.
+struct PartPlan {
+  wino_ring::Plan p;
+  int cfg;
+  PartPlan(int dims, int N, int D, int H, int W, int Cout, int part_n) : p(dims, N, D, H, W, Cout) {
+    cfg = pick_fused_cfg(dims, p.T, p.CoutP);
+    wino_ring::Plan q(dims, part_n, D, H, W, Cout);              // what lf_wino_fused_gemm does with N = part_n
+    const int qc = pick_fused_cfg(dims, q.T, q.CoutP);
+    q.split(dims == 3 ? 64 : 16, kCfg[qc].mt, kCfg[qc].nt, fused_want(qc));
+    p.split(dims == 3 ? 64 : 16, kCfg[cfg].mt, kCfg[cfg].nt, fused_want(cfg));
+    p.zs = q.zs;
+  }
+};
 
-extern "C" int lf_wino_fused_cout_padded(int Cout) { return (Cout + 63) / 64 * 64; }
-
-// bytes of scratch lf_wino_fused_gemm needs for this shape (0: none).  (An upper bound over the workgroup shapes.)
-extern "C" size_t lf_wino_fused_scratch_bytes(int dims, int N, int D, int H, int W, int Cout) {
-  if ((dims != 2 && dims != 3) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0) return 0;
-  wino_ring::Plan p(dims, N, D, H, W, Cout);
+size_t fused_scratch_bytes(int dims, int N, int D, int H, int W, int Cout, int part_n) {
+  if ((dims != 2 && dims != 3) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cout <= 0 || part_n <= 0 || N % part_n) return 0;
+  wino_ring::Plan p(dims, N, D, H, W, Cout), q(dims, part_n, D, H, W, Cout);
   int zs = 1;
   for (int c = 0; c < NCFG; ++c) {
     if (dims == 3 && c >= 3) continue;
-    p.split(dims == 3 ? 64 : 16, kCfg[c].mt, kCfg[c].nt, fused_want(c));
-    zs = p.zs > zs ? p.zs : zs;
+    q.split(dims == 3 ? 64 : 16, kCfg[c].mt, kCfg[c].nt, fused_want(c));
+    zs = q.zs > zs ? q.zs : zs;
   }
   p.zs = zs;
   return p.scratch_bytes();
 }
 
-// y = epilogue(output_transform(V[f] . U2[f]^T)):  V [F][T][Cin] from lf_wino{2,3}d_input_transform;
-// scratch: lf_wino_fused_scratch_bytes(...) bytes (small problems are split over the frequencies);
-// U2 [F][CoutP][Cin] (output-channel major, CoutP = lf_wino_fused_cout_padded(Cout), zero padded);
-// y channels-last [N][D][H][W][Cout].  flags: LF_EPI_LRELU (PixelNorm: run lf_pixelnorm_fwd on y afterwards).
-extern "C" int lf_wino_fused_gemm(const float* V, const float* U2, const float* bias, float* y, void* scratch,
-                                  size_t scratch_bytes, int dims, int N, int D, int H, int W, int Cin, int Cout, float he,
-                                  unsigned flags, float slope, void* stream) {
+int fused_gemm(const float* V, const float* U2, const float* bias, float* y, void* scratch, size_t scratch_bytes, int dims, int N,
+               int D, int H, int W, int Cin, int Cout, float he, unsigned flags, float slope, int part_n, void* stream) {
   lf_clear_error();
   if ((dims != 2 && dims != 3) || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return LF_EINVAL;
   if ((Cin & 3) || (Cout & 3) || (dims == 2 && D != 1) || (flags & ~(LF_EPI_LRELU | LF_OUT_DEPTH_INNER))) return LF_EINVAL;
+  if (part_n <= 0 || N % part_n) return LF_EINVAL;
   if (!lf_aligned16(V) || !lf_aligned16(U2) || !lf_aligned16(y) || (bias && !lf_aligned16(bias))) return LF_EALIGN;
-  wino_ring::Plan p(dims, N, D, H, W, Cout);
-  const int cfg = pick_fused_cfg(dims, p.T, p.CoutP);
-  p.split(dims == 3 ? 64 : 16, kCfg[cfg].mt, kCfg[cfg].nt, fused_want(cfg));
+  PartPlan pp(dims, N, D, H, W, Cout, part_n);
+  wino_ring::Plan& p = pp.p;
+  const int cfg = pp.cfg;
   if (const int st = p.check(Cin, scratch, scratch_bytes)) return st;
   hipStream_t s = (hipStream_t)stream;
 #define LF_FUSED(DIMS_, WM_, WN_, BA_, BB_)                                                                                         \
@@ -200,6 +208,39 @@ extern "C" int lf_wino_fused_gemm(const float* V, const float* U2, const float* 
 #undef LF_FUSED
   if (st || p.zs == 1) return st;
   return wino_ring::finish<wino_fused_finish_kernel>(p, s, bias, y, p.ysize / 4, p.zs, Cout / 4, he, flags & LF_EPI_LRELU, slope);
+}
+
+}  // namespace
+
+extern "C" int lf_wino_fused_cout_padded(int Cout) { return (Cout + 63) / 64 * 64; }
+
+// bytes of scratch lf_wino_fused_gemm needs for this shape (0: none).  (An upper bound over the workgroup shapes.)
+extern "C" size_t lf_wino_fused_scratch_bytes(int dims, int N, int D, int H, int W, int Cout) {
+  return fused_scratch_bytes(dims, N, D, H, W, Cout, N);
+}
+
+// y = epilogue(output_transform(V[f] . U2[f]^T)):  V [F][T][Cin] from lf_wino{2,3}d_input_transform;
+// scratch: lf_wino_fused_scratch_bytes(...) bytes (small problems are split over the frequencies);
+// U2 [F][CoutP][Cin] (output-channel major, CoutP = lf_wino_fused_cout_padded(Cout), zero padded);
+// y channels-last [N][D][H][W][Cout].  flags: LF_EPI_LRELU (PixelNorm: run lf_pixelnorm_fwd on y afterwards).
+extern "C" int lf_wino_fused_gemm(const float* V, const float* U2, const float* bias, float* y, void* scratch,
+                                  size_t scratch_bytes, int dims, int N, int D, int H, int W, int Cin, int Cout, float he,
+                                  unsigned flags, float slope, void* stream) {
+  return fused_gemm(V, U2, bias, y, scratch, scratch_bytes, dims, N, D, H, W, Cin, Cout, he, flags, slope, N, stream);
+}
+
+// The same over N samples in N / part_n parts of part_n consecutive samples, with the frequency split of a launch of ONE part
+// (as lf_resample3d_bwd_coef_part does for the coefficient gradient): every output value is formed by the operations, in the
+// order, of lf_wino_fused_gemm called on its part alone with N = part_n -- one GEMM launch and at most one finish launch for
+// the whole batch.  scratch: lf_wino_fused_scratch_bytes_part(...) bytes.  part_n = N: lf_wino_fused_gemm.
+extern "C" size_t lf_wino_fused_scratch_bytes_part(int dims, int N, int D, int H, int W, int Cout, int part_n) {
+  return fused_scratch_bytes(dims, N, D, H, W, Cout, part_n);
+}
+
+extern "C" int lf_wino_fused_gemm_part(const float* V, const float* U2, const float* bias, float* y, void* scratch,
+                                       size_t scratch_bytes, int dims, int N, int D, int H, int W, int Cin, int Cout, float he,
+                                       unsigned flags, float slope, int part_n, void* stream) {
+  return fused_gemm(V, U2, bias, y, scratch, scratch_bytes, dims, N, D, H, W, Cin, Cout, he, flags, slope, part_n, stream);
 }
 
 // tuning hook for lf_set_tuning (key 3, resample.hip): workgroup shape of the fused GEMM, -1 = by shape

@@ -255,13 +255,16 @@ class _WideWinograd(_CameraBlocks):
     """Wide blocks (released model: 256 -> 256 on 16^3): Winograd input transform + lf_wino_fused_gemm (ops.wide_conv)."""
     # (fused fp32-MFMA GEMM / output transform / epilogue kernel; the packs are cached on the parameters)
     wide = True
+    # rows per part of the launches (lf_wino_fused_gemm_part); None: the batch's own plan.  engine_multi.MultiTargetEngine with
+    # per_target_plan=True sets it to the hypotheses per target for the duration of a call
+    part_n = None
 
     def forward(self, li, x, flags, depth_inner=False):
-        return ops.wide_conv(x, self.w[li], self.bias[li], self.he[li], flags, depth_inner=depth_inner)
+        return ops.wide_conv(x, self.w[li], self.bias[li], self.he[li], flags, depth_inner=depth_inner, part_n=self.part_n)
 
     def data_grad(self, i, g, acts, norms, flags, bounds):
         gpre = ops._epilogue_bwd(g, acts[i + 1], norms[i], flags)
-        return ops.wide_conv(gpre, self.w[i], None, self.he[i], 0, transpose=True)[0]
+        return ops.wide_conv(gpre, self.w[i], None, self.he[i], 0, transpose=True, part_n=self.part_n)[0]
 
 
 class _WideWinogradF16x3(_CameraBlocks):

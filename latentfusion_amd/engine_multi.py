@@ -8,10 +8,13 @@ RenderLoopEngine.  Everything below the loss already works per hypothesis; what 
     part_n = n): its fixed-order block partition no longer follows the batch size;
   * the latent term's cosine distance is evaluated per target slice.
 So per target the losses and camera gradients are bit-identical to RenderLoopEngine on that target's n rows alone for the
-kernels whose per-sample arithmetic does not depend on the batch.  Exceptions (tests/test_multi_target_engine_gpu.py names
-their tolerances): conv_mode 'f16x3' (batch-wide gradient scales) and every renderer with wide (>= 64-channel) layers, the
-released architecture included: lf_wino_fused_gemm picks its workgroup configuration (pick_fused_cfg) and its frequency
-split (wino_ring::Plan::split, csrc/wino_ring.h) from the batch's tile count N x tiles, so a row's summation order follows the batch size.
+kernels whose per-sample arithmetic does not depend on the batch.  On renderers with wide (>= 64-channel) layers, the released
+architecture included, that needs per_target_plan=True: lf_wino_fused_gemm picks its frequency split
+(wino_ring::Plan::split, csrc/wino_ring.h) from the batch's tile count N x tiles, so by default a row's summation order
+follows the batch size; with the option every wide launch takes the split of ONE target's rows (lf_wino_fused_gemm_part).
+Exceptions that remain (tests/test_multi_target_engine_gpu.py, tests/test_multi_target_part_plan_gpu.py name their
+tolerances): conv_mode 'f16x3' (batch-wide input and gradient scales; refused with per_target_plan) and the ranking form's
+factor projection with proj_kernel 'library' (the library picks its GEMM kernel by the row count; 'mfma' is row-independent).
 
 Several objects (a scene's frame holds a few, each with its own latent volume): `z_obj` is then a sequence of T volumes, one
 per target.  Nothing below the resampler is per object -- camera blocks, projection, decoder, loss and optimiser work per row
@@ -78,7 +81,19 @@ class MultiTargetEngine(RenderLoopEngine):
 
     MAX_ROWS = 65535
 
-    def __init__(self, photographer, z_obj, targets, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None):
+    def __init__(self, photographer, z_obj, targets, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None,
+                 per_target_plan=False):
+        """per_target_plan: every fp32 wide (>= 64-channel) Winograd launch of a call -- the camera blocks' convolutions and data
+        gradients, and the 2-D decoder's under ops.wide_parts -- takes the frequency split of a launch of ONE target's n rows
+        (lf_wino_fused_gemm_part, part_n = n), so on wide renderers too every target's losses and camera gradients are
+        bit-identical to RenderLoopEngine on its rows alone.  False (default): the batch's own plan, as before.  On a renderer
+        without wide layers the option changes nothing; with conv_mode 'f16x3' it is refused (NotImplementedError): that
+        form's input and gradient scales are maxima over the whole batch, which no launch plan undoes."""
+        self.per_target_plan = bool(per_target_plan)
+        if self.per_target_plan and conv_mode == 'f16x3':
+            raise NotImplementedError("per_target_plan with conv_mode 'f16x3': the split-precision kernels scale their inputs and "
+                                      'gradients by batch-wide maxima, so a per-target launch plan would not reproduce the '
+                                      'single-target loop')
         targets = list(targets)
         if not targets:
             raise ValueError('MultiTargetEngine needs at least one target')
@@ -139,10 +154,16 @@ class MultiTargetEngine(RenderLoopEngine):
                 raise ValueError(f'z_target_latent has {z_target_latent.shape[0]} rows: expected {N} or {self.T}')
             z_target_latent = z_target_latent.repeat_interleave(n, dim=0)
         self._n = n
+        part = n if self.per_target_plan else None
+        if part is not None and self.plan.wide:
+            self.plan.part_n = part                              # the camera blocks' launches (engine._WideWinograd)
         try:
-            return RenderLoopEngine.forward_backward(self, camera, need_grad, z_target_latent, params, masked_depth)
+            with ops.wide_parts(part):                            # the decoder's wide 2-D layers (ops._Conv3x3), forward and backward
+                return RenderLoopEngine.forward_backward(self, camera, need_grad, z_target_latent, params, masked_depth)
         finally:
             self._n = None
+            if self.plan.wide:
+                self.plan.part_n = None
 
     # ---- the per-target pieces ----
     def _loss_fwd(self, lg, coefs, masked_depth):

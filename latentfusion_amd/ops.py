@@ -466,15 +466,22 @@ def _wino_conv_fused(x, cout, flags, depth_inner, v_shape, v_dtype, transform, s
     return y, norm
 
 
-def conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner=False):
+def conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner=False, part_n=None):
     """Wide 2-D / 3-D conv: Winograd input transform, then ONE launch for the per-frequency fp32-MFMA products, the
     output transform, He scale, bias and LeakyReLU (lf_wino_fused_gemm); PixelNorm as a pass over the (small) output.
     depth_inner (3-D only): y comes back as a plain (N, H, W, D, cout) tensor (LF_OUT_DEPTH_INNER): the layout the factor
-    projection that follows the last camera block wants.  Returns (y, norm or None)."""
+    projection that follows the last camera block wants.
+    part_n: the N rows are N / part_n parts of part_n consecutive rows, and every part's output is bit-identical to this call
+    on that part alone (lf_wino_fused_gemm_part: the part's frequency split, one launch for the batch); None: the batch's own
+    plan.  Returns (y, norm or None)."""
     L = _lib.lib()
     dims = x.dim() - 2
     N, cin = x.shape[0], x.shape[1]
     D, H, W = (x.shape[2:] if dims == 3 else (1,) + tuple(x.shape[2:]))
+    if part_n is not None:
+        part_n = _part_rows(part_n)
+        if N % part_n:
+            raise ValueError(f'part_n = {part_n} does not divide the {N} rows')
     if dims == 3:
         T = L.lf_wino3d_tiles(N, D, H, W)
         transform = ('wino3d_input', lambda V: check(L.lf_wino3d_input_transform(_ptr(x), _ptr(V), N, D, H, W, cin, _stream()),
@@ -485,21 +492,64 @@ def conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner=False):
                                                      'lf_wino2d_input_transform'))
 
     def gemm(V, y, scr, nscr, gflags):
-        check(L.lf_wino_fused_gemm(_ptr(V), _ptr(U2), _ptr(bias) if bias is not None else None, _ptr(y), scr, nscr, dims, N, D, H,
-                                   W, cin, cout, he, gflags, SLOPE, _stream()), 'lf_wino_fused_gemm')
+        b = _ptr(bias) if bias is not None else None
+        if part_n is None:
+            check(L.lf_wino_fused_gemm(_ptr(V), _ptr(U2), b, _ptr(y), scr, nscr, dims, N, D, H, W, cin, cout, he, gflags, SLOPE,
+                                       _stream()), 'lf_wino_fused_gemm')
+        else:
+            check(L.lf_wino_fused_gemm_part(_ptr(V), _ptr(U2), b, _ptr(y), scr, nscr, dims, N, D, H, W, cin, cout, he, gflags,
+                                            SLOPE, part_n, _stream()), 'lf_wino_fused_gemm_part')
+
+    def scratch_bytes():                                      # the scratch follows the query of the entry point that is called
+        if part_n is None:
+            return L.lf_wino_fused_scratch_bytes(dims, N, D, H, W, cout)
+        return L.lf_wino_fused_scratch_bytes_part(dims, N, D, H, W, cout, part_n)
     return _wino_conv_fused(x, cout, flags, depth_inner, (16 if dims == 2 else 64, T, cin), torch.float32, transform,
-                            lambda: L.lf_wino_fused_scratch_bytes(dims, N, D, H, W, cout), (f'wino{dims}d_fused', gemm))
+                            scratch_bytes, (f'wino{dims}d_fused', gemm))
 
 
-def wide_conv(x, weight, bias, he, flags, transpose=False, depth_inner=False):
-    """Dispatch of a wide (>= 64-channel) 3x3(x3) convolution or its data gradient (transpose=True) by WIDE_CONV_MODE."""
+def wide_conv(x, weight, bias, he, flags, transpose=False, depth_inner=False, part_n=None):
+    """Dispatch of a wide (>= 64-channel) 3x3(x3) convolution or its data gradient (transpose=True) by WIDE_CONV_MODE.
+    part_n: see conv_wino_fused ('fused' only)."""
     cout = weight.shape[1] if transpose else weight.shape[0]
     if WIDE_CONV_MODE == 'fused':
         U2 = _pk(weight, 'wfb' if transpose else 'wff', lambda w: pack_conv_wino_fused(w, transpose=transpose))
-        return conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner)
+        return conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner, part_n)
+    if part_n is not None:
+        raise NotImplementedError("part_n needs WIDE_CONV_MODE = 'fused': the library GEMM of 'bmm' picks its kernel by the batch")
     from . import experimental                     # 'bmm': the three-stage form on the library GEMM (A/B reference)
     U = _pk(weight, 'g3b' if transpose else 'g3f', lambda w: experimental.pack_conv3d_wino_gemm(w, transpose=transpose))
     return experimental.conv3d_wino_gemm(x, U, bias, he, flags)
+
+
+# Scope of the per-part launch plan (MultiTargetEngine per_target_plan=True): inside `with ops.wide_parts(n):` the fp32 wide 2-D
+# and 3-D convolutions of _Conv3x3 treat their batch as parts of n consecutive rows (wide_conv part_n = n), so each part's rows
+# are bit-identical to the same convolution on that part alone.  The forward records n on ctx and the data gradient uses it
+# whatever scope the backward runs in.  None: the batch's own plan.  Weight gradients are not affected, and neither are the
+# split-precision forms (ops.wide2d_f16x3: their scales come from the whole batch).
+WIDE_PARTS = None
+
+
+def _part_rows(n):
+    if isinstance(n, bool) or not isinstance(n, int) or n <= 0:
+        raise ValueError(f'part rows must be a positive int, got {n!r}')
+    return n
+
+
+class wide_parts:
+    def __init__(self, n):
+        self.n = None if n is None else _part_rows(n)
+
+    def __enter__(self):
+        global WIDE_PARTS
+        self.prev = WIDE_PARTS
+        WIDE_PARTS = self.n
+        return self
+
+    def __exit__(self, *exc):
+        global WIDE_PARTS
+        WIDE_PARTS = self.prev
+        return False
 
 
 def pack_conv_wino_fused_f16x3(weight, transpose=False):
@@ -610,6 +660,15 @@ class wide2d_f16x3:
 def _wide2d_f16x3_routed(cin, cout, H, W, N):
     n_min = WIDE2D_F16X3_ROUTE.get((cin, cout, H, W))
     return n_min is not None and N >= n_min
+
+
+def _wide_part_n(N):
+    """part_n of a wide convolution on N rows under the ops.wide_parts scope (None outside it)."""
+    if WIDE_PARTS is None or WIDE_CONV_MODE != 'fused':
+        return None
+    if N % WIDE_PARTS:
+        raise ValueError(f'ops.wide_parts({WIDE_PARTS}) does not divide a batch of {N} rows')
+    return WIDE_PARTS
 
 
 def epilogue_bwd_amax(gy, y, norm, flags, amax_out):
@@ -843,6 +902,7 @@ class _Conv3x3(torch.autograd.Function):
         ctx.ac = AUTOCAST is not None
         split2d = WIDE2D_F16X3 and not ctx.ac and WIDE_CONV_MODE == 'fused'
         ctx.f16x3 = (False, False)                            # (forward, data gradient) on the split-precision 2-D kernel
+        ctx.part_n = None
         if ctx.ac and _wino_ok(x, weight):                    # autocast, 3-D 16 -> 16: direct conv on the bf16 MFMA
             y, norm = conv3d_c16_ring_bf16(x, _pk(weight, 'r3f', pack_conv3d_c16_ring_bf16), b, he, flags, 1)
             # (the input is saved un-rounded: the bf16 weight-gradient kernel rounds it while staging, like this one)
@@ -859,7 +919,8 @@ class _Conv3x3(torch.autograd.Function):
                 if ctx.f16x3[0]:                              # ... or its split-precision form (ops.wide2d_f16x3 scope)
                     y, norm = wide_conv_f16x3(x, weight, b, he, flags)
                 else:
-                    y, norm = wide_conv(x, weight, b, he, flags)
+                    ctx.part_n = _wide_part_n(x.shape[0])     # ops.wide_parts scope; the data gradient follows it
+                    y, norm = wide_conv(x, weight, b, he, flags, part_n=ctx.part_n)
             else:
                 wpack = _pk(weight, 'c3f', pack_conv3x3)
                 y, norm = _conv3x3_raw(x, wpack, b, weight.shape[0], he, flags, True)
@@ -886,7 +947,7 @@ class _Conv3x3(torch.autograd.Function):
                     elif ctx.f16x3[1]:
                         gx, _ = wide_conv_f16x3(gpc, w, None, ctx.he, 0, transpose=True)
                     elif _wino_gemm_ok(gpc, w):
-                        gx, _ = wide_conv(gpc, w, None, ctx.he, 0, transpose=True)
+                        gx, _ = wide_conv(gpc, w, None, ctx.he, 0, transpose=True, part_n=ctx.part_n)
                     else:
                         wpack_t = _pk(w, 'c3b', lambda t: pack_conv3x3(t, transpose=True))
                         gx, _ = _conv3x3_raw(gpc, wpack_t, None, w.shape[1], ctx.he, 0, False)

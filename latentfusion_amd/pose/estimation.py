@@ -483,8 +483,14 @@ class GradientPoseEstimator(PoseEstimator):
     def __init__(self, *, learning_rate, num_samples, num_iters, converge_threshold, converge_patience,
                  lr_reduce_patience=25, lr_reduce_threshold=1e-5, lr_reduce_factor=0.5, track_stats=False,
                  loss_schedules=None, optimizer='adamw', use_engine=True, conv_mode='auto', engine_streams=1,
-                 fuse_projection=None, engine_graph=False, **kwargs):
+                 fuse_projection=None, engine_graph=False, per_target_plan=False, **kwargs):
         super().__init__(use_engine=use_engine, conv_mode=conv_mode, fuse_projection=fuse_projection, **kwargs)
+        # per_target_plan (estimate_batch only; also an [args] key of the TOML): the batched loop's wide launches take the launch
+        # plan of one target's rows (MultiTargetEngine per_target_plan), so the batch reproduces estimate() on wide renderers too
+        self.per_target_plan = bool(per_target_plan)
+        if self.per_target_plan and conv_mode == 'f16x3':
+            raise NotImplementedError("per_target_plan with conv_mode 'f16x3': the split-precision kernels scale their inputs and "
+                                      'gradients by batch-wide maxima, so a per-target launch plan would not reproduce estimate()')
         self.engine_graph = engine_graph         # replay the engine's evaluation from a captured hipGraph (engine.forward_backward_graph)
         self.engine_streams = engine_streams     # hypothesis groups evaluated concurrently on separate HIP streams (engine.py)
         self.learning_rate, self.num_samples, self.num_iters = learning_rate, num_samples, num_iters
@@ -731,9 +737,15 @@ class GradientPoseEstimator(PoseEstimator):
         the returned list is what estimate(z_obj, targets[t], camera=cameras[t]) returns (the best cameras, plus stat_history /
         camera_history per the flags) -- bit for bit on the kernels whose per-hypothesis arithmetic does not depend on the
         batch size (tests/test_multi_target_estimator_gpu.py): the 16-channel renderers (SYN, occlusion) in conv_mode
-        'winograd' / 'fp32'.  NOT on renderers with wide (>= 64-channel) layers, the released architecture included, nor in
-        conv_mode 'f16x3': lf_wino_fused_gemm chooses its workgroup configuration and frequency split from the batch's tile
-        count, and the f16x3 gradient scales come from a batch-wide max, so a row's rounding follows its batch mates; Adam
+        'winograd' / 'fp32'.  On renderers with wide (>= 64-channel) layers, the released architecture included, the same
+        holds with per_target_plan=True (constructor argument or [args] key of the TOML; tests/test_multi_target_part_plan_gpu.py):
+        every wide Winograd launch of the batched loop then takes the frequency split that one target's rows would choose
+        (lf_wino_fused_gemm_part), per (object, target) with a volume list as well.  Without the option lf_wino_fused_gemm
+        chooses that split from the batch's tile count and a row's rounding follows its batch mates.  Never in conv_mode
+        'f16x3' (refused together with per_target_plan): its input and gradient scales come from a batch-wide max.  (The
+        engine's ranking form -- need_grad=False, masked_depth=True, not used by this loop -- is bit-identical per target with
+        per_target_plan and proj_kernel='mfma'; with 'library' it stays within the single-target tolerance, because the
+        library picks its GEMM kernel by the row count.)  Adam
         amplifies such last-bit differences to percent-level loss differences within a few iterations.  `cameras`: T Camera
         batches of equal length; None draws initial_pose + sample_cameras_with_estimate per target, in target order.
 
@@ -793,7 +805,7 @@ class GradientPoseEstimator(PoseEstimator):
                     eng = MultiTargetEngine(self.model.photographer, z_obj if z_of is None else z_of[b:e], dev_targets[b:e],
                                             self.loss_weights,
                                             conv_mode=self.conv_mode, fuse_projection=self.fuse_projection,
-                                            proj_kernel=self.proj_kernel)
+                                            proj_kernel=self.proj_kernel, per_target_plan=self.per_target_plan)
                     out += self._run_batch(eng, dev_targets[b:e], zoomed[b:e])
                     del eng
                 return out
