@@ -589,15 +589,20 @@ int lf_grid_sample2d_bwd(const float* img, const float* grid, const float* gout,
  * dims = 3 (27 taps), 2 (9 taps, D = 1) or 0 (pointwise: one tap, rows = N*D*H*W).  x, gpre channels-last
  * [N][D][H][W][C]; gpre is the gradient w.r.t. the pre-activation (after lf_epilogue_bwd); scale = he.
  * x == NULL: all-ones single-channel input, i.e. gw[0][co][0] = sum_v gpre[v][co] (bias gradient, scale 1).
- * Deterministic: per-block partials in `scratch` (lf_conv_bwd_weight_scratch_bytes), fixed-order fp64 sum. */
+ * Deterministic: per-block partials in `scratch`, fixed-order fp64 sum.  Scratch: lf_conv_bwd_weight_scratch_bytes of the
+ * same arguments (Cin = 0 for x == NULL), LF_ENOSPC and nothing launched below it.  A buffer of that size also serves
+ * lf_conv_bwd_weight_bf16(_io) on the same shape (it is the larger of the two needs where both kernels apply). */
 size_t lf_conv_bwd_weight_scratch_bytes(int dims, int N, int D, int H, int W, int Cin, int Cout);
 int lf_conv_bwd_weight(const float* x, const float* gpre, float* gw, void* scratch, size_t scratch_bytes,
                        int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, void* stream);
 /* The same weight gradient on the bf16 MFMA (autocast policy of the training step; recon/models.py:199,405): x and gpre
  * are rounded to bf16 (RNE) as they are staged -- the identity on operands the policy has already rounded -- products
- * are exact, accumulation fp32, partials summed in a fixed order in fp64 like lf_conv_bwd_weight (same scratch size).
- * 3-D 16 -> 16 layers with N*D*H*W >= 8192, D*H*W*64 < 2^31 and (D+3)*H*W*64 < 2^32 only: LF_EINVAL otherwise (the caller
- * keeps lf_conv_bwd_weight for the rest). */
+ * are exact, accumulation fp32, partials summed in a fixed order in fp64 like lf_conv_bwd_weight.
+ * Domain: dims = 3, Cin = Cout = 16, N*D*H*W >= 8192, D*H*W*64 < 2^31 - 1 and (D+3)*H*W*64 < 2^32.
+ * lf_conv_bwd_weight_bf16_scratch_bytes returns the scratch the entries below demand (LF_ENOSPC below it) inside the domain
+ * and 0 outside it, where they return LF_EINVAL (the caller keeps lf_conv_bwd_weight for the rest); it asks nothing of the
+ * device outside the domain. */
+size_t lf_conv_bwd_weight_bf16_scratch_bytes(int dims, int N, int D, int H, int W, int Cin, int Cout);
 int lf_conv_bwd_weight_bf16(const float* x, const float* gpre, float* gw, void* scratch, size_t scratch_bytes,
                             int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, void* stream);
 /* ... with x (io & 1) and / or gpre (io & 2) stored as bf16 channels-last records (see lf_conv3d_c16_ring_bf16_io). */

@@ -212,297 +212,42 @@ __global__ void __launch_bounds__(512) wgrad3d_c16_kernel(
 
 // ---- the same product on the bf16 MFMA (autocast policy of the training step) ------------------------------------------
 // v_mfma_f32_16x16x32_bf16 contracts 32 voxels per instruction at 8x the fp32 MFMA's rate per voxel, but wants its K
-// run -- 8 consecutive voxels of ONE channel per lane -- where channels-last memory has 16 channels of one voxel: the
-// tile is transposed on its way into LDS.  A thread loads the same 16-byte quarter (4 channels) of TWO voxels adjacent
-// in x into registers, rounds to bf16 (RNE, v_cvt_pk_bf16_f32: the identity on operands autocast has already rounded),
-// and writes four dwords = the two voxels of each of its channels (v_perm) into channel-major planes.  A lane then reads
-// its 8-voxel K run with one ds_read_b128; the kx = 0, 1, 2 taps of a row come from the SAME five dwords (kx = 2: a dword
-// later; kx = 1: v_alignbyte).
-// With the MFMAs this cheap the kernel is bound by what it asks of L2 / HBM, so a workgroup walks UP a column of
-// 2 x 8 x 16 tiles and keeps the x halo in a ring of six z-plane slots ([16 ch][6 slots][10 rows][18 (+6) x] bf16): a
-// tile reads four planes, two of which the next tile reads again, so only the two new planes (and the tile's own 2 x 8 x 16
-// block of gpre, double-buffered) are fetched per tile -- 39 KB instead of 62 KB -- while the current tile is contracted.
-// Four waves; wave w owns the (kz, ky) stencil rows 2w, 2w+1 for all eight 32-voxel K groups (2 rows x 16 voxels) of the
-// tile and row 8 for K groups 2w, 2w+1: 54 MFMAs per wave and tile, nine accumulators, and only row 8 is summed across
-// waves (through LDS, fixed order) at the end.  Two workgroups per CU (62 KB of LDS each).
-// Products of bf16 operands are exact in fp32 and accumulation is fp32 as on the fp32 kernel: same result up to
-// summation order.  Partials: one 27 x 256 block per workgroup, summed by wgrad_reduce_kernel (fixed order, fp64).
+// run -- 8 consecutive voxels of ONE channel per lane -- where channels-last memory has 16 channels of one voxel.  gfx950
+// transposes on the way OUT of LDS: the tile stays in LDS as it is in memory, bf16 channels-last records of 32 B, and a lane
+// gets "channel (lane & 15) of four consecutive voxels" from one ds_read_b64_tr_b16 at the address of record
+// (voxel + (lane >> 2 & 3)), channel quad (lane & 3).  Two of them = the 8-voxel K run; a stencil shift along x is 32 B of
+// address.  Bank-conflict free by construction: an instruction's two 16-lane groups of a half-wave read the 128-byte chunks
+// x = 0..3 and 4..7 (then 8..11 and 12..15) of one row = disjoint halves of the 64 banks, whatever the row / tap offset -- so
+// the K run of lane group k is voxels {4 (k & 1) .. +3} and {4 (k & 1) + 8 .. +3} of row k >> 1 of the K group's two rows,
+// for BOTH operands.
+// Staging: fp32 operands are rounded to bf16 (RNE, v_cvt_pk_bf16_f32: the identity on operands autocast has already rounded)
+// in registers and written with plain 8-byte stores.  With the MFMAs this cheap the kernel is bound by what it asks of
+// L2 / HBM, so a workgroup walks UP a column of 2 x 8 x 16 tiles and keeps the x halo in the six-slot ring of 10 x 18-voxel
+// z-planes of the ring convolutions (ring_tile.h): a tile reads four planes, two of which the next tile reads again, so only
+// the two new planes and the tile's own 2 x 8 x 16 block of gpre (double-buffered) are fetched per tile, by waves 4..7, one
+// tile ahead of the contraction on waves 0..3.
+// Contraction wave w owns the (kz, ky) stencil rows 2w, 2w+1 for all eight 32-voxel K groups (2 rows x 16 voxels) of the tile
+// and row 8 for K groups 2w, 2w+1: 54 MFMAs per wave and tile, nine accumulators, and only row 8 is summed across waves
+// (through LDS, fixed order) at the end.  WG_TR_WGS workgroups per CU.
+// Products of bf16 operands are exact in fp32 and accumulation is fp32 as on the fp32 kernel: same result up to summation
+// order.  Partials: one 27 x 256 block per workgroup, summed by wgrad_reduce_kernel (fixed order, fp64).
+// Measured against the channel-major staging it replaced (v_perm transposes into LDS, ds_read_b128 + v_alignbyte operands:
+// two- to four-fold bank conflicts on every read): 1.92 -> 1.20 ms per 32 volumes, profiles/r06_wgrad_tr_ab.txt.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) bf16x4t lds_bf16x4t;
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 template <int I> struct WIC { static constexpr int v = I; };
 template <int B, int E, typename F>
 __device__ __forceinline__ void wstatic_for(F&& f) {
   if constexpr (B < E) { f(WIC<B>{}); wstatic_for<B + 1, E>(f); }
 }
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-#ifndef WG_ABL
-#define WG_ABL 0                                                 // ablations (tools/wgrad_ab.py): 1 no contraction, 2 no commit to LDS, 4 no loads
-#endif
-constexpr int BRING = 6;                                         // z-plane slots: 4 being read + 2 being filled
-constexpr int BRS = 48;                                          // bytes per halo row: 18 bf16 (+6)
-constexpr int BPL = WHY * BRS;                                   // 480 B per plane slot and channel
-constexpr int BXS = BRING * BPL + 16;                            // channel stride of the x planes (2896 B: 20 banks)
-constexpr int BGR = 32;                                          // bytes per gpre row: 16 bf16
-constexpr int BGS = WTZ * WTY * BGR + 16;                        // channel stride of the gpre planes (528 B)
-constexpr int BXB = 16 * BXS;                                    // 46,336 B
-constexpr int BGB = 16 * BGS;                                    // 8,448 B per gpre buffer
-constexpr int BLDS = BXB + 2 * BGB;                              // 63,232 B
-constexpr int BPP = 2 * WHY * (WHX / 2);                         // 180 voxel pairs in two halo planes
-constexpr int BXIT = (BPP * 4 + 255) / 256;                      // 3 x pair-pieces per thread and tile ...
-constexpr int BNIT = BXIT + (WTZ * WTY * WTX / 2) * 4 / 256;     // ... + 2 gpre pair-pieces
-constexpr unsigned BOOB = 0x80000000u;
-
-__device__ __forceinline__ int bmod6(int v) { return v >= 6 ? v - 6 : v; }      // v in [0, 12)
-
-// IO (round 5): bit 0 -- x, bit 1 -- gpre are stored as bf16 channels-last records (32 B per voxel) instead of fp32 ones: the
-// staging rounds fp32 operands to bf16 anyway, so operands kept rounded in memory give the same products from half the bytes.
-template <int IO>
-__global__ void __launch_bounds__(256, 2) wgrad3d_c16_bf16_kernel(
-    const float* __restrict__ x, const float* __restrict__ gp, float* __restrict__ partial,
-    int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z, int ntiles) {
-  constexpr bool X16 = (IO & 1) != 0, G16 = (IO & 2) != 0;
-  constexpr int XSH = X16 ? 5 : 6, GSH = G16 ? 5 : 6;                // log2 bytes per voxel record
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int m = lane & 15, k = lane >> 4;
-  const int nb = gridDim.x;
-  const int lb = (nb % 8 == 0) ? (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8 : blockIdx.x;   // XCD-aware ranges
-  const int per = (ntiles + nb - 1) / nb;
-  const int t_begin = lb * per;
-  const int t_end = min(t_begin + per, ntiles);
-  const long nvox = (long)D * H * W;
-  const unsigned plane_vox = (unsigned)(H * W);
-
-  f32x4 acc[9];                                                  // rows 2w, 2w+1 (x 3 kx), then this wave's share of row 8
-#pragma unroll
-  for (int t = 0; t < 9; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-  if (t_begin < t_end) {
-    const int q = lane & 3;
-    // pair-piece constants.  x pieces (it < 3): pair P of the two incoming planes = (plane P / 90, row, x pair); gpre pieces:
-    // pair of the tile's 2 x 8 x 16 block.  lxy = x | y << 8 | plane << 16 relative to the tile origin - 1 (x) / the tile
-    // origin (gpre); dst = LDS byte offset of channel 4q's dword inside slot 0 / gpre buffer 0.  The slots past the 180th
-    // pair repeat it (same data, same address), so nothing below branches on the wave.
-    int lxy[BNIT], dst[BNIT];
-#pragma unroll
-    for (int it = 0; it < BNIT; ++it) {
-      if (it < BXIT) {
-        const int pr = min((wave + 4 * it) * 16 + (lane >> 2), BPP - 1);
-        const int pl = pr / (BPP / 2), rem = pr - pl * (BPP / 2), row = rem / (WHX / 2), px = rem - row * (WHX / 2);
-        lxy[it] = (2 * px) | (row << 8) | (pl << 16);
-        dst[it] = 4 * q * BXS + row * BRS + px * 4;
-      } else {
-        const int pr = (wave + 4 * (it - BXIT)) * 16 + (lane >> 2);
-        const int lx = 2 * (pr & 7), ly = (pr >> 3) & 7, lz = pr >> 6;
-        lxy[it] = lx | (ly << 8) | (lz << 16);
-        dst[it] = BXB + 4 * q * BGS + (lz * WTY + ly) * BGR + lx * 2;
-      }
-    }
-    // per COLUMN of tiles: byte offsets inside the sample of each piece's first voxel with the incoming plane pair / the
-    // tile at z = 0, and which of its two voxels lie inside the volume in x and y (bits 2 it, 2 it + 1); the plane itself is
-    // added per tile, and planes outside [0, D) fall outside the buffer (below zero wraps) and read as zero
-    unsigned coff[BNIT];
-    unsigned okm = 0;
-    const float *cx_ptr = x, *cg_ptr = gp;
-    auto column = [&](int bx, int by, int bn) {
-      okm = 0;
-#pragma unroll
-      for (int it = 0; it < BNIT; ++it) {
-        const int halo = it < BXIT ? 1 : 0;
-        const int gx = bx * WTX - halo + (lxy[it] & 0xff), gy = by * WTY - halo + ((lxy[it] >> 8) & 0xff);
-        const int sh = halo ? XSH : GSH;
-        coff[it] = (unsigned)(((gy * W + gx) << sh) + (q << (sh - 2))) + (((unsigned)(lxy[it] >> 16) * plane_vox) << sh);
-        const bool oky = (unsigned)gy < (unsigned)H;
-        okm |= ((oky && (unsigned)gx < (unsigned)W) ? 1u : 0u) << (2 * it);
-        okm |= ((oky && (unsigned)(gx + 1) < (unsigned)W) ? 1u : 0u) << (2 * it + 1);
-      }
-      cx_ptr = x + (long)bn * nvox * (X16 ? 8 : 16);               // (declared float*: a bf16 record is 8 floats' worth of bytes)
-      cg_ptr = gp + (long)bn * nvox * (G16 ? 8 : 16);
-    };
-    u32x4 st[BNIT][2];
-    // x planes zx, zx + 1 of the column (and, with_g, the gpre block of the tile at planes zg, zg + 1) -> registers
-    auto issue = [&](int zx, int zg, bool with_g) {
-      const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)cx_ptr, 0, (unsigned)(nvox << XSH), 0x00020000);
-      const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)cg_ptr, 0, with_g ? (unsigned)(nvox << GSH) : 0u, 0x00020000);
-      const unsigned zoffx = ((unsigned)zx * plane_vox) << XSH, zoffg = ((unsigned)zg * plane_vox) << GSH;
-#pragma unroll
-      for (int it = 0; it < BNIT; ++it) {
-        const unsigned o = coff[it] + (it < BXIT ? zoffx : zoffg);
-        const int o0 = (int)(((okm >> (2 * it)) & 1u) ? o : BOOB);
-        if ((it < BXIT) ? X16 : G16) {                               // (folds after unrolling)
-          const int o1 = (int)(((okm >> (2 * it + 1)) & 1u) ? o + 32u : BOOB);
-          const u32x2 a = __builtin_amdgcn_raw_buffer_load_b64(it < BXIT ? rx : rg, o0, 0, 0);
-          const u32x2 b = __builtin_amdgcn_raw_buffer_load_b64(it < BXIT ? rx : rg, o1, 0, 0);
-          st[it][0] = (u32x4){a[0], a[1], 0u, 0u};
-          st[it][1] = (u32x4){b[0], b[1], 0u, 0u};
-        } else {
-          const int o1 = (int)(((okm >> (2 * it + 1)) & 1u) ? o + 64u : BOOB);
-          st[it][0] = __builtin_amdgcn_raw_buffer_load_b128(it < BXIT ? rx : rg, o0, 0, 0);
-          st[it][1] = __builtin_amdgcn_raw_buffer_load_b128(it < BXIT ? rx : rg, o1, 0, 0);
-        }
-      }
-    };
-    // registers -> bf16 planes: x pieces into ring slots s0 (first plane) / s1, gpre pieces into buffer gsel
-    auto commit = [&](int s0, int s1, int gsel, bool with_g) {
-#pragma unroll
-      for (int it = 0; it < BNIT; ++it) {
-        if (it >= BXIT && !with_g) continue;                       // (uniform)
-        unsigned e01, e23, o01, o23;
-        if ((it < BXIT) ? X16 : G16) {                               // already bf16 pairs
-          e01 = st[it][0][0]; e23 = st[it][0][1]; o01 = st[it][1][0]; o23 = st[it][1][1];
-        } else {
-          const f32x4 e = __builtin_bit_cast(f32x4, st[it][0]), o = __builtin_bit_cast(f32x4, st[it][1]);
-          e01 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){e[0], e[1]}, bf16x2));
-          e23 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){e[2], e[3]}, bf16x2));
-          o01 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){o[0], o[1]}, bf16x2));
-          o23 = __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2){o[2], o[3]}, bf16x2));
-        }
-        const int cs = it < BXIT ? BXS : BGS;
-        unsigned char* d = smem + dst[it] + (it < BXIT ? ((lxy[it] >> 16) ? s1 : s0) * BPL : gsel * BGB);
-        // one dword per channel: [voxel x, voxel x + 1]
-        *(unsigned*)(d) = __builtin_amdgcn_perm(o01, e01, 0x05040100u);
-        *(unsigned*)(d + cs) = __builtin_amdgcn_perm(o01, e01, 0x07060302u);
-        *(unsigned*)(d + 2 * cs) = __builtin_amdgcn_perm(o23, e23, 0x05040100u);
-        *(unsigned*)(d + 3 * cs) = __builtin_amdgcn_perm(o23, e23, 0x07060302u);
-      }
-    };
-    // operand offsets: K group kg = (plane z = kg >> 2, row pair rp = kg & 3); lane group k -> row 2*rp + (k >> 1), x half k & 1
-    const int a_lane = BXB + m * BGS + (k >> 1) * BGR + (k & 1) * 16;                             // + gsel*BGB + (z*WTY + 2*rp) * BGR
-    const int b_lane = m * BXS + (k >> 1) * BRS + (k & 1) * 16;                                   // + slot(z + kz)*BPL + (ky + 2*rp) * BRS
-    const int kz0 = (2 * wave) / 3, ky0 = (2 * wave) % 3, kz1 = (2 * wave + 1) / 3, ky1 = (2 * wave + 1) % 3;
-    auto three_taps = [&](const bf16x8 a, const unsigned char* row, f32x4* c) {
-      const u32x4 d = *(const u32x4*)row;
-      const unsigned d4 = *(const unsigned*)(row + 16);
-      const u32x4 b1 = (u32x4){__builtin_amdgcn_alignbyte(d[1], d[0], 2), __builtin_amdgcn_alignbyte(d[2], d[1], 2),
-                               __builtin_amdgcn_alignbyte(d[3], d[2], 2), __builtin_amdgcn_alignbyte(d4, d[3], 2)};
-      const u32x4 b2 = (u32x4){d[1], d[2], d[3], d4};
-      c[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, d), c[0], 0, 0, 0);
-      c[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, b1), c[1], 0, 0, 0);
-      c[2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, __builtin_bit_cast(bf16x8, b2), c[2], 0, 0, 0);
-    };
-    auto contract = [&](int rot, int gsel) {
-      // halo plane hp (0..3) of the tile sits in ring slot (rot + hp) % 6
-      const unsigned char* ab = smem + a_lane + gsel * BGB;
-      const unsigned char* r0[2], *r1[2], *r8[2];
-#pragma unroll
-      for (int z = 0; z < 2; ++z) {
-        r0[z] = smem + b_lane + bmod6(rot + z + kz0) * BPL + ky0 * BRS;
-        r1[z] = smem + b_lane + bmod6(rot + z + kz1) * BPL + ky1 * BRS;
-        r8[z] = smem + b_lane + bmod6(rot + z + 2) * BPL + 2 * BRS;
-      }
-#pragma unroll
-      for (int kg = 0; kg < 8; ++kg) {
-        const int z = kg >> 2, rp = kg & 3;
-        const bf16x8 a = *(const bf16x8*)(ab + (z * WTY + 2 * rp) * BGR);
-        three_taps(a, r0[z] + 2 * rp * BRS, acc);
-        three_taps(a, r1[z] + 2 * rp * BRS, acc + 3);
-      }
-#pragma unroll
-      for (int g = 0; g < 2; ++g) {                               // stencil row 8 = (kz, ky) = (2, 2): K groups 2w, 2w + 1
-        const int kg = 2 * wave + g, z = kg >> 2, rp = kg & 3;    // (wave-uniform)
-        const bf16x8 a = *(const bf16x8*)(ab + (z * WTY + 2 * rp) * BGR);
-        three_taps(a, (z ? r8[1] : r8[0]) + 2 * rp * BRS, acc + 6);
-      }
-    };
-
-    // tile coordinates are stepped, not divided; z fastest: the range walks up columns
-    int cx, cy, cz, cn;
-    {
-      int tt = t_begin;
-      cz = tt % tiles_z; tt /= tiles_z;
-      cx = tt % tiles_x; tt /= tiles_x;
-      cy = tt % tiles_y; cn = tt / tiles_y;
-    }
-    int rot = 0;
-    column(cx, cy, cn);
-    issue(cz * WTZ - 1, 0, false);
-    __builtin_amdgcn_sched_barrier(0);
-    commit(0, 1, 0, false);
-    issue(cz * WTZ + 1, cz * WTZ, true);
-    __builtin_amdgcn_sched_barrier(0);
-    commit(2, 3, 0, true);
-    __syncthreads();
-    for (int t = t_begin; t < t_end; ++t) {
-      const int gsel = (t - t_begin) & 1;
-      int nx = cx, ny = cy, nz = cz + 1, nn = cn;
-      if (nz == tiles_z) { nz = 0; ++nx; }
-      if (nx == tiles_x) { nx = 0; ++ny; }
-      if (ny == tiles_y) { ny = 0; ++nn; }
-      const bool on = t + 1 < t_end;
-      const bool slide = on && nz != 0;
-      if (on) {
-        if (!slide) column(nx, ny, nn);
-        // the two planes the next tile adds (slide: its halo planes 2, 3; new column: its planes 0, 1) and its gpre block
-        if (!(WG_ABL & 4)) issue(nz * WTZ - 1 + (slide ? 2 : 0), nz * WTZ, true);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      if (!(WG_ABL & 1)) contract(rot, gsel);
-      __builtin_amdgcn_sched_barrier(0);
-      if (on && !(WG_ABL & 2)) commit(bmod6(rot + 4), bmod6(rot + 5), gsel ^ 1, true);
-      __syncthreads();                                          // this tile's planes 0, 1 are free; the new planes are visible
-      if (on && !slide) {
-        // bottom of a new column: what arrived are its planes 0, 1 (slots rot+4, rot+5); planes 2, 3 go to the slots this
-        // tile has just released (exposed once per column)
-        rot = bmod6(rot + 4);
-        issue(nz * WTZ + 1, 0, false);
-        __builtin_amdgcn_sched_barrier(0);
-        commit(bmod6(rot + 2), bmod6(rot + 3), 0, false);
-        __syncthreads();
-      } else {
-        rot = bmod6(rot + 2);
-      }
-      cx = nx; cy = ny; cz = nz; cn = nn;
-    }
-  }
-  // row 8 (taps 24..26): waves 1..3 hand their shares to wave 0 through LDS, summed in wave order
-  f32x4* red = (f32x4*)smem;                                    // [wave - 1][3][64 lanes]
-  __syncthreads();
-  if (wave > 0) {
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) red[((wave - 1) * 3 + kx) * 64 + lane] = acc[6 + kx];
-  }
-  __syncthreads();
-  if (wave == 0) {
-#pragma unroll
-    for (int w = 0; w < 3; ++w)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) acc[6 + kx] += red[(w * 3 + kx) * 64 + lane];
-  }
-  float* out = partial + (long)blockIdx.x * 27 * 256;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    if (r == 2 && wave != 0) break;
-    const int zy = r == 2 ? 8 : 2 * wave + r;
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) out[(zy * 3 + kx) * 256 + (4 * k + i) * 16 + m] = acc[r * 3 + kx][i];
-  }
-}
-
-// ---- round 6: the same contraction with the operands read by the LDS TRANSPOSE load (ds_read_b64_tr_b16) ------------------
-// PMC on the kernel above: SQ_LDS_BANK_CONFLICT = 0.68 of SQ_LDS_IDX_ACTIVE, LDS issue stalls + waits = 0.7 of the wave cycles
-// -- its channel-major planes (strides chosen for 32 banks; ds_read_b128 sees 64) conflict two-fold on every operand read,
-// four-fold on the fifth-dword reads, and the transposing commit (v_perm + four ds_write_b32 per pair-piece) conflicts too;
-// the contraction alone takes 1.67 of the 1.92 ms per 32 volumes (tools/wgrad_ab.py, -DWG_ABL).  gfx950 can transpose on the
-// way OUT of LDS instead: the tile stays in LDS as it is in memory, bf16 channels-last records of 32 B (x: the six-slot
-// ring of 10 x 18-voxel halo planes of the ring convolutions, conv_split.hip; gpre: the 2 x 8 x 16 block, double-buffered),
-// written with plain 8-byte stores, and a lane gets "channel (lane & 15) of four consecutive voxels" from one
-// ds_read_b64_tr_b16 at the address of record (voxel + (lane >> 2 & 3)), channel quad (lane & 3).  Two of them = the
-// 8-voxel K run of v_mfma_f32_16x16x32_bf16; a stencil shift along x is 32 B of address, not a v_alignbyte.  Bank-conflict
-// free by construction: an instruction's two 16-lane groups of a half-wave read the 128-byte chunks x = 0..3 and 4..7
-// (then 8..11 and 12..15) of one row = disjoint halves of the 64 banks, whatever the row / tap offset -- so the K run of
-// lane group k is voxels {4 (k & 1) .. +3} and {4 (k & 1) + 8 .. +3} of row k >> 1 of the K group's two rows, for BOTH
-// operands.  Wave / accumulator assignment, partials and the reduce kernel are those of the kernel above (bit-compatible
-// up to the order of the products inside one MFMA's K = 32, which is exact in fp32: same results).
-typedef __bf16 bf16x4t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) bf16x4t lds_bf16x4t;
 constexpr int TXP = RINGs * PLANE_B;                              // 34,560 B: the x ring
 constexpr int TGB = WTZ * WTY * WTX * 32;                         // 8,192 B per gpre buffer
 constexpr int TLDS = TXP + 2 * TGB + 1024;                        // + guard: a shifted K run of the last row reads past its plane
+
+__device__ __forceinline__ int bmod6(int v) { return v >= 6 ? v - 6 : v; }      // v in [0, 12)
 
 __device__ __forceinline__ bf16x8 tr_pair(const unsigned char* p0, const unsigned char* p1) {
   const bf16x4t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4t*)p0);
@@ -510,8 +255,9 @@ __device__ __forceinline__ bf16x8 tr_pair(const unsigned char* p0, const unsigne
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// -D switches of tools/wgrad_ab.py
 #ifndef WG_ABL
-#define WG_ABL 0                                                 // ablations of the kernel below (tools/wgrad_ab.py): 1 no contraction, 2 no commit to LDS, 4 no loads
+#define WG_ABL 0                                                 // ablations: 1 no contraction, 2 no commit to LDS, 4 no loads
 #endif
 #ifndef WG_TR_PF
 #define WG_TR_PF 1                                                // contraction steps whose operand reads are in flight ahead of the MFMAs
@@ -519,6 +265,8 @@ __device__ __forceinline__ bf16x8 tr_pair(const unsigned char* p0, const unsigne
 #ifndef WG_TR_WGS
 #define WG_TR_WGS 2                                               // resident workgroups per CU (8 waves each: 53 KB of LDS, <= 128 VGPRs)
 #endif
+// IO: bit 0 -- x, bit 1 -- gpre are stored as bf16 channels-last records (32 B per voxel) instead of fp32 ones: the staging
+// rounds fp32 operands to bf16 anyway, so operands kept rounded in memory give the same products from half the bytes.
 template <int IO>
 __global__ void __launch_bounds__(512, 2 * WG_TR_WGS) wgrad3d_c16_tr_kernel(
     const float* __restrict__ x, const float* __restrict__ gp, float* __restrict__ partial,
@@ -829,15 +577,71 @@ bool wgrad_plan(int dims, long total, int Cin, int Cout, bool ones, WgradPlan& p
 
 }  // namespace
 
-static bool wgrad_fast3d(int dims, int N, int D, int H, int W, int Cin, int Cout) {
-  return dims == 3 && Cin == 16 && Cout == 16 && (long)D * H * W * 64 < 0x7fffffffL && (long)N * D * H * W >= 8192;
+// ---- host side of the two tiled 3-D 16 -> 16 kernels: one plan, one launch path ------------------------------------------------
+// Domain, tile walk, block counts and scratch of both forms, from the shape alone; the entry points, their scratch queries and
+// the launch below all read it.  The domain is decided before anything asks the device (the block counts need its CU count).
+enum { WG16_FP32 = 0, WG16_BF16 = 1 };
+struct Wgrad16Plan {
+  bool ok[2];                                                      // the shape is in the form's domain
+  int tiles_x, tiles_y, tiles_z, ntiles;                           // 2 x 8 x 16-voxel tiles per axis, and over all samples
+  int nblk[2];                                                     // workgroups = 27 x 256 partial blocks the reduce sums
+  size_t bytes[2];                                                 // scratch the form needs (0 outside its domain)
+  size_t max_bytes() const { return bytes[0] > bytes[1] ? bytes[0] : bytes[1]; }
+};
+
+static Wgrad16Plan wgrad16_plan(int dims, int N, int D, int H, int W, int Cin, int Cout) {
+  Wgrad16Plan p = {};
+  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || dims != 3 || Cin != 16 || Cout != 16) return p;
+  // 32-bit byte offsets inside a sample; small problems stay on the generic kernel
+  if ((long)D * H * W * 64 >= 0x7fffffffL || (long)N * D * H * W < 8192) return p;
+  p.tiles_x = (W + WTX - 1) / WTX; p.tiles_y = (H + WTY - 1) / WTY; p.tiles_z = (D + WTZ - 1) / WTZ;
+  const long pt = (long)p.tiles_x * p.tiles_y * p.tiles_z * N;
+  if (pt > 0x7fffffffL) return p;
+  p.ntiles = (int)pt;
+  p.ok[WG16_FP32] = true;
+  // the bf16 kernel's 32-bit offsets reach three planes past the sample (halo planes of the last tile + the pair's second plane)
+  p.ok[WG16_BF16] = (long)(D + 3) * H * W * 64 <= 0xffffffffL;
+  const int cus = lf_cu_count();
+  p.nblk[WG16_FP32] = cus;                                         // one workgroup per CU (2 x 62 KB of LDS)
+  p.nblk[WG16_BF16] = WG_TR_WGS * cus;
+  for (int f = 0; f < 2; ++f) p.bytes[f] = p.ok[f] ? (size_t)p.nblk[f] * 27 * 256 * sizeof(float) : 0;
+  return p;
 }
 
+// The tiled kernel of `form` (bf16: storage variant io) over the plan's tiles, then the fixed-order sum of its blocks.  Every
+// workgroup writes its 27 x 256 block (zeros when it has no tiles), so the grid is always the plan's block count.  The caller
+// has checked p.ok[form], the scratch size and the operands' alignment.
+static int wgrad16_launch(const Wgrad16Plan& p, int form, int io, const void* x, const void* gpre, float* gw, void* scratch,
+                          int N, int D, int H, int W, float scale, hipStream_t s) {
+  typedef void (*kern_t)(const float*, const float*, float*, int, int, int, int, int, int, int, int);
+  struct Kern { kern_t fn; int lds; lf_devmask_t attr_set; };      // (both forms: 512 threads)
+  static Kern kerns[5] = {{wgrad3d_c16_kernel, 2 * WBUF}, {wgrad3d_c16_tr_kernel<0>, TLDS}, {wgrad3d_c16_tr_kernel<1>, TLDS},
+                          {wgrad3d_c16_tr_kernel<2>, TLDS}, {wgrad3d_c16_tr_kernel<3>, TLDS}};
+  Kern& k = kerns[form == WG16_FP32 ? 0 : 1 + io];
+  const hipError_t e = lf_ensure_dyn_lds(k.attr_set, (const void*)k.fn, k.lds);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(k.fn, dim3(p.nblk[form]), dim3(512), (size_t)k.lds, s, (const float*)x, (const float*)gpre, (float*)scratch,
+                     N, D, H, W, p.tiles_x, p.tiles_y, p.tiles_z, p.ntiles);
+  const int st = lf_launch_status();
+  if (st) return st;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(27, 1, 4), dim3(256), 0, s, (const float*)scratch, gw, p.nblk[form], 27, 1, 1, 16, 16,
+                     scale);
+  return lf_launch_status();
+}
+
+// Scratch contract of lf_conv_bwd_weight: at least this much, whichever kernel the call takes -- the tiled 16 -> 16 kernel
+// (where the size is the larger of the two forms' needs, so that one buffer also serves the bf16 entries on the same shape),
+// the generic kernel (also the fall-back for operands that are not 16-byte aligned) or the bias column sums, which need less.
 extern "C" size_t lf_conv_bwd_weight_scratch_bytes(int dims, int N, int D, int H, int W, int Cin, int Cout) {
-  if (wgrad_fast3d(dims, N, D, H, W, Cin, Cout)) return (size_t)lf_cu_count() * 8 * 27 * 256 * sizeof(float);
+  const size_t tiled = wgrad16_plan(dims, N, D, H, W, Cin, Cout).max_bytes();
   WgradPlan p;
-  if (!wgrad_plan(dims, (long)N * D * H * W, Cin > 0 ? Cin : 1, Cout, Cin <= 0, p)) return 0;
-  return (size_t)p.nblk * p.taps * p.nct * p.ncit * 256 * sizeof(float);
+  const bool gen = wgrad_plan(dims, (long)N * D * H * W, Cin > 0 ? Cin : 1, Cout, Cin <= 0, p);
+  const size_t generic = gen ? (size_t)p.nblk * p.taps * p.nct * p.ncit * 256 * sizeof(float) : 0;
+  return tiled > generic ? tiled : generic;
+}
+
+extern "C" size_t lf_conv_bwd_weight_bf16_scratch_bytes(int dims, int N, int D, int H, int W, int Cin, int Cout) {
+  return wgrad16_plan(dims, N, D, H, W, Cin, Cout).bytes[WG16_BF16];
 }
 
 extern "C" int lf_conv_bwd_weight(const float* x, const float* gpre, float* gw, void* scratch, size_t scratch_bytes,
@@ -845,6 +649,8 @@ extern "C" int lf_conv_bwd_weight(const float* x, const float* gpre, float* gw, 
   lf_clear_error();
   if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || gpre == nullptr || gw == nullptr) return LF_EINVAL;
   const bool ones = (x == nullptr);
+  if (scratch_bytes < lf_conv_bwd_weight_scratch_bytes(dims, N, D, H, W, ones ? 0 : Cin, Cout)) return LF_ENOSPC;   // the contract
+  // ... and every path checks what its own launch writes
   if (ones && Cout == 16 && lf_aligned16(gpre)) {
     const long rows = (long)N * D * H * W;
     long chunk = (rows + 1023) / 1024;                            // ~1024 blocks: four per CU keep enough loads in flight
@@ -858,27 +664,12 @@ extern "C" int lf_conv_bwd_weight(const float* x, const float* gpre, float* gw, 
     hipLaunchKernelGGL(colsum16_final_kernel, dim3(1), dim3(256), 0, s, (const float*)scratch, nblk, gw, scale);
     return lf_launch_status();
   }
-  if (!ones && wgrad_fast3d(dims, N, D, H, W, Cin, Cout) && lf_aligned16(x) && lf_aligned16(gpre)) {
-    const int cus = lf_cu_count();
-    if (scratch_bytes < (size_t)cus * 8 * 27 * 256 * sizeof(float)) return LF_ENOSPC;
-    const int ptx = (W + WTX - 1) / WTX, pty = (H + WTY - 1) / WTY, ptz = (D + WTZ - 1) / WTZ;
-    const long pt = (long)ptx * pty * ptz * N;
-    if (pt > 0x7fffffffL) return LF_EINVAL;
-    const size_t shmem = (size_t)2 * WBUF;
-    static lf_devmask_t attr_set;
-    {
-      hipError_t e = lf_ensure_dyn_lds(attr_set, (const void*)wgrad3d_c16_kernel, (int)shmem);
-      if (e != hipSuccess) return (int)e;
+  if (!ones && lf_aligned16(x) && lf_aligned16(gpre)) {
+    const Wgrad16Plan p16 = wgrad16_plan(dims, N, D, H, W, Cin, Cout);
+    if (p16.ok[WG16_FP32]) {
+      if (scratch_bytes < p16.bytes[WG16_FP32]) return LF_ENOSPC;
+      return wgrad16_launch(p16, WG16_FP32, 0, x, gpre, gw, scratch, N, D, H, W, scale, (hipStream_t)stream);
     }
-    hipStream_t s = (hipStream_t)stream;
-    // every workgroup writes its 8 x 27 x 256 partials (zeros when it has no tiles), so the grid is always `cus`
-    hipLaunchKernelGGL(wgrad3d_c16_kernel, dim3(cus), dim3(512), shmem, s, x, gpre, (float*)scratch, N, D, H, W, ptx, pty,
-                       ptz, (int)pt);
-    int st = lf_launch_status();
-    if (st) return st;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(27, 1, 4), dim3(256), 0, s, (const float*)scratch, gw, cus, 27, 1, 1, 16, 16,
-                       scale);
-    return lf_launch_status();
   }
   if (ones) Cin = 1;
   WgradPlan p;
@@ -900,58 +691,17 @@ extern "C" int lf_conv_bwd_weight(const float* x, const float* gpre, float* gw, 
   return lf_launch_status();
 }
 
-static int wgrad_bf16_launch(const void* x, const void* gpre, float* gw, void* scratch, size_t scratch_bytes,
-                             int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, int io, void* stream);
+extern "C" int lf_conv_bwd_weight_bf16_io(const void* x, const void* gpre, float* gw, void* scratch, size_t scratch_bytes,
+                                          int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, int io, void* stream) {
+  lf_clear_error();
+  if (x == nullptr || gpre == nullptr || gw == nullptr || io < 0 || io > 3) return LF_EINVAL;
+  const Wgrad16Plan p = wgrad16_plan(dims, N, D, H, W, Cin, Cout);
+  if (!p.ok[WG16_BF16] || !lf_aligned16(x) || !lf_aligned16(gpre)) return LF_EINVAL;
+  if (scratch_bytes < p.bytes[WG16_BF16]) return LF_ENOSPC;
+  return wgrad16_launch(p, WG16_BF16, io, x, gpre, gw, scratch, N, D, H, W, scale, (hipStream_t)stream);
+}
 
 extern "C" int lf_conv_bwd_weight_bf16(const float* x, const float* gpre, float* gw, void* scratch, size_t scratch_bytes,
                                        int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, void* stream) {
-  return wgrad_bf16_launch(x, gpre, gw, scratch, scratch_bytes, dims, N, D, H, W, Cin, Cout, scale, 0, stream);
-}
-
-extern "C" int lf_conv_bwd_weight_bf16_io(const void* x, const void* gpre, float* gw, void* scratch, size_t scratch_bytes,
-                                          int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, int io, void* stream) {
-  if (io < 0 || io > 3) return LF_EINVAL;
-  return wgrad_bf16_launch(x, gpre, gw, scratch, scratch_bytes, dims, N, D, H, W, Cin, Cout, scale, io, stream);
-}
-
-static int wgrad_bf16_launch(const void* x, const void* gpre, float* gw, void* scratch, size_t scratch_bytes,
-                             int dims, int N, int D, int H, int W, int Cin, int Cout, float scale, int io, void* stream) {
-  lf_clear_error();
-  if (N <= 0 || D <= 0 || H <= 0 || W <= 0 || x == nullptr || gpre == nullptr || gw == nullptr) return LF_EINVAL;
-  if (!wgrad_fast3d(dims, N, D, H, W, Cin, Cout) || !lf_aligned16(x) || !lf_aligned16(gpre)) return LF_EINVAL;
-  // the kernel's 32-bit offsets reach three planes past the sample (halo planes of the last tile + the pair's second plane)
-  if ((long)(D + 3) * H * W * 64 > 0xffffffffL) return LF_EINVAL;
-#ifdef WG_OLD
-  const int nb = 2 * lf_cu_count();
-#else
-  const int nb = WG_TR_WGS * lf_cu_count();
-#endif
-  if (scratch_bytes < (size_t)nb * 27 * 256 * sizeof(float)) return LF_ENOSPC;
-  const int ptx = (W + WTX - 1) / WTX, pty = (H + WTY - 1) / WTY, ptz = (D + WTZ - 1) / WTZ;
-  const long pt = (long)ptx * pty * ptz * N;
-  if (pt > 0x7fffffffL) return LF_EINVAL;
-  typedef void (*kern_t)(const float*, const float*, float*, int, int, int, int, int, int, int, int);
-#ifdef WG_OLD                                                      // (A/B: the channel-major kernel of rounds 2-5, tools/wgrad_ab.py)
-  const size_t shmem = (size_t)BLDS;
-  static const kern_t kerns[4] = {wgrad3d_c16_bf16_kernel<0>, wgrad3d_c16_bf16_kernel<1>, wgrad3d_c16_bf16_kernel<2>, wgrad3d_c16_bf16_kernel<3>};
-#else
-  const size_t shmem = (size_t)TLDS;
-  static const kern_t kerns[4] = {wgrad3d_c16_tr_kernel<0>, wgrad3d_c16_tr_kernel<1>, wgrad3d_c16_tr_kernel<2>, wgrad3d_c16_tr_kernel<3>};
-#endif
-  static lf_devmask_t attr_set[4];
-  {
-    hipError_t e = lf_ensure_dyn_lds(attr_set[io], (const void*)kerns[io], (int)shmem);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipStream_t s = (hipStream_t)stream;
-#ifdef WG_OLD
-  const unsigned threads = 256;
-#else
-  const unsigned threads = 512;                                   // four contraction waves + four staging waves
-#endif
-  hipLaunchKernelGGL(kerns[io], dim3(nb), dim3(threads), shmem, s, (const float*)x, (const float*)gpre, (float*)scratch, N, D, H, W, ptx, pty, ptz, (int)pt);
-  int st = lf_launch_status();
-  if (st) return st;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(27, 1, 4), dim3(256), 0, s, (const float*)scratch, gw, nb, 27, 1, 1, 16, 16, scale);
-  return lf_launch_status();
+  return lf_conv_bwd_weight_bf16_io(x, gpre, gw, scratch, scratch_bytes, dims, N, D, H, W, Cin, Cout, scale, 0, stream);
 }

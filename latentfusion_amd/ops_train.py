@@ -2,6 +2,7 @@
 weight / bias gradients, the 16 -> 16 layers and resampler under the bf16 autocast + storage policy, the ConvGRU fuser as one
 autograd node, the fused lift.  Reached through `ops.<name>` (ops.__getattr__) and through ops' dispatchers (conv3x3, conv1x1,
 resample_*, lift), which pick these forms when a gradient is wanted / the policy is on."""
+import contextlib
 import functools
 import math  # noqa: F401
 
@@ -142,30 +143,19 @@ def _resample_ac_ok(vol, coef):
             and max(vol.shape[2:]) < 0x7fff)
 
 
-def bias_grad(gp, dims):
-    """Column sums of the pre-activation gradient = d(loss)/d(bias) (lf_conv_bwd_weight with x == NULL).
-    gp: channels-last (N,C,[D,]H,W), or a plain [rows][C] matrix for dims = 0."""
-    L = _lib.lib()
+def _geom(t, dims):
+    """(N, D, H, W, C) of a channels-last (N,C,[D,]H,W) tensor, or of a plain [rows][C] matrix (rows as W) for dims = 0."""
     if dims == 0:
-        rows, cout = gp.shape[0], gp.shape[1]
-        N, D, H, W = 1, 1, 1, rows
-    else:
-        N, cout = gp.shape[0], gp.shape[1]
-        D, H, W = (gp.shape[2:] if dims == 3 else (1,) + tuple(gp.shape[2:]))
-    gb = torch.empty(1, cout, 1, device=gp.device, dtype=torch.float32)
-    nbytes = L.lf_conv_bwd_weight_scratch_bytes(0, N, D, H, W, 0, cout)
-    scratch = torch.empty(nbytes // 4 + 1, device=gp.device, dtype=torch.float32)
-    check(L.lf_conv_bwd_weight(None, _ptr(gp), _ptr(gb), _ptr(scratch, True), scratch.numel() * 4, 0, N, D, H, W, 0, cout,
-                               1.0, _stream()), 'lf_conv_bwd_weight')
-    return gb.reshape(cout)
+        return 1, 1, 1, t.shape[0], t.shape[1]
+    D, H, W = t.shape[2:] if dims == 3 else (1,) + tuple(t.shape[2:])
+    return t.shape[0], D, H, W, t.shape[1]
 
 
 def _wgrad_bf16_ok(gp, dims, cin, cout):
-    """Shapes lf_conv_bwd_weight_bf16 takes (the rest stays on lf_conv_bwd_weight with pre-rounded operands)."""
-    if not (dims == 3 and cin == 16 and cout == 16 and gp.numel() // gp.shape[1] >= 8192):
-        return False
-    D, H, W = gp.shape[2:]
-    return D * H * W * 64 < 2 ** 31 and (D + 3) * H * W * 64 <= 0xffffffff
+    """Shapes lf_conv_bwd_weight_bf16(_io) takes: its scratch query is non-zero there (include/lf_hip.h states the domain;
+    the rest stays on lf_conv_bwd_weight with pre-rounded operands)."""
+    N, D, H, W, _ = _geom(gp, dims)
+    return _lib.lib().lf_conv_bwd_weight_bf16_scratch_bytes(dims, N, D, H, W, cin, cout) != 0
 
 
 def _wide_wgrad_ok(x, gp, dims, cin, cout):
@@ -174,12 +164,64 @@ def _wide_wgrad_ok(x, gp, dims, cin, cout):
             and x.data_ptr() % 16 == 0 and gp.data_ptr() % 16 == 0)
 
 
+class _Wgrad:
+    """A weight-gradient launch planned once and made many times.  The shape fixes the route (`entry`): the wide kernel when
+    the caller says the operands qualify (`wide`: _wide_wgrad_ok), the bf16 MFMA when both operands are bf16 values (`bf16`) and
+    the shape is in its domain, else lf_conv_bwd_weight.  `scratch` is what that entry point's own query asks (with `bias`, or
+    for cin = 0, also what the bias launch asks), allocated here and shared by every call: calls on one stream are in order."""
+    WIDE, BF16, GENERIC = 'lf_conv_bwd_weight_wide', 'lf_conv_bwd_weight_bf16_io', 'lf_conv_bwd_weight'
+
+    def __init__(self, dims, N, D, H, W, cin, cout, device, he, bf16=False, wide=False, bias=False):
+        L = _lib.lib()
+        self.dims, self.sp, self.cin, self.cout, self.he = dims, (D, H, W), cin, cout, he
+        shape = (dims, N, D, H, W, cin, cout)
+        self.entry, nbytes = None, 0
+        if cin and wide:
+            self.entry, nbytes = self.WIDE, L.lf_conv_bwd_weight_wide_scratch_bytes(*shape)
+        elif cin:
+            nbytes = L.lf_conv_bwd_weight_bf16_scratch_bytes(*shape) if bf16 else 0
+            self.entry = self.BF16 if nbytes else self.GENERIC
+            nbytes = nbytes or L.lf_conv_bwd_weight_scratch_bytes(*shape)
+        if bias or not cin:
+            nbytes = max(nbytes, L.lf_conv_bwd_weight_scratch_bytes(0, N, D, H, W, 0, cout))
+        self.scratch = torch.empty(nbytes // 4 + 4, device=device, dtype=torch.float32)
+
+    def _launch(self, entry, x, gp, out, dims, cin, he, *io):
+        N = gp.shape[0] if self.dims else 1
+        check(getattr(_lib.lib(), entry)(_ptr(x) if x is not None else None, _ptr(gp), _ptr(out), _ptr(self.scratch, True),
+                                         self.scratch.numel() * 4, dims, N, *self.sp, cin, self.cout, he, *io, _stream()), entry)
+
+    def __call__(self, x, gp, out):
+        """out [taps][cout][cin] = he * sum_v gp[v] x[v + tap] on the current stream.  The bf16 entry takes either operand in fp32
+        or bf16 storage, and fewer samples than planned (its scratch does not depend on N); the others read fp32."""
+        if self.entry == self.BF16:
+            io = ((1 if x.dtype == torch.bfloat16 else 0) | (2 if gp.dtype == torch.bfloat16 else 0),)
+        elif x.dtype != torch.float32 or gp.dtype != torch.float32:
+            raise TypeError(f'{self.entry} reads fp32 operands')
+        else:
+            io = ()
+        with _timed('wgrad_wide', f'{self.dims}:{self.cin}:{self.cout}') if self.entry == self.WIDE else contextlib.nullcontext():
+            self._launch(self.entry, x, gp, out, self.dims, self.cin, self.he, *io)
+
+    def bias(self, gp, gb):
+        """gb [cout] = column sums of gp (lf_conv_bwd_weight with x == NULL) on the same scratch."""
+        self._launch(self.GENERIC, None, gp, gb, 0, 0, 1.0)
+
+
+def bias_grad(gp, dims):
+    """Column sums of the pre-activation gradient = d(loss)/d(bias) (lf_conv_bwd_weight with x == NULL).
+    gp: channels-last (N,C,[D,]H,W), or a plain [rows][C] matrix for dims = 0."""
+    N, D, H, W, cout = _geom(gp, dims)
+    gb = torch.empty(1, cout, 1, device=gp.device, dtype=torch.float32)
+    _Wgrad(dims, N, D, H, W, 0, cout, gp.device, 1.0).bias(gp, gb)
+    return gb.reshape(cout)
+
+
 def conv_bwd_weight(x, gp, dims, cin, he, want_bias=True, bf16=None):
     """Weight and bias gradients of y = conv(x, W) * he + b from the pre-activation gradient `gp`
     (lf_conv_bwd_weight).  x, gp: channels-last (N,C,[D,]H,W), or plain [rows][C] matrices for dims = 0.
     Returns (gw [taps][Cout][Cin], gb [Cout] or None when want_bias is False).  bf16: both operands are bf16 values (None:
-    the ambient autocast policy) -- 3-D 16 -> 16 layers then run on the bf16 MFMA (lf_conv_bwd_weight_bf16)."""
-    L = _lib.lib()
+    the ambient autocast policy) -- 3-D 16 -> 16 layers then run on the bf16 MFMA (lf_conv_bwd_weight_bf16_io)."""
     if bf16 is None:
         bf16 = ops.AUTOCAST is not None
     if dims == 3 and gp.shape[1] == 16 and cin > 16:
@@ -200,36 +242,14 @@ def conv_bwd_weight(x, gp, dims, cin, he, want_bias=True, bf16=None):
             gb = gb_c if c0 == 0 else gb                       # the bias gradient (column sums of gp) once, not per chunk
             parts.append(gw_c)
         return torch.cat(parts, dim=2), gb
-    if dims == 0:
-        rows, cout = gp.shape[0], gp.shape[1]
-        N, D, H, W = 1, 1, 1, rows
-    else:
-        N, cout = gp.shape[0], gp.shape[1]
-        D, H, W = (gp.shape[2:] if dims == 3 else (1,) + tuple(gp.shape[2:]))
-    taps = {0: 1, 2: 9, 3: 27}[dims]
-    gw = torch.empty(taps, cout, cin, device=gp.device, dtype=torch.float32)
-    gb = torch.empty(1, cout, 1, device=gp.device, dtype=torch.float32) if want_bias else None
-    wide = _wide_wgrad_ok(x, gp, dims, cin, cout)
-    nbytes = max(L.lf_conv_bwd_weight_wide_scratch_bytes(dims, N, D, H, W, cin, cout) if wide else
-                 L.lf_conv_bwd_weight_scratch_bytes(dims, N, D, H, W, cin, cout),
-                 L.lf_conv_bwd_weight_scratch_bytes(0, N, D, H, W, 0, cout))
-    scratch = torch.empty(nbytes // 4 + 4, device=gp.device, dtype=torch.float32)
-    if wide:
-        # wide layers: 64 x 64 channel tiles staged in LDS (products exact, so the autocast policy's operands too)
-        with _timed('wgrad_wide', f'{dims}:{cin}:{cout}'):
-            check(L.lf_conv_bwd_weight_wide(_ptr(x), _ptr(gp), _ptr(gw), _ptr(scratch, True), scratch.numel() * 4, dims, N, D, H, W,
-                                            cin, cout, he, _stream()), 'lf_conv_bwd_weight_wide')
-    elif bf16 and _wgrad_bf16_ok(gp, dims, cin, cout):
-        # autocast: both operands are bf16 values -- the bf16 MFMA forms the same exact products 8x faster
-        check(L.lf_conv_bwd_weight_bf16(_ptr(x), _ptr(gp), _ptr(gw), _ptr(scratch, True), scratch.numel() * 4, dims, N, D, H, W, cin, cout,
-                                        he, _stream()), 'lf_conv_bwd_weight_bf16')
-    else:
-        check(L.lf_conv_bwd_weight(_ptr(x), _ptr(gp), _ptr(gw), _ptr(scratch, True), scratch.numel() * 4, dims, N, D, H, W, cin, cout,
-                                   he, _stream()), 'lf_conv_bwd_weight')
+    N, D, H, W, cout = _geom(gp, dims)
+    gw = torch.empty({0: 1, 2: 9, 3: 27}[dims], cout, cin, device=gp.device, dtype=torch.float32)
+    wg = _Wgrad(dims, N, D, H, W, cin, cout, gp.device, he, bf16=bf16, wide=_wide_wgrad_ok(x, gp, dims, cin, cout), bias=want_bias)
+    wg(x, gp, gw)
     if not want_bias:
         return gw, None
-    check(L.lf_conv_bwd_weight(None, _ptr(gp), _ptr(gb), _ptr(scratch, True), scratch.numel() * 4, 0, N, D, H, W, 0, cout,
-                               1.0, _stream()), 'lf_conv_bwd_weight')
+    gb = torch.empty(1, cout, 1, device=gp.device, dtype=torch.float32)
+    wg.bias(gp, gb)
     return gw, gb.reshape(cout)
 
 
@@ -376,23 +396,20 @@ class _Conv16AC(torch.autograd.Function):
             side = done = None
             if fast:
                 # the weight gradient first, on the side stream (WGRAD_STREAM): it then runs beside the data gradient below
-                L = _lib.lib()
-                N, _, D, H, W = gp.shape
+                N, D, H, W, _ = _geom(gp, 3)
                 gwt = torch.empty(27, 16, 16, device=gp.device, dtype=torch.float32)
-                nb = L.lf_conv_bwd_weight_scratch_bytes(3, N, D, H, W, 16, 16)
-                scr = torch.empty(nb // 4 + 1, device=gp.device, dtype=torch.float32)
+                wg = _Wgrad(3, N, D, H, W, 16, 16, gp.device, ctx.he, bf16=True)
                 io = (1 if x_saved.dtype == torch.bfloat16 else 0) | 2
                 main = torch.cuda.current_stream()
                 if WGRAD_STREAM and ops.KERNEL_TIMER is None:
                     side = side_stream(gp.device)
                     side.wait_stream(main)                    # gp (and the allocations above) are ready
                 with torch.cuda.stream(side) if side is not None else _timed('wgrad3d_c16_bf16', f'{N}:io{io}'):
-                    check(L.lf_conv_bwd_weight_bf16_io(_ptr(x_saved), _ptr(gp), _ptr(gwt), _ptr(scr, True), scr.numel() * 4, 3, N, D, H, W, 16, 16,
-                                                       ctx.he, io, _stream()), 'lf_conv_bwd_weight_bf16_io')
+                    wg(x_saved, gp, gwt)
                     if side is not None:
                         done = torch.cuda.Event()
                         done.record(side)
-                        for t in (x_saved, gp, gwt, scr):
+                        for t in (x_saved, gp, gwt, wg.scratch):
                             t.record_stream(side)
             if ctx.needs_input_grad[0] and ctx.pw and gp.dtype == torch.bfloat16:
                 # pointwise data gradient (+ this layer's bias gradient when nothing ran before it): one streamed pass
@@ -798,20 +815,12 @@ class _GruFuse(torch.autograd.Function):
         acc = [empty_cl(shape1, dev).zero_() for _ in range(3)] if need_w else [None] * 3
         # weight-gradient blocks [step][gate][z | state][27][16][16], summed over the steps at the end (fixed order)
         gwb = torch.zeros(max(V - 1, 1), 3, 2, 27, 16, 16, device=dev, dtype=torch.float32) if need_w else None
-        nbytes = max(L.lf_conv_bwd_weight_scratch_bytes(3, 1, D, H, W, 16, 16), L.lf_conv_bwd_weight_scratch_bytes(0, 1, D, H, W, 0, 16))
-        scratch = torch.empty(nbytes // 4 + 1, device=dev, dtype=torch.float32) if need_w else None
-        fast = _wgrad_bf16_ok(zz[0:1], 3, 16, 16)
+        wg = _Wgrad(3, 1, D, H, W, 16, 16, dev, he, bf16=ac) if need_w else None      # (one scratch: the launches are in order)
 
         def wgrad(x, gp, dst):
-            if ac and fast:
-                io = (1 if x.dtype == torch.bfloat16 else 0) | (2 if gp.dtype == torch.bfloat16 else 0)
-                check(L.lf_conv_bwd_weight_bf16_io(_ptr(x), _ptr(gp), _ptr(dst), _ptr(scratch, True), scratch.numel() * 4, 3, 1, D, H, W,
-                                                   16, 16, he, io, _stream()), 'lf_conv_bwd_weight_bf16_io')
-            else:
-                xf = round_bf16(x.float()) if ac else x
-                gf = round_bf16(gp.float()) if ac else gp
-                check(L.lf_conv_bwd_weight(_ptr(xf), _ptr(gf), _ptr(dst), _ptr(scratch, True), scratch.numel() * 4, 3, 1, D, H, W, 16, 16,
-                                           he, _stream()), 'lf_conv_bwd_weight')
+            if ac and wg.entry != _Wgrad.BF16:                    # small volumes: the fp32-MFMA kernel on the same bf16 values
+                x, gp = round_bf16(x.float()), round_bf16(gp.float())
+            wg(x, gp, dst)
         gh1 = empty_cl(shape1, dev)
         gh12 = empty_cl(shape1, dev)
         grh = empty_cl16(shape1, dev, T16)
@@ -823,7 +832,7 @@ class _GruFuse(torch.autograd.Function):
         gdone = [None, None]
         if side is not None:
             side.wait_stream(main)
-            for t in (gwb, scratch, zz) + tuple(b for bb in gbuf for b in bb):
+            for t in (gwb, wg.scratch, zz) + tuple(b for bb in gbuf for b in bb):
                 t.record_stream(side)
         steps, hs = ctx.steps, ctx.hs
         for i in range(V - 1, 0, -1):
@@ -916,11 +925,10 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
         hi = lo
     gwb = torch.zeros(len(chunks), 3, 2, 27, 16, 16, device=dev, dtype=torch.float32) if need_w else None
     acc = [empty_cl(shape1, dev) for _ in range(3)] if need_w else None
-    nbytes = L.lf_conv_bwd_weight_scratch_bytes(3, V, D, H, W, 16, 16)
-    scratch = torch.empty(nbytes // 4 + 1, device=dev, dtype=torch.float32) if need_w else None     # (one: the launches are in order)
+    wg = _Wgrad(3, V, D, H, W, 16, 16, dev, he, bf16=True) if need_w else None     # (one scratch: the launches are in order)
     if side is not None:
         side.wait_stream(main)                                    # (the allocations above)
-        for t in [gwb, zz, UP, RP, CA, RH, HS, HX, scratch] + acc:
+        for t in [gwb, zz, UP, RP, CA, RH, HS, HX, wg.scratch] + acc:
             t.record_stream(side)
 
     def weight_grads(ci, lo, hi):
@@ -929,9 +937,7 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
         j = slice(lo - 1, hi - 1)
         for k, (gp, xh) in enumerate(((UP, HX), (RP, HX), (CA, RH))):
             for q, x in enumerate((zz[lo:hi], xh[j])):
-                io = (1 if x.dtype == torch.bfloat16 else 0) | 2
-                check(L.lf_conv_bwd_weight_bf16_io(_ptr(x), _ptr(gp[j]), _ptr(gwb[ci, k, q]), _ptr(scratch, True), scratch.numel() * 4, 3, nv, D, H, W,
-                                                   16, 16, he, io, _stream()), 'lf_conv_bwd_weight_bf16_io')
+                wg(x, gp[j], gwb[ci, k, q])
             check(L.lf_sum_views_bf16(_ptr(gp[j]), _ptr(acc[k]), n, nv, int(ci > 0), _stream()), 'lf_sum_views_bf16')
 
     def on_side(fn, *a):
