@@ -28,7 +28,13 @@ extern "C" {
  * per CU of lf_conv3d_c16_ring_bf16, 2 (default) or 3.  key 6: samples per pass of the binned splat at most (0 = default: as many
  * as 512 MB of lists hold; tests use 1 or 2 to walk the multi-pass path at small sizes).  key 7: the fp32 Winograd 16-channel
  * kernels (lf_conv3d_c16_wino, _projfwd, _projbwd), 1 = the transforms next to the MFMAs as packed fp32 instructions (default),
- * 0 = the scalar form they replace (bit-identical results; profiles/wino_pack_ab.json).
+ * 0 = the scalar form they replace (bit-identical results; profiles/wino_pack_ab.json).  key 8: the same kernels
+ * (lf_conv3d_c16_wino, _projfwd), 1 = a call whose epilogue arguments match one of the render loop's three combinations (forward
+ * block: LeakyReLU | PixelNorm with bias and norm_out; data gradient with the previous layer's LeakyReLU' / PixelNorm'; plain data
+ * gradient; no amax_out) runs the kernel compiled for that combination, with the registers this frees spent on un-fenced address
+ * arithmetic and a resident bias (default), 0 = every call runs the generic kernel, 2 = the compiled forms without that spending
+ * (bit-identical results for every value; profiles/wino_forms_ab.json).  Calls that match no combination, and every call under
+ * key 7 = 0, run the generic kernel whatever the value.
  * Returns the previous value or LF_EINVAL. */
 int lf_set_tuning(int key, int value);
 

@@ -133,6 +133,69 @@ __device__ __forceinline__ void pk_fence(f32x4& a, f32x4& b) { asm("s_nop 1" : "
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+// The epilogue arithmetic of the fixed forms (WF_*, at conv3d_c16_wino_body), spelled out.  The generic kernels leave fp
+// contraction to the compiler, and which products it fuses into v_fma / v_pk_fma depends on the code around them: with the
+// runtime tests folded away the same source lines come out with OTHER fusions (sum of squares without fmas, every
+// `v - yp * dot` fused, ...) and the results differ in the last bit.  These functions pin, with contraction off, exactly the
+// roundings the generic kernels are compiled to; tests/test_wino_forms_gpu.py holds the two together bit for bit, so a
+// compiler that changes its mind about the generic kernels shows there.  To re-derive the pattern then: the device listing of
+// this file (command line in tools/wino_isa_count.py), kernel conv3d_c16_wino_kernel<true>, behind its last v_mfma: the block with
+// v_rsq_f32 is the forward epilogue (which product opens the v_fmac chain of the sum of squares, whether the Newton step is a
+// v_fmaak), the block with v_rcp_f32 the previous layer's backward (which of the four `v - yp * dot` are v_pk_fma and which a
+// v_mul + v_pk_add neg; whether 2 - pn * r is a v_sub); conv3d_c16_wino_projfwd_kernel<true> has the forward block once more.
+// quad_sum with its two instructions pinned: the compiler is free to split a step into v_mov_dpp + v_add with the operands the
+// other way round, which hands on the OTHER lane's NaN where both are NaNs (sign and payload; found by the NaN case of the
+// test).  (s_nop 4: the compiler cannot pad hazards inside asm; five wait states cover a DPP read behind a VALU write of the
+// register, 2, and behind a VALU write of EXEC, 5.)
+__device__ __forceinline__ float quad_sum_pinned(float v) {
+  float a, b;
+  asm("s_nop 4\n\tv_add_f32_dpp %0, %1, %1 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(a) : "v"(v));
+  asm("s_nop 4\n\tv_add_f32_dpp %0, %1, %1 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf bound_ctrl:1" : "=v"(b) : "v"(a));
+  return b;
+}
+//   forward block: u = fma(scale, o, b); LeakyReLU as max(u, u * slope); ss = fma(u3, u3, fma(u2, u2, fma(u0, u0, u1 * u1)));
+//                  tq = fma(quad_sum(ss), 1/16, eps); rinv = r * fma(r, (-0.5 tq) r, 1.5), r = v_rsq(tq)
+__device__ __forceinline__ void wino_epi_fwd_block(const f32x4 o, const f32x4 b, float scale, float slope, float eps,
+                                                   f32x4& v, float& rn) {
+#pragma clang fp contract(off)
+  f32x4 u;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float t = __builtin_fmaf(scale, o[e], b[e]);
+    u[e] = fmaxf(t, t * slope);
+  }
+  const float ss = __builtin_fmaf(u[3], u[3], __builtin_fmaf(u[2], u[2], __builtin_fmaf(u[0], u[0], u[1] * u[1])));
+  const float tq = __builtin_fmaf(quad_sum_pinned(ss), 1.f / 16.f, eps);
+  const float r = __builtin_amdgcn_rsqf(tq);
+  const float rinv = r * __builtin_fmaf(r, (-0.5f * tq) * r, 1.5f);
+  rn = tq * rinv;
+  v = u * rinv;
+}
+//   previous layer's PixelNorm' / LeakyReLU': plain products and sums for v = o * scale, the dot product and the Newton step
+//   of the reciprocal; `v - yp * dot` fused for channels 0, 1 of the quarter and not for 2, 3
+__device__ __forceinline__ f32x4 wino_epi_dgrad_prev(const f32x4 o, const f32x4 yp, float pn, float scale, float slope) {
+#pragma clang fp contract(off)
+  f32x4 v = o * scale;
+  const float dot = quad_sum_pinned(((v[0] * yp[0] + v[1] * yp[1]) + v[2] * yp[2]) + v[3] * yp[3]) * (1.f / 16.f);
+  const float r = __builtin_amdgcn_rcpf(pn);
+  const float rinv = r * (2.f - pn * r);
+  v[0] = __builtin_fmaf(-yp[0], dot, v[0]) * rinv;
+  v[1] = __builtin_fmaf(-yp[1], dot, v[1]) * rinv;
+  v[2] = (v[2] - yp[2] * dot) * rinv;
+  v[3] = (v[3] - yp[3] * dot) * rinv;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = yp[e] > 0.f ? v[e] : v[e] * slope;
+  return v;
+}
+//   plain data gradient: fma(scale, o, +0) -- the generic kernel's `o * scale + bias` with the zero it holds for a missing
+//   bias (a product of -0 comes out as +0)
+__device__ __forceinline__ f32x4 wino_epi_dgrad_plain(const f32x4 o, float scale) {
+  f32x4 v;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) v[e] = __builtin_fmaf(scale, o[e], 0.f);
+  return v;
+}
+
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // The MFMA phase of one 16-tile group in the packed form: rows b = 0..3 of the y input transform, their 16 MFMAs each
@@ -387,7 +450,23 @@ struct WinoProj {
 // conflict-free by ds_read_b128 with lane = q * 16 + v (the hardware's lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...)
 __device__ __forceinline__ int tr_swz(int v) { return (0x78 >> (2 * ((v >> 2) & 3))) & 3; }
 
-template <bool SPLIT, int FUSE = 0, bool PACK = false>
+// FORM: the per-tile path behind the MFMA phase (z output transform, epilogue, previous-layer backward, stores, next-halo
+// fetch / commit, projection) compiled for ONE combination of the epilogue arguments instead of generic over their runtime
+// values.  Generic, every launch carries the live ranges and the branches of every form (242 VGPRs, 527 VALU and 66
+// branches behind the last MFMA); a fixed form carries its own only (profiles/wino_forms_isa.txt).  The forms are the ones
+// the render loop launches; the host entry points pick one from their runtime arguments (wino_form_of) and send every other
+// combination to WF_GENERIC.  Everything but the epilogue arithmetic is the generic path's source with the arguments pinned;
+// the arithmetic is wino_epi_* above, the generic kernels' roundings spelled out: bit-identical.
+enum : int {
+  WF_GENERIC = 0,
+  WF_FWD_BLOCK = 1,     // flags = LReLU | PixelNorm, bias and norm_out present, no prev_y, no amax_out
+  WF_DGRAD_PREV = 2,    // flags = 0, no bias, prev_y and prev_norm present, prev_flags = LReLU | PixelNorm, no amax_out
+  WF_DGRAD_PLAIN = 3,   // flags = 0, no bias, no prev_y, no amax_out
+};
+// OPT (fixed forms only) = 1: the registers a fixed form frees are spent on dropping the two optimiser fences that exist only
+// because hoisting used to spill (hrel[] in fetch_half, the projection's lane index) and on keeping the bias quarter resident
+// across tiles; 0 = fences and per-tile bias read as in the generic kernel (lf_set_tuning(8, 2), for the A/B).
+template <bool SPLIT, int FUSE = 0, bool PACK = false, int FORM = WF_GENERIC, int OPT = 0>
 __device__ __forceinline__ void conv3d_c16_wino_body(
     const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ norm_out,
@@ -395,6 +474,21 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
     float he, unsigned flags, float slope, float eps,
     const float* __restrict__ prev_y, const float* __restrict__ prev_norm, unsigned prev_flags,
     const float* __restrict__ amax_in, float* __restrict__ amax_out, const WinoProj pj = WinoProj()) {
+  static_assert(FORM == WF_GENERIC || (!SPLIT && FUSE != 2 && PACK), "fixed forms: the packed all-fp32 kernels only");
+  static_assert(OPT == 0 || OPT == 1, "");
+  static_assert(FORM != WF_GENERIC || OPT == 0, "the generic kernel stays as it is");
+  // a fixed form pins the arguments it is defined by: every test on them below folds at compile time
+  constexpr bool HAS_BIAS = FORM == WF_FWD_BLOCK;              // (fixed forms; the generic form tests the pointer)
+  if constexpr (FORM == WF_FWD_BLOCK) {
+    flags = LF_EPI_LRELU | LF_EPI_PIXELNORM;
+    prev_y = nullptr; prev_norm = nullptr; prev_flags = 0u; amax_out = nullptr;
+  } else if constexpr (FORM == WF_DGRAD_PREV) {
+    flags = 0u; prev_flags = LF_EPI_LRELU | LF_EPI_PIXELNORM;
+    bias = nullptr; norm_out = nullptr; amax_out = nullptr;
+  } else if constexpr (FORM == WF_DGRAD_PLAIN) {
+    flags = 0u; prev_flags = 0u;
+    bias = nullptr; norm_out = nullptr; prev_y = nullptr; prev_norm = nullptr; amax_out = nullptr;
+  }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const buf = smem;                              // halo
   unsigned char* const px = smem + BUFw;                        // partial exchange
@@ -507,8 +601,10 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
   u32x4 hlo[NITw], hhi[NITw];
   auto fetch_half = [&](u32x4 (&dst)[NITw], __amdgpu_buffer_rsrc_t rs, int base, unsigned sel) {
     // (opaque to the optimiser, or base + hrel[] of every branch is hoisted out of the tile loop into registers)
+    if constexpr (!(OPT & 1)) {
 #pragma unroll
-    for (int i = 0; i < NITw; ++i) asm volatile("" : "+v"(hrel[i]));
+      for (int i = 0; i < NITw; ++i) asm volatile("" : "+v"(hrel[i]));
+    }
     if (sel == 0) {                                             // wave-uniform: interior tile, one VALU add per piece
 #pragma unroll
       for (int it = 0; it < NITw; ++it) dst[it] = __builtin_amdgcn_raw_buffer_load_b128(rs, base + hrel[it], 0, 0);
@@ -674,6 +770,8 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
         if (it < 2 || fa < 3 || lane < 16) *(u32x4*)(buf + pl * (HYw * HXw * 64) + it * 4096 + sbase) = tmp[it];
     }
   };
+  f32x4 bv_res = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if constexpr (HAS_BIAS && (OPT & 1)) bv_res = *(const f32x4*)(bias + eq * 4);
   // FUSE = 1: per-wave projection accumulators (2 output rows x 16 x x 16 cout) and the A operands of the tile's two planes
   f32x4 pacc[2] = {(f32x4){0.f, 0.f, 0.f, 0.f}, (f32x4){0.f, 0.f, 0.f, 0.f}};
 
@@ -749,19 +847,26 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
     float pnv[4];
     if (prev_y != nullptr) {
       const float* pybase = prev_y + (long)tt * nvox * 16;
-      const float* pnbase = prev_norm ? prev_norm + (long)tt * nvox : nullptr;
+      const float* pnbase = (FORM == WF_DGRAD_PREV || prev_norm) ? prev_norm + (long)tt * nvox : nullptr;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         pyv[k] = okv[k] ? *(const f32x4*)(pybase + voxi[k] * 16 + eq * 4) : (f32x4){0.f, 0.f, 0.f, 0.f};
-        pnv[k] = (okv[k] && pnbase) ? pnbase[voxi[k]] : 1.f;
+        pnv[k] = (okv[k] && (FORM == WF_DGRAD_PREV || pnbase)) ? pnbase[voxi[k]] : 1.f;
       }
     }
     // (bias is re-read per tile -- an L1 hit queued ahead of the halo -- rather than held in four registers)
+    // (a fixed form with OPT bit 0 has the registers: bv_res, loaded once)
     f32x4 bv4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    {
+    if constexpr (FORM == WF_GENERIC) {
       const float* bp = bias;
       asm volatile("" : "+s"(bp));
       if (bp != nullptr) bv4 = *(const f32x4*)(bp + eq * 4);
+    } else if constexpr (HAS_BIAS && (OPT & 1)) {
+      bv4 = bv_res;
+    } else if constexpr (HAS_BIAS) {
+      const float* bp = bias;
+      asm volatile("" : "+s"(bp));
+      bv4 = *(const f32x4*)(bp + eq * 4);
     }
     TS(4);
     if constexpr (FUSE == 2) {
@@ -788,14 +893,18 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
     }
 
     unsigned char* ybase = (unsigned char*)(y + (long)tt * nvox * 16) + eq * 16;
-    float* nbase = norm_out ? norm_out + (long)tt * nvox : nullptr;
+    float* nbase = (FORM == WF_FWD_BLOCK || norm_out) ? norm_out + (long)tt * nvox : nullptr;
     f32x4 v[4];
     float rn[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       rn[k] = 1.f;
       if constexpr ((WINO_ABL & 1) != 0) { v[k] = o[k]; continue; }
-      if (prev_y == nullptr || addmode) {
+      if constexpr (FORM == WF_FWD_BLOCK) {
+        wino_epi_fwd_block(o[k], bv4, out_scale, slope, eps, v[k], rn[k]);
+      } else if constexpr (FORM == WF_DGRAD_PLAIN) {
+        v[k] = wino_epi_dgrad_plain(o[k], out_scale);
+      } else if (prev_y == nullptr || addmode) {
         float ss = 0.f;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -821,7 +930,9 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
     TS(7);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      if (!(WINO_ABL & 1) && prev_y != nullptr && !addmode) {
+      if constexpr (FORM == WF_DGRAD_PREV) {
+        if (!(WINO_ABL & 1)) v[k] = wino_epi_dgrad_prev(o[k], pyv[k], pnv[k], out_scale, slope);
+      } else if (!(WINO_ABL & 1) && prev_y != nullptr && !addmode) {
         const f32x4 yp = pyv[k];
         v[k] = o[k] * out_scale;
         if (prev_flags & LF_EPI_PIXELNORM) {
@@ -837,7 +948,7 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
       }
       if (okv[k]) {
         __builtin_nontemporal_store(v[k], (f32x4*)(ybase + (unsigned)(voxi[k] * 64)));   // streamed: L2 is for halos
-        if (!(WINO_ABL & 16) && (prev_y == nullptr || addmode) && (flags & LF_EPI_PIXELNORM) && nbase != nullptr && eq == 0) nbase[voxi[k]] = rn[k];
+        if (!(WINO_ABL & 16) && (prev_y == nullptr || addmode) && (flags & LF_EPI_PIXELNORM) && (FORM == WF_FWD_BLOCK || nbase != nullptr) && eq == 0) nbase[voxi[k]] = rn[k];
         if (amax_out != nullptr)
           wave_amax = fmaxf(wave_amax, fmaxf(fmaxf(fabsf(v[k][0]), fabsf(v[k][1])), fmaxf(fabsf(v[k][2]), fabsf(v[k][3]))));
       }
@@ -862,7 +973,7 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
       // finished records -> B-operand order through this wave's own (consumed) slices of the exchange region
       __builtin_amdgcn_sched_barrier(0);
       int lop = lane;
-      asm volatile("" : "+v"(lop));                               // (opaque: or per-lane 64-bit addresses are hoisted out of the loop and spilled)
+      if constexpr (!(OPT & 1)) asm volatile("" : "+v"(lop));     // (opaque: or per-lane 64-bit addresses are hoisted out of the loop and spilled)
       const int trn = lop & 15, trk = lop >> 4;
       f32x4 pw_a[2];                                             // L2-resident weight slices of the tile's two planes
 #pragma unroll
@@ -981,8 +1092,44 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_wino_projbwd_kernel(
                                  eps, prev_y, prev_norm, prev_flags, nullptr, nullptr, pj);
 }
 
+// The fixed forms (packed transforms only: under lf_set_tuning key 7 = 0 every call runs the generic scalar kernel).
+template <int FORM, int OPT>
+__global__ void __launch_bounds__(256, 2) conv3d_c16_wino_form_kernel(
+    const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
+    float* __restrict__ y, float* __restrict__ norm_out, int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z,
+    int ntiles, float he, unsigned flags, float slope, float eps, const float* __restrict__ prev_y,
+    const float* __restrict__ prev_norm, unsigned prev_flags, float* __restrict__ amax_out) {
+  conv3d_c16_wino_body<false, 0, true, FORM, OPT>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags,
+                                                 slope, eps, prev_y, prev_norm, prev_flags, nullptr, amax_out);
+}
+
+template <int FORM, int OPT>
+__global__ void __launch_bounds__(256, 2) conv3d_c16_wino_projfwd_form_kernel(
+    const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
+    float* __restrict__ y, float* __restrict__ norm_out, int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z,
+    int ntiles, float he, unsigned flags, float slope, float eps, const float* __restrict__ prev_y,
+    const float* __restrict__ prev_norm, unsigned prev_flags, WinoProj pj) {
+  conv3d_c16_wino_body<false, 1, true, FORM, OPT>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags,
+                                                 slope, eps, prev_y, prev_norm, prev_flags, nullptr, nullptr, pj);
+}
+
 // lf_set_tuning key 7: 1 = packed transforms next to the MFMAs (wino_rows_packed; default), 0 = the scalar form.  Bit-identical.
 int g_wino_pack = 1;
+// lf_set_tuning key 8: 1 = calls that match a fixed form run it, OPT = 1 (default), 0 = every call runs the generic kernel,
+// 2 = the fixed forms with OPT = 0.  Bit-identical.
+int g_wino_forms = 1;
+
+// The fixed form a call may run, from ALL the arguments a form pins: a call that differs in any of them (add mode, amax_out,
+// LeakyReLU alone, flags without a bias, ...) is WF_GENERIC.
+int wino_form_of(const float* bias, const float* norm_out, unsigned flags, const float* prev_y, const float* prev_norm,
+                 unsigned prev_flags, const float* amax_out) {
+  const unsigned full = LF_EPI_LRELU | LF_EPI_PIXELNORM;
+  if (!g_wino_pack || !g_wino_forms || amax_out != nullptr) return WF_GENERIC;
+  if (flags == full && bias != nullptr && norm_out != nullptr && prev_y == nullptr) return WF_FWD_BLOCK;
+  if (flags == 0u && bias == nullptr && prev_y != nullptr && prev_norm != nullptr && prev_flags == full) return WF_DGRAD_PREV;
+  if (flags == 0u && bias == nullptr && prev_y == nullptr) return WF_DGRAD_PLAIN;
+  return WF_GENERIC;
+}
 
 template <auto kernel, bool COLUMNS = false, typename... Extra>
 int launch_wino(const float* x, const void* upack, const float* bias, float* y, float* norm_out, int N, int D,
@@ -1015,10 +1162,15 @@ int launch_wino(const float* x, const void* upack, const float* bias, float* y, 
 
 }  // namespace
 
-// tuning hook for lf_set_tuning (key 7, resample.hip)
+// tuning hooks for lf_set_tuning (keys 7 and 8, resample.hip)
 int lf_internal_wino_set_pack(int v) {
   const int prev = g_wino_pack;
   if (v == 0 || v == 1) g_wino_pack = v;
+  return prev;
+}
+int lf_internal_wino_set_forms(int v) {
+  const int prev = g_wino_forms;
+  if (v >= 0 && v <= 2) g_wino_forms = v;
   return prev;
 }
 
@@ -1030,6 +1182,18 @@ extern "C" int lf_conv3d_c16_wino(const float* x, const float* upack, const floa
                                   const float* prev_y, const float* prev_norm, unsigned prev_flags,
                                   float* amax_out, void* stream) {
   lf_clear_error();
+#define LF_WINO_FORM(F, O) \
+  launch_wino<conv3d_c16_wino_form_kernel<F, O>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y, prev_norm, \
+                                                 prev_flags, stream, amax_out)
+#define LF_WINO_OPTS(F) (g_wino_forms == 2 ? LF_WINO_FORM(F, 0) : LF_WINO_FORM(F, 1))
+  switch (wino_form_of(bias, norm_out, flags, prev_y, prev_norm, prev_flags, amax_out)) {
+    case WF_FWD_BLOCK: return LF_WINO_OPTS(WF_FWD_BLOCK);
+    case WF_DGRAD_PREV: return LF_WINO_OPTS(WF_DGRAD_PREV);
+    case WF_DGRAD_PLAIN: return LF_WINO_OPTS(WF_DGRAD_PLAIN);
+    default: break;
+  }
+#undef LF_WINO_OPTS
+#undef LF_WINO_FORM
   return g_wino_pack ? launch_wino<conv3d_c16_wino_kernel<true>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y,
                                                                   prev_norm, prev_flags, stream, amax_out)
                      : launch_wino<conv3d_c16_wino_kernel<false>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y,
@@ -1060,6 +1224,13 @@ extern "C" int lf_conv3d_c16_wino_projfwd(const float* x, const float* upack, co
   if (!lf_aligned16(proj_wA) || !lf_aligned16(zp) || (proj_bias && !lf_aligned16(proj_bias))) return LF_EALIGN;
   if ((proj_flags & ~(LF_EPI_LRELU | LF_EPI_PIXELNORM)) != 0) return LF_EINVAL;
   WinoProj pj = {proj_wA, proj_bias, zp, pnorm, nullptr, nullptr, proj_he, proj_flags};
+  if (wino_form_of(bias, norm_out, flags, nullptr, nullptr, 0u, nullptr) == WF_FWD_BLOCK) {
+#define LF_WINO_FORM(O) \
+  launch_wino<conv3d_c16_wino_projfwd_form_kernel<WF_FWD_BLOCK, O>, true>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, \
+                                                                          nullptr, nullptr, 0u, stream, pj)
+    return g_wino_forms == 2 ? LF_WINO_FORM(0) : LF_WINO_FORM(1);
+#undef LF_WINO_FORM
+  }
   return g_wino_pack ? launch_wino<conv3d_c16_wino_projfwd_kernel<true>, true>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope,
                                                                                 eps, nullptr, nullptr, 0u, stream, pj)
                      : launch_wino<conv3d_c16_wino_projfwd_kernel<false>, true>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope,

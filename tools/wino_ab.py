@@ -10,7 +10,8 @@ Each variant is checked against the first one (max |diff| of forward and fused-b
 round-robin: forward (bias + LeakyReLU + PixelNorm), data-gradient fused with the previous layer's backward and the
 forward with the factor projection riding on it (lf_conv3d_c16_wino_projfwd).  A whole liblf_hip.so works as a variant
 too (the parent commit's against this one's), and `path@0` / `path@1` selects the scalar / packed transforms of that
-library through lf_set_tuning(7, .) before each of its calls."""
+library through lf_set_tuning(7, .) before each of its calls; `path@8=0` / `path@8=1` (any `key=value`, comma-separated) the
+generic kernels / the compile-time epilogue forms.  The plain data gradient (no previous layer) is timed as well."""
 import ctypes
 import os
 import sys
@@ -51,7 +52,9 @@ def bind(spec):
 
     def select():
         if pack:
-            L.lf_set_tuning(7, int(pack))
+            for kv in pack.split(','):
+                k, _, v = kv.rpartition('=')
+                L.lf_set_tuning(int(k or 7), int(v))
 
     def f(*a):
         select()
@@ -68,8 +71,8 @@ def bind(spec):
 def run(f, y, nrm, gout):
     assert f(x.data_ptr(), up.data_ptr(), b.data_ptr(), y.data_ptr(), nrm.data_ptr(), N, S, S, S, he, flags, 0.2, 1e-8,
              None, None, 0, None, st) == 0
-    return lambda: f(x.data_ptr(), upt.data_ptr(), None, gout.data_ptr(), None, N, S, S, S, he, 0, 0.2, 1e-8,
-                     y.data_ptr(), nrm.data_ptr(), flags, None, st)
+    return lambda plain=False: f(x.data_ptr(), upt.data_ptr(), None, gout.data_ptr(), None, N, S, S, S, he, 0, 0.2, 1e-8,
+                                 None if plain else y.data_ptr(), None if plain else nrm.data_ptr(), 0 if plain else flags, None, st)
 
 
 # `path:fwd` / `path:bwd` restricts a variant to one of the two calls (builds with a hard-wired epilogue)
@@ -98,11 +101,12 @@ for i, p in enumerate(sys.argv[1:]):
 tf = [[] for _ in fs]
 tb = [[] for _ in fs]
 tp = [[] for _ in fs]
+tg = [[] for _ in fs]
 for r in range(ROUNDS):
     for i, f in enumerate(fs):
         y, nrm, go, bw = outs[i]
-        for which, acc in ((0, tf), (1, tb)):
-            if only[i] == ('bwd', 'fwd')[which]:
+        for which, acc in ((0, tf), (1, tb), (2, tg)):
+            if only[i] == ('bwd', 'fwd', 'fwd')[which]:
                 acc[i].append(float('nan'))
                 continue
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -111,7 +115,7 @@ for r in range(ROUNDS):
                 if which == 0:
                     f(x.data_ptr(), up.data_ptr(), b.data_ptr(), y.data_ptr(), nrm.data_ptr(), N, S, S, S, he, flags, 0.2, 1e-8, None, None, 0, None, st)
                 else:
-                    bw()
+                    bw(which == 2)
             e1.record()
             torch.cuda.synchronize()
             acc[i].append(e0.elapsed_time(e1) / 5)
@@ -123,6 +127,6 @@ for r in range(ROUNDS):
         torch.cuda.synchronize()
         tp[i].append(e0.elapsed_time(e1) / 5)
 for i, p in enumerate(sys.argv[1:]):
-    a, c, d = sorted(tf[i]), sorted(tb[i]), sorted(tp[i])
+    a, c, d, e = sorted(tf[i]), sorted(tb[i]), sorted(tp[i]), sorted(tg[i])
     print(f'{p}: fwd median {a[len(a) // 2]:.4f} ms (min {a[0]:.4f}), bwd+prev median {c[len(c) // 2]:.4f} ms (min {c[0]:.4f}), '
-          f'projfwd median {d[len(d) // 2]:.4f} ms (min {d[0]:.4f})')
+          f'bwd plain median {e[len(e) // 2]:.4f} ms (min {e[0]:.4f}), projfwd median {d[len(d) // 2]:.4f} ms (min {d[0]:.4f})')

@@ -4,6 +4,7 @@
     hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -fno-gpu-rdc -Ilatentfusion_amd/csrc --cuda-device-only -S \
           latentfusion_amd/csrc/conv_wino.hip -o wino.s
     python tools/wino_isa_count.py wino.s [more.s ...]
+    python tools/wino_isa_count.py --same-as parent.s wino.s     (also: which kernels of parent.s have the same listing in wino.s)
 
 Per kernel: VALU and MFMA instructions, packed / scalar fp32 adds and subtractions, s_nop, VGPRs, spills, scratch.  The
 four z-frequency instantiations of wino_compute each run on one wave, so a count / 4 is per wave and tile (plus the
@@ -58,14 +59,47 @@ def kernels(path):
     return rows
 
 
+FORMS = {'1': 'fwd block', '2': 'dgrad+prev', '3': 'dgrad plain'}
+
+
 def short(name):
+    m = re.search(r'(conv3d_c16_wino\w*?_form_kernel)ILi(\d)ELi(\d)E', name)
+    if m:                                                       # the fixed epilogue forms: <form, OPT>
+        return f'{m.group(1)}<{FORMS[m.group(2)]}, {m.group(3)}>'
     m = re.search(r'(conv3d_c16_wino\w*?_kernel)(ILb([01])E)?', name)
     return m.group(1) + ({'1': '<packed>', '0': '<scalar>', None: ''}[m.group(3)])
 
 
-for path in sys.argv[1:]:
+def listings(path):
+    """Per kernel: its instructions and labels, comments dropped, the function's index taken out of the block labels."""
+    name, out = None, {}
+    for line in open(path):
+        t = line.strip()
+        m = re.match(r'^(_ZN\S*conv3d_c16_wino\S*):', t)
+        if m:
+            name = m.group(1)
+            out[name] = []
+        elif name is not None and t.startswith('.Lfunc_end'):
+            name = None
+        elif name is not None:
+            t = re.sub(r'\.LBB\d+_', '.LBB_', re.sub(r';.*', '', t)).strip()
+            if t:
+                out[name].append(t)
+    return out
+
+
+args = sys.argv[1:]
+base = None
+if args[:1] == ['--same-as']:
+    base, args = args[1], args[2:]
+for path in args:
     print(f'# {path}')
     print('| kernel | ' + ' | '.join(COLS) + ' |')
     print('|---|' + '---|' * len(COLS))
     for name, r in kernels(path).items():
         print(f'| `{short(name)}` | ' + ' | '.join(str(r[c]) for c in COLS) + ' |')
+    if base is not None:
+        old, new = listings(base), listings(path)
+        print(f'\n# listings of {base} against {path} (comments dropped, block labels renumbered):')
+        for name, body in old.items():
+            print(f'#   `{short(name)}`: {len(body)} lines, ' + ('IDENTICAL' if new.get(name) == body else 'DIFFERENT' if name in new else 'absent'))
