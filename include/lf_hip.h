@@ -584,6 +584,51 @@ int lf_grid_sample2d_fwd(const float* img, const float* grid, float* out, int N,
 int lf_grid_sample2d_bwd(const float* img, const float* grid, const float* gout, float* gimg, float* ggrid,
                          int N, int C, int H, int W, int Ho, int Wo, int bilinear, int border, void* stream);
 
+/* Fused depth-based reprojection of image-based rendering (ibr.py:11-93: depth_to_warp_field + reproject_views) for B
+ * objects, Vo output and Vi input views, all planar fp32:
+ *   image_in [B][Vi][C][H][W], depth_in [B][Vi][H][W] (metric z, used as it stands), depth_out [B][Vo][H][W] (normalised,
+ *   denormalised with the output camera's znear - 0.01 / zfar + 0.01), mask_out [B][Vo][H][W] or NULL;
+ *   image_re[b][o][i][c] at image_re + ((b*Vo + o)*Vi + i) * image_row_stride + c*H*W, depth_re[b][o][i] at depth_re + (same
+ *   row) * depth_row_stride: C*H*W and H*W for packed outputs, (C+2)*H*W each with depth_re = image_re + C*H*W to land in the
+ *   (B*Vo, Vi, C+2, H, W) input of the IBR generator (the plane after the depth is not touched).
+ * Per (b, o, i, pixel): the output pixel of the linspace(0,1) viewport lattice is unprojected with its depth, carried to
+ * object space and projected into input view i; image_in[b][i] is sampled there (bilinear, align_corners=False, zeros padding,
+ * the taps of lf_grid_sample2d_fwd, also for a non-finite coordinate), and so is the transformed input depth, whose value at
+ * each tap is formed from depth_in at that tap: unprojected, carried into output camera o, its z normalised with the OUTPUT
+ * camera's bounds, clamped to [0,1] (NaN kept), *2-1.  With mask_out the stores are image_re * m and (depth_re + 1) * m - 1,
+ * every operation rounded on its own.  No grid, point set or expanded image is materialised.  The coordinate chain runs in
+ * fp64 on the fp32 records and is split into floor + offset before the fp32 sampling (at the zero-padded frame edge the value
+ * changes by |image| per pixel; an fp32 chain would move that edge by several 1e-6 pixels at W = 32 already).
+ * Records (floats, formed in fp64 on the host; ops.pack_ibr_cameras), vp = viewport (x0, y0, x1, y1).  The entries of the
+ * coordinate chain are kept as TWO floats, v ~ rec[k] + rec[k + LF_IBR_*_SPLIT] (the fp32 rounding of v and the fp32 rounding of
+ * the remainder), because a relative error e of that chain moves the sample by e*W pixels; the others are rounded once.
+ *   pair_rec [B][Vo][Vi][LF_IBR_PAIR_FLOATS]: [0,12) rows N0, N1, N2 (4 floats each) of the 3x4 map  K_i E_i E_o^-1  (output
+ *     camera -> object -> input image) with N0 := (N0 - vp_i.x0 N2) / (vp_i.x1 - vp_i.x0), N1 likewise in y, so that for the
+ *     camera point P = (x, y, z, 1):  sample x = W * (N0.P)/(N2.P) - 0.5,  y = H * (N1.P)/(N2.P) - 0.5;  [16,28) their second
+ *     floats;  [12,16) the z row of E_o E_i^-1 (input camera -> object -> output camera) as D = (row - (0,0,0,zn_o)) /
+ *     (zf_o - zn_o): normalised depth before the clamp = D.P for the input-camera point P.  zn = znear - 0.01, zf = zfar + 0.01.
+ *   in_rec [B][Vi][LF_IBR_VIEW_FLOATS], out_rec [B][Vo][LF_IBR_VIEW_FLOATS]: [0] ax = (vp.x1 - vp.x0)/fu, [1] bx = (vp.x0 - u0)/fu,
+ *     [2] ay, [3] by likewise (camera x / z = ax * lattice + bx); out_rec also [4] = (zf - zn)/2, [5] = (zf + zn)/2
+ *     (z = d*[4] + [5]) and at [8,14) the second floats of [0,6).  The rest is padding.
+ * bwd: g_image_re [B][Vo][Vi][C][H][W] and g_depth_re [B][Vo][Vi][H][W], packed, either may be NULL (not both); with mask_out
+ * they are the gradients of the masked outputs.  g_image_in and g_depth_in are accumulated with float atomics into buffers the
+ * caller zeroed -- NOT run-to-run identical in the last bits; g_depth_out (through the sampling coordinate of both samples) is
+ * summed over i and c in a fixed order inside one thread, without atomics -- run-to-run identical.  Any of the three may be
+ * NULL.  Cameras are constants (no gradient); a tap whose normalised depth is outside [0,1] passes no gradient to depth_in.
+ * LF_EINVAL and nothing launched: a NULL required pointer, a size below 1, a row stride below the packed row, H*W or the
+ * number of 256-pixel blocks >= 2^31 - 1.  One 4-byte store per lane and plane: no alignment demands. */
+#define LF_IBR_PAIR_FLOATS 32
+#define LF_IBR_PAIR_SPLIT 16
+#define LF_IBR_VIEW_FLOATS 16
+#define LF_IBR_VIEW_SPLIT 8
+int lf_ibr_reproject_fwd(const float* image_in, const float* depth_in, const float* depth_out, const float* mask_out,
+                         const float* pair_rec, const float* in_rec, const float* out_rec, float* image_re, float* depth_re,
+                         int B, int Vo, int Vi, int C, int H, int W, long image_row_stride, long depth_row_stride, void* stream);
+int lf_ibr_reproject_bwd(const float* image_in, const float* depth_in, const float* depth_out, const float* mask_out,
+                         const float* pair_rec, const float* in_rec, const float* out_rec, const float* g_image_re,
+                         const float* g_depth_re, float* g_image_in, float* g_depth_in, float* g_depth_out,
+                         int B, int Vo, int Vi, int C, int H, int W, void* stream);
+
 /* Weight gradient of the He-equalised conv (training step; autograd of equalized.py:57-64):
  *   gw[tap][co][ci] = scale * sum_v gpre[v][co] * x[v + tap][ci],   tap = (kz*3 + ky)*3 + kx, zero padding,
  * dims = 3 (27 taps), 2 (9 taps, D = 1) or 0 (pointwise: one tap, rows = N*D*H*W).  x, gpre channels-last

@@ -22,6 +22,7 @@ LF_MAP_O2C = 0
 LF_MAP_C2O = 1
 LF_MAP_COEFS = 20
 LF_FUSE_MEAN, LF_FUSE_MAX, LF_FUSE_ABSMAX, LF_FUSE_MEDIAN = 0, 1, 2, 3
+LF_IBR_PAIR_FLOATS, LF_IBR_PAIR_SPLIT, LF_IBR_VIEW_FLOATS, LF_IBR_VIEW_SPLIT = 32, 16, 16, 8   # camera records of lf_ibr_reproject_*
 LF_AMAX_FLOATS = 2048          # floats of a max-abs side-channel buffer (include/lf_hip.h)
 
 P = c_void_p
@@ -128,6 +129,8 @@ SIGNATURES = {
     'lf_fuse_blend_bwd': (c_int, [P, P, P, P, P, c_int, c_long, c_int, c_long, c_long, P]),
     'lf_grid_sample2d_fwd': (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_grid_sample2d_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_ibr_reproject_fwd': (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_long, c_long, P]),
+    'lf_ibr_reproject_bwd': (c_int, [P, P, P, P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_conv_bwd_weight_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     'lf_conv_bwd_weight': (c_int, [P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     'lf_conv_bwd_weight_bf16_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

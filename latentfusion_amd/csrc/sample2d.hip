@@ -5,11 +5,10 @@
 // grid: [N][Ho][Wo][2] = (x, y) in [-1, 1]; modes bilinear / nearest (round-half-even like ATen).
 // One thread per output pixel, looping over the (few) channels; backward w.r.t. the grid is a plain
 // per-pixel sum, backward w.r.t. the image scatters with float atomics (not used on any ranking path).
-#include "lf_common.h"
+// The tap / validity logic lives in sample2d_taps.h, shared with the fused IBR reprojection (ibr.hip).
+#include "sample2d_taps.h"
 
 namespace {
-
-__device__ __forceinline__ float unnorm(float g, int size) { return ((g + 1.f) * (float)size - 1.f) * 0.5f; }
 
 // border padding: clip to [0, size-1]; returns d(clipped)/d(p)
 __device__ __forceinline__ float clip_border(float& p, int size) {
@@ -26,26 +25,14 @@ __global__ void __launch_bounds__(256) sample2d_fwd_kernel(const float* __restri
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= N * Ho * Wo) return;
   const int n = idx / (Ho * Wo), pix = idx - n * Ho * Wo;
-  float px = unnorm(grid[(long)idx * 2 + 0], W), py = unnorm(grid[(long)idx * 2 + 1], H);
+  float px = lf_unnorm2d(grid[(long)idx * 2 + 0], W), py = lf_unnorm2d(grid[(long)idx * 2 + 1], H);
   if (BORDER) { clip_border(px, W); clip_border(py, H); }
   const float* src = img + (long)n * C * H * W;
   float* dst = out + (long)n * C * Ho * Wo + pix;
   if (BILINEAR) {
-    const float fx = floorf(px), fy = floorf(py);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const float tx = px - fx, ty = py - fy;
-    const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)x1 < (unsigned)W;
-    const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)y1 < (unsigned)H;
-    const float w00 = (1.f - tx) * (1.f - ty), w01 = tx * (1.f - ty), w10 = (1.f - tx) * ty, w11 = tx * ty;
-    for (int c = 0; c < C; ++c) {
-      const float* s = src + (long)c * H * W;
-      float v = 0.f;
-      if (vy0 && vx0) v += s[y0 * W + x0] * w00;
-      if (vy0 && vx1) v += s[y0 * W + x1] * w01;
-      if (vy1 && vx0) v += s[y1 * W + x0] * w10;
-      if (vy1 && vx1) v += s[y1 * W + x1] * w11;
-      dst[(long)c * Ho * Wo] = v;
-    }
+    const lf_taps2d t = lf_bilinear_taps(px, py, H, W);
+    const lf_weights2d w = lf_bilinear_weights(t);
+    for (int c = 0; c < C; ++c) dst[(long)c * Ho * Wo] = lf_bilinear_gather(src + (long)c * H * W, W, t, w);
   } else {
     const int xn = (int)nearbyintf(px), yn = (int)nearbyintf(py);
     const bool ok = (unsigned)xn < (unsigned)W && (unsigned)yn < (unsigned)H;
@@ -61,7 +48,7 @@ __global__ void __launch_bounds__(256) sample2d_bwd_kernel(const float* __restri
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= N * Ho * Wo) return;
   const int n = idx / (Ho * Wo), pix = idx - n * Ho * Wo;
-  float px = unnorm(grid[(long)idx * 2 + 0], W), py = unnorm(grid[(long)idx * 2 + 1], H);
+  float px = lf_unnorm2d(grid[(long)idx * 2 + 0], W), py = lf_unnorm2d(grid[(long)idx * 2 + 1], H);
   float mx = 0.5f * (float)W, my = 0.5f * (float)H;            // d(p)/d(grid)
   if (BORDER) { mx *= clip_border(px, W); my *= clip_border(py, H); }
   const float* src = img + (long)n * C * H * W;
@@ -69,16 +56,14 @@ __global__ void __launch_bounds__(256) sample2d_bwd_kernel(const float* __restri
   const float* go = gout + (long)n * C * Ho * Wo + pix;
   float gx = 0.f, gy = 0.f;
   if (BILINEAR) {
-    const float fx = floorf(px), fy = floorf(py);
-    const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-    const float tx = px - fx, ty = py - fy;
-    const bool vx0 = (unsigned)x0 < (unsigned)W, vx1 = (unsigned)x1 < (unsigned)W;
-    const bool vy0 = (unsigned)y0 < (unsigned)H, vy1 = (unsigned)y1 < (unsigned)H;
+    const lf_taps2d t = lf_bilinear_taps(px, py, H, W);
+    const int x0 = t.x0, y0 = t.y0, x1 = t.x1, y1 = t.y1;
+    const float tx = t.tx, ty = t.ty;
+    const bool vx0 = t.vx0, vx1 = t.vx1, vy0 = t.vy0, vy1 = t.vy1;
     for (int c = 0; c < C; ++c) {
       const float g = go[(long)c * Ho * Wo];
-      const float* s = src + (long)c * H * W;
-      const float v00 = (vy0 && vx0) ? s[y0 * W + x0] : 0.f, v01 = (vy0 && vx1) ? s[y0 * W + x1] : 0.f;
-      const float v10 = (vy1 && vx0) ? s[y1 * W + x0] : 0.f, v11 = (vy1 && vx1) ? s[y1 * W + x1] : 0.f;
+      float v00, v01, v10, v11;
+      lf_tap_values(src + (long)c * H * W, W, t, v00, v01, v10, v11);
       gx += g * ((v01 - v00) * (1.f - ty) + (v11 - v10) * ty);
       gy += g * ((v10 - v00) * (1.f - tx) + (v11 - v01) * tx);
       if (gsrc) {

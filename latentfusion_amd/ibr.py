@@ -10,6 +10,32 @@ import torch
 from . import image_ops, three
 from .three.batchview import b2bv, bv2b
 
+# How reproject_views(_batch) computes when its `kernel` argument is None: 'composed' (tensor ops around two
+# lf_grid_sample2d_fwd calls, one object at a time) or 'fused' (ops.ibr_reproject: one lf_ibr_reproject_fwd launch for all
+# objects, views and pixels; device tensors only, cameras are constants).
+KERNEL = 'composed'
+KERNELS = ('composed', 'fused')
+
+
+def _resolve_kernel(kernel):
+    kernel = KERNEL if kernel is None else kernel
+    if kernel not in KERNELS:
+        raise ValueError(f'Unknown IBR kernel {kernel!r} (one of {KERNELS})')
+    return kernel
+
+
+def _fused_reproject(image_in, depth_in, depth_out, camera_in, camera_out, mask_out=None, out=None):
+    """The 'fused' path for (B,V,.,H,W) tensors and flat object-major cameras."""
+    from . import ops
+    if torch.is_grad_enabled() and any(t.requires_grad for cam in (camera_in, camera_out) for t in
+                                       (cam.intrinsic, cam.viewport, cam.log_quaternion, cam.translation)):
+        raise NotImplementedError("kernel='fused' treats the cameras as constants; use kernel='composed' for camera gradients")
+    for t in (image_in, depth_in, depth_out):
+        if not t.is_cuda:
+            raise ValueError("kernel='fused' needs device tensors (the composed path serves host tensors)")
+    records = ops.pack_ibr_cameras(camera_in.to(image_in.device), camera_out.to(image_in.device), batch_size=image_in.shape[0])
+    return ops.ibr_reproject(image_in.float(), depth_in.float(), depth_out.float(), records, mask_out=mask_out, out=out)
+
 
 def outer_distance(x1, x2, metric='cosine', eps=1e-8):
     """Pairwise distance matrix (reference distances.py:27-42; cosine only is used here)."""
@@ -60,8 +86,13 @@ def depth_to_warp_field(source_cam, target_cam, target_depth):
     return torch.stack((gx, gy), dim=-1).view(len(target_cam), len(source_cam), h, w, 2)
 
 
-def reproject_views(image_in, depth_in, depth_out, camera_in, camera_out):
-    """(V_i,C,H,W) inputs -> (V_o,V_i,C,H,W) reprojected images and depths (reference ibr.py:52-93)."""
+def reproject_views(image_in, depth_in, depth_out, camera_in, camera_out, kernel=None):
+    """(V_i,C,H,W) inputs -> (V_o,V_i,C,H,W) reprojected images and depths (reference ibr.py:52-93).
+    kernel: None (the module's KERNEL) | 'composed' | 'fused'."""
+    if _resolve_kernel(kernel) == 'fused':
+        image_re, depth_re = _fused_reproject(image_in.unsqueeze(0), depth_in.unsqueeze(0), depth_out.unsqueeze(0), camera_in,
+                                              camera_out)
+        return image_re.squeeze(0), depth_re.squeeze(0)
     grid = bv2b(depth_to_warp_field(camera_in, camera_out, depth_out))
     v_i, v_o = len(camera_in), len(camera_out)
     image = bv2b(image_in.unsqueeze(0).expand(v_o, -1, -1, -1, -1))
@@ -75,33 +106,58 @@ def reproject_views(image_in, depth_in, depth_out, camera_in, camera_out):
     return b2bv(image_re, v_i), b2bv(depth_re, v_i)
 
 
-def reproject_views_batch(image_in, depth_in, depth_out, camera_in, camera_out):
-    """reproject_views per object of a batch (reference ibr.py:96-138).
+def _camera_distances(camera_in, camera_out, nb):
+    """Rotation / position distances between every output and input camera of each object, each (B,V_o,V_i)."""
+    n_in, n_out = len(camera_in) // nb, len(camera_out) // nb
+    dist_r, dist_t = [], []
+    for i in range(nb):
+        cin, cout = camera_in[i * n_in:(i + 1) * n_in], camera_out[i * n_out:(i + 1) * n_out]
+        dist_r.append(three.quaternion.angular_distance(cout.quaternion, cin.quaternion, eps=1e-2) / math.pi)
+        dist_t.append(outer_distance(cout.position, cin.position, metric='cosine') / 2.0)
+    return torch.stack(dist_r, dim=0), torch.stack(dist_t, dim=0)
+
+
+def reproject_views_batch(image_in, depth_in, depth_out, camera_in, camera_out, kernel=None, mask_out=None, out=None):
+    """reproject_views per object of a batch (reference ibr.py:96-138).  kernel as in reproject_views; with 'fused' all
+    objects are one launch, and mask_out / out are handed to ops.ibr_reproject (they are refused on 'composed').
 
     image_in (B,V_i,C,H,W), depth_in (B,V_i,1,H,W), depth_out (B,V_o,1,H,W); cameras flat, object-major.
     Returns reprojected images and depths (B,V_o,V_i,.,H,W) and the rotation / position distances between every
     output and input camera, each (B,V_o,V_i): angular distance / pi (acos clamp 1e-2) and cosine distance / 2."""
     nb, n_in, n_out = image_in.shape[0], image_in.shape[1], depth_out.shape[1]
+    if _resolve_kernel(kernel) == 'fused':
+        image_re, depth_re = _fused_reproject(image_in, depth_in, depth_out, camera_in, camera_out, mask_out, out)
+        return (image_re, depth_re) + _camera_distances(camera_in, camera_out, nb)
+    if mask_out is not None or out is not None:
+        raise ValueError("mask_out / out belong to kernel='fused'")
     imgs, deps, dist_r, dist_t = [], [], [], []
     for i in range(nb):
         cin, cout = camera_in[i * n_in:(i + 1) * n_in], camera_out[i * n_out:(i + 1) * n_out]
         dist_r.append(three.quaternion.angular_distance(cout.quaternion, cin.quaternion, eps=1e-2) / math.pi)
         dist_t.append(outer_distance(cout.position, cin.position, metric='cosine') / 2.0)
-        img_re, dep_re = reproject_views(image_in[i], depth_in[i], depth_out[i], cin, cout)
+        img_re, dep_re = reproject_views(image_in[i], depth_in[i], depth_out[i], cin, cout, kernel='composed')
         imgs.append(img_re)
         deps.append(dep_re)
     return torch.stack(imgs, dim=0), torch.stack(deps, dim=0), torch.stack(dist_r, dim=0), torch.stack(dist_t, dim=0)
 
 
-def render_ibr(camera_in, camera_out, image_in, depth_fake_in, depth_fake_out, p=0.5, weight_type='cam_dist', eps=1e-2):
+def render_ibr(camera_in, camera_out, image_in, depth_fake_in, depth_fake_out, p=0.5, weight_type='cam_dist', eps=1e-2,
+               kernel=None):
     """Blend of the reprojected input views, weights softmax(1 / clamp(d^p, eps)) over the inputs
-    (reference ibr.py:181-222; weight types cam_dist / cam_angle / cam_hybrid / depth)."""
+    (reference ibr.py:181-222; weight types cam_dist / cam_angle / cam_hybrid / depth).  kernel as in reproject_views
+    ('fused': one reprojection launch for all objects)."""
     outs, reprojs = [], []
     nb = image_in.shape[0]
     n_in, n_out = len(camera_in) // nb, len(camera_out) // nb
+    fused = None
+    if _resolve_kernel(kernel) == 'fused':
+        fused = _fused_reproject(image_in, depth_fake_in, depth_fake_out, camera_in, camera_out)
     for i in range(nb):
         cin, cout = camera_in[i * n_in:(i + 1) * n_in], camera_out[i * n_out:(i + 1) * n_out]
-        img_re, depth_re = reproject_views(image_in[i], depth_fake_in[i], depth_fake_out[i], cin, cout)
+        if fused is not None:
+            img_re, depth_re = fused[0][i], fused[1][i]
+        else:
+            img_re, depth_re = reproject_views(image_in[i], depth_fake_in[i], depth_fake_out[i], cin, cout, kernel='composed')
         reprojs.append(img_re)
         if weight_type == 'depth':
             diff = (depth_re - depth_fake_out[i].unsqueeze(1).expand_as(depth_re)).abs()
@@ -122,12 +178,14 @@ def render_ibr(camera_in, camera_out, image_in, depth_fake_in, depth_fake_out, p
     return torch.stack(outs, dim=0), torch.stack(reprojs, dim=0)
 
 
-def render_latent_ibr(photographer, z_obj, camera_in, camera_out, image_in, p=0.5, weight_type='cam_dist', eps=0.0001):
+def render_latent_ibr(photographer, z_obj, camera_in, camera_out, image_in, p=0.5, weight_type='cam_dist', eps=0.0001,
+                      kernel=None):
     """Depths of the input and output views from the latent renderer, colour by IBR; differentiable, returns
     (colour, depth_out, mask_out, reprojections) (reference ibr.py:141-154)."""
     fake_in, _, _ = photographer.decode(z_obj, camera_in)
     fake_out, _, _ = photographer.decode(z_obj, camera_out)
-    color, reproj = render_ibr(camera_in, camera_out, image_in, fake_in['depth'], fake_out['depth'], p, weight_type, eps)
+    color, reproj = render_ibr(camera_in, camera_out, image_in, fake_in['depth'], fake_out['depth'], p, weight_type, eps,
+                               kernel=kernel)
     return color, fake_out['depth'], fake_out['mask'], reproj
 
 
@@ -158,11 +216,11 @@ def warp_blend_logits(logits, image_reproj, flow_size):
 
 
 def render_latent_ibr2(photographer, z_obj, camera_in, camera_out, image_in, p=0.5, weight_type='cam_dist',
-                       return_latent=True, eps=0.0001, apply_mask=False):
+                       return_latent=True, eps=0.0001, apply_mask=False, kernel=None):
     """Depth from the latent renderer for input and output views, colour by IBR (reference ibr.py:157-178)."""
     with torch.no_grad():
         y_in, _, _ = photographer.decode(z_obj, camera_in, apply_mask=apply_mask)
         y_out, z_out, _ = photographer.decode(z_obj, camera_out, return_latent=return_latent, apply_mask=apply_mask)
-    color, _ = render_ibr(camera_in, camera_out, image_in, y_in['depth'], y_out['depth'], p, weight_type, eps)
+    color, _ = render_ibr(camera_in, camera_out, image_in, y_in['depth'], y_out['depth'], p, weight_type, eps, kernel=kernel)
     y_out['color'] = color * (y_out['mask'] > 0.5) if apply_mask else color
     return y_out, z_out

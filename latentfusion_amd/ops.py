@@ -1475,6 +1475,175 @@ def grid_sample2d(img, grid, mode='bilinear', padding_mode='zeros'):
 
 
 # ---------------------------------------------------------------------------------------------
+# fused IBR reprojection (ibr.reproject_views as one launch for all objects, views and pixels)
+# ---------------------------------------------------------------------------------------------
+class IbrRecords:
+    """Camera records of lf_ibr_reproject_* (layout: include/lf_hip.h): `pair` (B,V_o,V_i,32), `view_in` (B,V_i,16),
+    `view_out` (B,V_o,16), fp32, slices of one buffer so that `to(device)` is one copy."""
+
+    def __init__(self, flat, batch, n_out, n_in):
+        self.flat, self.batch, self.n_out, self.n_in = flat, batch, n_out, n_in
+        n_pair, n_vin = batch * n_out * n_in * _lib.LF_IBR_PAIR_FLOATS, batch * n_in * _lib.LF_IBR_VIEW_FLOATS
+        self.pair = flat[:n_pair].view(batch, n_out, n_in, _lib.LF_IBR_PAIR_FLOATS)
+        self.view_in = flat[n_pair:n_pair + n_vin].view(batch, n_in, _lib.LF_IBR_VIEW_FLOATS)
+        self.view_out = flat[n_pair + n_vin:].view(batch, n_out, _lib.LF_IBR_VIEW_FLOATS)
+
+    def to(self, device):
+        return IbrRecords(self.flat.to(device), self.batch, self.n_out, self.n_in)
+
+
+def _mm4(a, b):
+    """(..., n, 4) @ (..., 4, m), written out term by term: every element is the same four products and three sums whatever
+    the batch shape, which a library matmul does not promise."""
+    return sum(a[..., :, k, None] * b[..., None, k, :] for k in range(4))
+
+
+def pack_ibr_cameras(camera_in, camera_out, batch_size=1, depth_eps=0.01):
+    """Host packing of the camera records of `ibr_reproject` for flat, object-major cameras (len = batch_size * views).
+
+    Per pair (o, i): output camera -> object -> input image with the input viewport folded in, and input camera -> object ->
+    z row of the output camera with the output camera's depth normalisation folded in; per view: the unprojection of the
+    viewport lattice (and, for output views, the depth denormalisation).  Everything is formed in fp64 from the Camera
+    properties, pair by pair (a record does not depend on its batch mates), and rounded once to fp32; the entries of the
+    sampling-coordinate chain also carry the fp32 rounding of what that leaves (see the header).  Returns IbrRecords on the
+    cameras' device."""
+    dev = camera_in.device
+    if camera_out.device != dev:
+        raise ValueError('camera_in and camera_out must be on one device')
+    n_in, n_out = len(camera_in) // batch_size, len(camera_out) // batch_size
+    if n_in * batch_size != len(camera_in) or n_out * batch_size != len(camera_out) or n_in < 1 or n_out < 1:
+        raise ValueError('the camera counts must be positive multiples of batch_size')
+
+    def host(cam, n):
+        c = cam._map(lambda t: t.detach().to('cpu', torch.float64))
+        rot, t = c.rotation_matrix[:, :3, :3], c.translation
+        ext = torch.zeros(len(c), 4, 4, dtype=torch.float64)
+        inv = torch.zeros(len(c), 4, 4, dtype=torch.float64)
+        ext[:, :3, :3], ext[:, :3, 3], ext[:, 3, 3] = rot, t, 1.0                           # obj_to_cam
+        inv[:, :3, :3], inv[:, 3, 3] = rot.transpose(1, 2), 1.0                             # cam_to_obj
+        inv[:, :3, 3] = -sum(rot[:, k, :] * t[:, k, None] for k in range(3))
+        vp = c.viewport
+        view = torch.zeros(len(c), _lib.LF_IBR_VIEW_FLOATS, dtype=torch.float64)
+        view[:, 0], view[:, 1] = c.viewport_width / c.fu, (vp[:, 0] - c.u0) / c.fu
+        view[:, 2], view[:, 3] = c.viewport_height / c.fv, (vp[:, 1] - c.v0) / c.fv
+        zn, zf = c.znear - depth_eps, c.zfar + depth_eps
+        view[:, 4], view[:, 5] = (zf - zn) / 2.0, (zf + zn) / 2.0
+        bv = lambda x: x.view(batch_size, n, *x.shape[1:])                                   # noqa: E731
+        return dict(K=bv(c.intrinsic), ext=bv(ext), inv=bv(inv), vp=bv(vp), view=bv(view), zn=bv(zn), zf=bv(zf))
+
+    ci, co = host(camera_in, n_in), host(camera_out, n_out)
+    # (B, V_o, V_i, ., .) by broadcasting: i on axis 2, o on axis 1
+    to_img = _mm4(_mm4(ci['K'][:, None], ci['ext'][:, None]), co['inv'][:, :, None])         # 3x4
+    vp_i = ci['vp'][:, None]
+    n0 = (to_img[..., 0, :] - vp_i[..., 0, None] * to_img[..., 2, :]) / (vp_i[..., 2] - vp_i[..., 0])[..., None]
+    n1 = (to_img[..., 1, :] - vp_i[..., 1, None] * to_img[..., 2, :]) / (vp_i[..., 3] - vp_i[..., 1])[..., None]
+    zrow = _mm4(co['ext'][:, :, None, 2:3, :], ci['inv'][:, None])[..., 0, :].clone()         # 1x4
+    zn, zf = co['zn'][:, :, None], co['zf'][:, :, None]
+    zrow[..., 3] = zrow[..., 3] - zn
+    zrow = zrow / (zf - zn)[..., None]
+    def split(v, n, at):                                # entries [0, n): leading float at [k], float of the remainder at [at + k]
+        lead = v.to(torch.float32)
+        lead[..., at:at + n] = (v[..., :n] - lead[..., :n].double()).to(torch.float32)
+        return lead
+
+    pair = torch.zeros(*n0.shape[:-1], _lib.LF_IBR_PAIR_FLOATS, dtype=torch.float64)
+    pair[..., 0:4], pair[..., 4:8], pair[..., 8:12], pair[..., 12:16] = n0, n1, to_img[..., 2, :], zrow
+    view_in = ci['view'].clone()
+    view_in[..., 4:] = 0.0
+    flat = torch.cat((split(pair, 12, _lib.LF_IBR_PAIR_SPLIT).reshape(-1), view_in.to(torch.float32).reshape(-1),
+                      split(co['view'], 6, _lib.LF_IBR_VIEW_SPLIT).reshape(-1)))
+    return IbrRecords(flat.to(dev), batch_size, n_out, n_in)
+
+
+def _ibr_shapes(image_in, depth_in, depth_out, mask_out, rec):
+    if image_in.dim() != 5:
+        raise ValueError('image_in must be (B, V_i, C, H, W)')
+    B, Vi, C, H, W = image_in.shape
+    Vo = rec.n_out
+    if (rec.batch, rec.n_in) != (B, Vi):
+        raise ValueError(f'records are for (B, V_i) = {(rec.batch, rec.n_in)}, image_in has {(B, Vi)}')
+    for t, n, name in ((depth_in, Vi, 'depth_in'), (depth_out, Vo, 'depth_out'), (mask_out, Vo, 'mask_out')):
+        if t is not None and (t.numel() != B * n * H * W or tuple(t.shape[:2]) != (B, n) or tuple(t.shape[-2:]) != (H, W)):
+            raise ValueError(f'{name} must be (B, {n}, 1, H, W) = ({B}, {n}, 1, {H}, {W}), got {tuple(t.shape)}')
+    return B, Vo, Vi, C, H, W
+
+
+def _ibr_fwd(image_in, depth_in, depth_out, mask_out, rec, out):
+    L = _lib.lib()
+    for t, name in ((image_in, 'image_in'), (depth_in, 'depth_in'), (depth_out, 'depth_out'), (rec.flat, 'records')):
+        _req(t, name)
+    B, Vo, Vi, C, H, W = _ibr_shapes(image_in, depth_in, depth_out, mask_out, rec)
+    image_in, depth_in, depth_out = image_in.contiguous(), depth_in.contiguous(), depth_out.contiguous()
+    if mask_out is not None:
+        mask_out = _req(mask_out, 'mask_out').contiguous()
+    if out is None:
+        image_re = torch.empty(B, Vo, Vi, C, H, W, device=image_in.device, dtype=torch.float32)
+        depth_re = torch.empty(B, Vo, Vi, 1, H, W, device=image_in.device, dtype=torch.float32)
+        strides = (C * H * W, H * W)
+    else:
+        rows = out.view(B, Vo, Vi, C + 2, H, W)
+        image_re, depth_re = rows[:, :, :, :C], rows[:, :, :, C:C + 1]
+        strides = ((C + 2) * H * W, (C + 2) * H * W)
+    check(L.lf_ibr_reproject_fwd(_ptr(image_in), _ptr(depth_in), _ptr(depth_out), _ptr(mask_out) if mask_out is not None else None,
+                                 rec.pair.data_ptr(), rec.view_in.data_ptr(), rec.view_out.data_ptr(), _ptr(image_re),
+                                 _ptr(depth_re), B, Vo, Vi, C, H, W, strides[0], strides[1], _stream()), 'lf_ibr_reproject_fwd')
+    return (image_in, depth_in, depth_out, mask_out), (image_re, depth_re)
+
+
+class _IbrReproject(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image_in, depth_in, depth_out, mask_out, rec):
+        saved, outs = _ibr_fwd(image_in, depth_in, depth_out, mask_out, rec, None)
+        ctx.save_for_backward(*saved)
+        ctx.rec = rec
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_image, g_depth):
+        L = _lib.lib()
+        image_in, depth_in, depth_out, mask_out = ctx.saved_tensors
+        rec = ctx.rec
+        B, Vo, Vi, C, H, W = _ibr_shapes(image_in, depth_in, depth_out, mask_out, rec)
+        need = ctx.needs_input_grad
+        if not any(need[:3]) or (g_image is None and g_depth is None):
+            return None, None, None, None, None
+        g_image = g_image.float().contiguous() if g_image is not None else None
+        g_depth = g_depth.float().contiguous() if g_depth is not None else None
+        gi = torch.zeros_like(image_in) if need[0] else None
+        gdi = torch.zeros_like(depth_in) if need[1] else None
+        gdo = torch.empty_like(depth_out) if need[2] else None
+        opt = lambda t: _ptr(t) if t is not None else None                                   # noqa: E731
+        check(L.lf_ibr_reproject_bwd(_ptr(image_in), _ptr(depth_in), _ptr(depth_out), opt(mask_out), rec.pair.data_ptr(),
+                                     rec.view_in.data_ptr(), rec.view_out.data_ptr(), opt(g_image), opt(g_depth), opt(gi), opt(gdi),
+                                     opt(gdo), B, Vo, Vi, C, H, W, _stream()), 'lf_ibr_reproject_bwd')
+        return gi, gdi, gdo, None, None
+
+
+def ibr_reproject(image_in, depth_in, depth_out, records, mask_out=None, out=None):
+    """ibr.reproject_views for B objects in one launch (lf_ibr_reproject_fwd / _bwd): image_in (B,V_i,C,H,W), depth_in
+    (B,V_i,1,H,W), depth_out (B,V_o,1,H,W), records = pack_ibr_cameras(...).  Returns (image_re, depth_re), shaped
+    (B,V_o,V_i,C|1,H,W).  mask_out (B,V_o,1,H,W): the outputs are image_re * m and (depth_re + 1) * m - 1, bit for bit
+    (a constant: a mask that requires grad is refused).  out: a contiguous (B*V_o, V_i, C+2, H, W) buffer the results are
+    written into (channels [0, C) and C; channel C+1 is left alone); the returned tensors are views of it and carry no
+    gradient, so inputs that require grad are refused with `out`.  Differentiable w.r.t. image_in, depth_in, depth_out."""
+    if not isinstance(records, IbrRecords):
+        raise TypeError('records must come from pack_ibr_cameras')
+    grad = torch.is_grad_enabled()
+    if mask_out is not None and grad and mask_out.requires_grad:
+        raise NotImplementedError('ibr_reproject: mask_out is a constant of the fused kernel; apply a differentiable mask outside')
+    if out is not None:
+        if grad and any(t.requires_grad for t in (image_in, depth_in, depth_out)):
+            raise NotImplementedError('ibr_reproject: results written into `out` carry no gradient')
+        B, Vi, C, H, W = image_in.shape
+        if not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous()
+                and out.numel() == B * records.n_out * Vi * (C + 2) * H * W):
+            raise ValueError('out must be a contiguous float32 device tensor of B*V_o*V_i*(C+2)*H*W elements')
+        with torch.no_grad():
+            return _ibr_fwd(image_in, depth_in, depth_out, mask_out, records, out)[1]
+    return _IbrReproject.apply(image_in, depth_in, depth_out, mask_out, records)
+
+
+# ---------------------------------------------------------------------------------------------
 # standalone PixelNorm / rescale
 # ---------------------------------------------------------------------------------------------
 class _PixelNorm(torch.autograd.Function):

@@ -27,14 +27,17 @@ class _Frozen:
 
 class LatentFusionModel:
     @classmethod
-    def from_checkpoint(cls, checkpoint, device='cpu'):
+    def from_checkpoint(cls, checkpoint, device='cpu', ibr_kernel=None):
         if isinstance(checkpoint, (Path, str)):
             checkpoint = torch.load(checkpoint, map_location='cpu', weights_only=False)
         sculptor, fuser, photographer, _, generator = models.load_models(checkpoint, device=device, return_generator=True)
-        return cls(sculptor, fuser, photographer, checkpoint['args']['camera_dist'], device, generator=generator)
+        return cls(sculptor, fuser, photographer, checkpoint['args']['camera_dist'], device, generator=generator,
+                   ibr_kernel=ibr_kernel)
 
-    def __init__(self, sculptor, fuser, photographer, camera_dist, device, generator=None):
+    def __init__(self, sculptor, fuser, photographer, camera_dist, device, generator=None, ibr_kernel=None):
+        """ibr_kernel: how the colour paths reproject (ibr.reproject_views): None = ibr.KERNEL, 'composed' or 'fused'."""
         self.device = device
+        self.ibr_kernel = ibr_kernel
         self.sculptor, self.fuser, self.photographer = sculptor.to(device), fuser.to(device), photographer.to(device)
         self.generator = generator.to(device) if generator is not None else None
         self.camera_dist = camera_dist
@@ -119,7 +122,7 @@ class LatentFusionModel:
         y, z = ibr.render_latent_ibr2(self.photographer, z_obj, input_obs.camera.clone().to(self.device),
                                       camera_out.clone().to(self.device),
                                       b2bv(input_obs.color, batch_size=1).to(self.device), p=p, weight_type='cam_dist',
-                                      return_latent=return_latent, apply_mask=apply_mask)
+                                      return_latent=return_latent, apply_mask=apply_mask, kernel=self.ibr_kernel)
         if return_latent:
             z = z.squeeze(0)
         return {k: v.squeeze(0) for k, v in y.items()}, z
@@ -132,29 +135,55 @@ class LatentFusionModel:
         if self.generator is None:
             raise ValueError('this checkpoint carries no IBR generator (modules.generator)')
         input_obs = self.preprocess_observation(input_obs)
+        stack = None
+        if ibr._resolve_kernel(self.ibr_kernel) == 'fused':
+            # the generator's stacked input (B*V_o, V_i, C+2, H, W): the fused kernel writes colour and depth straight into it
+            v_i, c, h, w = input_obs.color.shape
+            stack = torch.empty(len(camera_out), v_i, c + 2, h, w, device=input_obs.color.device, dtype=torch.float32)
         y_out, z_out, image_reproj, depth_reproj, _mask_out, depth_out, _dist_r, dist_t = self._render_reprojections(
-            z_obj, input_obs.color, input_obs.camera, camera_out)
+            z_obj, input_obs.color, input_obs.camera, camera_out, out=stack)
         if return_latent:
             z_out = z_out.squeeze(0)
         sims = 1.0 - dist_t * 2
-        x = torch.cat((image_reproj, depth_reproj,
-                       sims[:, :, None, None, None].expand(-1, -1, -1, *image_reproj.shape[-2:])), dim=2)
+        if stack is not None and image_reproj.data_ptr() == stack.data_ptr():
+            x = stack
+            x[:, :, -1] = sims[:, :, None, None]
+        else:
+            x = torch.cat((image_reproj, depth_reproj,
+                           sims[:, :, None, None, None].expand(-1, -1, -1, *image_reproj.shape[-2:])), dim=2)
         x = x.reshape(-1, x.shape[1] * x.shape[2], x.shape[3], x.shape[4])              # views folded into channels
         x = torch.cat((depth_out, x), dim=1)
         logits = self.generator(x)
         y_out['color'], _, _, _ = ibr.warp_blend_logits(logits, image_reproj, 5)
         return {k: v.squeeze(0) for k, v in y_out.items()}, z_out
 
-    def _render_reprojections(self, z_obj, color_in, camera_in, camera_out, return_latent=True):
+    def _render_reprojections(self, z_obj, color_in, camera_in, camera_out, return_latent=True, out=None):
         """reference recon/inference.py:193-217: depths of the input and output views from the latent renderer, the
-        input views reprojected into every output view and masked by the predicted output mask."""
+        input views reprojected into every output view and masked by the predicted output mask.  With the 'fused' IBR kernel
+        the mask is applied in the kernel's store and, where nothing asks for a gradient, the results are written into `out`
+        ((B*V_o, V_i, C+2, H, W), see ops.ibr_reproject) and returned as views of it."""
         from .. import ibr
         from ..three.batchview import bv2b
         y_in, _, _ = self.photographer.decode(z_obj, camera_in)
         y_out, z_out, _ = self.photographer.decode(z_obj, camera_out, return_latent=return_latent)
         mask_out, depth_out = y_out['mask'], y_out['depth']
+        if ibr._resolve_kernel(self.ibr_kernel) == 'fused':
+            color_in = color_in.unsqueeze(0)
+            grad = torch.is_grad_enabled()
+            in_kernel = not (grad and mask_out.requires_grad)                            # (the kernel's mask is a constant)
+            if grad and any(t.requires_grad for t in (color_in, y_in['depth'], y_out['depth'])):
+                out = None
+            image_reproj, depth_reproj, dist_r, dist_t = ibr.reproject_views_batch(
+                color_in, y_in['depth'], y_out['depth'], camera_in, camera_out, kernel='fused',
+                mask_out=mask_out if in_kernel else None, out=out)
+            if not in_kernel:
+                image_reproj = image_reproj * mask_out.unsqueeze(2)
+                depth_reproj = (depth_reproj + 1.0) * mask_out.unsqueeze(2) - 1.0
+            return (y_out, z_out, bv2b(image_reproj), bv2b(depth_reproj), bv2b(mask_out), bv2b(depth_out), bv2b(dist_r),
+                    bv2b(dist_t))
         image_reproj, depth_reproj, dist_r, dist_t = ibr.reproject_views_batch(color_in.unsqueeze(0), y_in['depth'],
-                                                                                y_out['depth'], camera_in, camera_out)
+                                                                                y_out['depth'], camera_in, camera_out,
+                                                                                kernel='composed')
         image_reproj = image_reproj * mask_out.unsqueeze(2)
         depth_reproj = (depth_reproj + 1.0) * mask_out.unsqueeze(2) - 1.0
         return (y_out, z_out, bv2b(image_reproj), bv2b(depth_reproj), bv2b(mask_out), bv2b(depth_out), bv2b(dist_r),
