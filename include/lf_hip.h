@@ -731,6 +731,35 @@ int lf_epilogue_bwd(const float* gy, const float* y, const float* norm, float* g
 int lf_epilogue_bwd_amax(const float* gy, const float* y, const float* norm, float* gp,
                          long rows, int C, unsigned flags, float slope, float* amax_out, void* stream);
 
+/* ---- latent loss term of the pose loop (csrc/latent.hip) ---------------------------------------------------------------------
+ * Cosine distance between the projected latent zp [N][P][C] (channels-last, P = h*w) and the target's latent code zt, per
+ * hypothesis (reference pose/estimation.py:111-114 over distances.py:5-9 = 1 - torch.cosine_similarity(.., eps = 1e-8)):
+ *   dist = 1 - dot / (max(|zp|, eps) * max(|zt|, eps)),  dot = sum zp*zt over the row's P*C values.
+ * zt is read through ELEMENT STRIDES (the form chosen of the two the kernel could take; no host-side conversion): value
+ * (n, p, c) lives at zt[n*zt_sn + p*zt_sp + c*zt_sc], so an (N, C, h, w) tensor is passed as it is, NCHW-contiguous
+ * (zt_sp = 1, zt_sc = P) or channels-last (zt_sp = C, zt_sc = 1; f32x4 loads when 16-byte aligned).  zt_n = 1 broadcasts one
+ * code to all rows (zt_sn is then ignored), else zt_n = N.  Strides are >= 0.
+ *   lf_latent_cosine_fwd   sums[N][4] = (dot, |zp|^2, |zt|^2, dist).  losses [N][8] (lf_pose_loss_fwd's layout) may be NULL; else
+ *                          losses[n][5] = dist and losses[n][4] += w_latent * dist.  Two launches: per-workgroup partial sums
+ *                          into `scratch` (lf_latent_cosine_scratch_bytes(N, P, C) bytes), then a fixed-order fp64 finish per
+ *                          row; no float atomics.  A row's split into partial sums depends on (P, C) only: row i of a batch is
+ *                          bit-identical to a call on that row alone.
+ *   lf_latent_cosine_bwd_epi  gp = Epi'(g_in + gscale * d(dist)/d(zp); zp, norm, flags) in one launch: the addend of the latent
+ *                          term joins the decoder's gradient g_in (NULL: the addend alone) at the projection's OUTPUT zp, then
+ *                          the epilogue backward of lf_epilogue_bwd in its three forms, or flags = 0: the plain sum.
+ *                          d(dist)/d(zp) = -( zt/(a b) - dot zp/(a^2 b |zp|) ), a = max(|zp|, eps), b = max(|zt|, eps): as
+ *                          autograd of torch.cosine_similarity, whose clamp acts on the value only (|zp| = 0: no zp term).
+ *                          `sums` is the forward's output; norm[N*P] is required with LF_EPI_PIXELNORM; gp == g_in allowed.
+ * Domain: C % 4 == 0 (else LF_EALIGN), 4 <= C <= 256, P >= 1, N >= 1, N * slices < 2^31 (else LF_EINVAL); zp, g_in, gp, sums and
+ * scratch 16-byte aligned (LF_EALIGN); a short scratch buffer is LF_ENOSPC.  Nothing is written in any of these cases. */
+size_t lf_latent_cosine_scratch_bytes(int N, long P, int C);
+int lf_latent_cosine_fwd(const float* zp, const float* zt, int zt_n, long zt_sn, long zt_sp, long zt_sc, float* sums,
+                         float* losses, float w_latent, void* scratch, size_t scratch_bytes, int N, long P, int C,
+                         void* stream);
+int lf_latent_cosine_bwd_epi(const float* g_in, const float* zp, const float* norm, const float* zt, int zt_n, long zt_sn,
+                             long zt_sp, long zt_sc, const float* sums, float gscale, float* gp, int N, long P, int C,
+                             unsigned flags, float slope, void* stream);
+
 /* Block-end rescale by exactly x2 (up = 1) or x0.5 (up = 0): nearest (linear = 0) or bi-/tri-linear
  * with align_corners=False (linear = 1) = Interpolate / F.interpolate(scale_factor=...) of
  * modules/__init__.py:18-36, blocks.py:160-162.  x: [N][D][H][W][C] (D = 1 for dims = 2); the output

@@ -340,10 +340,24 @@ def select_proj_kernel(proj_kernel, default, K, cout):
     return proj_kernel
 
 
+LATENT_KERNELS = ('autograd', 'fused')
+
+
+def select_latent_kernel(latent_kernel, default):
+    """Resolved `latent_kernel` of a RenderLoopEngine: None -> `default`; anything but LATENT_KERNELS is refused.  Pure host logic
+    (tests/test_latent_fused_args.py)."""
+    if latent_kernel is None:
+        latent_kernel = default
+    if latent_kernel not in LATENT_KERNELS:
+        raise ValueError(f'latent_kernel {latent_kernel!r}: one of {LATENT_KERNELS}')
+    return latent_kernel
+
+
 # What a tail forward (camera blocks' output -> projected latent) hands on: zp / pnorm: the projected latent and its PixelNorm
 # factors as buffers (explicit decoder, ranking latent term); feat: the same latent as the autograd decoder / latent term reads
-# it; leaf: the tensor autograd differentiates the 2-D part back to; occ_saved: what the explicit occlusion backward reads.
-_Tail = collections.namedtuple('_Tail', 'zp pnorm feat leaf occ_saved')
+# it; leaf: the tensor autograd differentiates the 2-D part back to; occ_saved: what the explicit occlusion backward reads;
+# lat: (zt, sums, gscale) of a fused latent term, whose gradient _proj_pre_grad adds at zp (None: no such term).
+_Tail = collections.namedtuple('_Tail', 'zp pnorm feat leaf occ_saved lat', defaults=(None,))
 
 
 class RenderLoopEngine:
@@ -364,6 +378,8 @@ class RenderLoopEngine:
     PROJ_GEMM = True                 # wide blocks, ranking only: depth-innermost last block + library GEMM for the factor projection
     PROJ_KERNEL = 'library'          # what the PROJ_GEMM branch launches when proj_kernel is None: 'library' (addmm + leaky_relu_ +
                                      # lf_pixelnorm_fwd) or 'mfma' (lf_rows_gemm_epi, one launch)
+    LATENT_KERNEL = 'autograd'       # what evaluates the 'latent' loss term when latent_kernel is None: 'autograd' (ATen cosine chain,
+                                     # the loss and the 2-D decoder as autograd nodes) or 'fused' (lf_latent_cosine_fwd / _bwd_epi)
 
     @staticmethod
     def supports(photographer, loss_weights):
@@ -380,7 +396,8 @@ class RenderLoopEngine:
     FUSE_FORMS = ('fwd',)
     _select_blocks = staticmethod(select_camera_blocks)
 
-    def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None):
+    def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None,
+                 latent_kernel=None):
         """conv_mode selects the kernels of the 16->16 camera-block convolutions:
         'fp32'     direct implicit-GEMM on the fp32 MFMA (works for every channel count);
         'winograd' F(2x2x2,3x3x3) minimal filtering, all-fp32 arithmetic (fp32 MFMA + fp32 transforms);
@@ -398,6 +415,13 @@ class RenderLoopEngine:
         The option only chooses what that branch launches: on 16-channel blocks, the 'sum' projection's or the occlusion
         module's tail, and on calls with need_grad=True the branch does not run and the option is idle (no pack is built;
         `proj_rows_pack` is None).
+        latent_kernel: what evaluates the 'latent' loss term (cosine distance of the projected latent to z_target_latent):
+        'autograd' = the ATen chain of _latent_distance, on a gradient call with the pose loss and the 2-D decoder as autograd
+        nodes; 'fused' = lf_latent_cosine_fwd for the distance (ranking and gradient calls) and lf_latent_cosine_bwd_epi for its
+        gradient, added at the projected latent inside the projection's epilogue backward, so that a gradient call keeps the
+        explicit decoder and the two-launch loss; None = LATENT_KERNEL.  'fused' needs the projection's PixelNorm buffer: on
+        tails without one (the 'sum' projection, a tail run as modules) and on calls without a latent term the option is idle
+        and the existing path runs.
         (Measured-and-rejected variants -- three-term Winograd products, the fused projection backward, hypothesis groups on
         several streams, hipGraph replay -- live in experimental.RenderLoopEngineX.)"""
         self.ph = photographer
@@ -433,6 +457,7 @@ class RenderLoopEngine:
         factor = photographer.projection_type == 'factor'
         self.proj_kernel = select_proj_kernel(proj_kernel, self.PROJ_KERNEL, D * C if factor else None,
                                               photographer.projection_block.conv.module.weight.shape[0] if factor else None)
+        self.latent_kernel = select_latent_kernel(latent_kernel, self.LATENT_KERNEL)
         self.proj_rows_pack = None
         if factor:
             pw = photographer.projection_block.conv.module.weight
@@ -697,7 +722,9 @@ class RenderLoopEngine:
         proj_gemm = self.PROJ_GEMM and self._wide_factor and not need_grad
         acts, norms, rode = self._blocks_fwd(self._resample(cf20, n), flags, proj_gemm)
         tail = self._tail_fwd(acts[-1], rode, flags, need_grad, proj_gemm, n)
-        latent_grad = zt is not None and need_grad
+        # the latent term on its own kernels (latent_kernel 'fused'): needs the projection's epilogue buffers
+        fused_lat = zt is not None and self.latent_kernel == 'fused' and tail.pnorm is not None
+        latent_grad = zt is not None and need_grad and not fused_lat
         explicit = self.dec is not None and not latent_grad
         if explicit:
             dacts, dnorms, logits = self._decoder_fwd(tail.zp, tail.pnorm, flags, n)
@@ -723,8 +750,14 @@ class RenderLoopEngine:
             # are two kernel calls, and autograd only carries d(logits) back through a generic decoder
             lg = ops.cl(logits.detach())                          # (n,2,h,w) channels-last == [n][h*w][2]
             losses, gsums, scratch = self._loss_fwd(lg, coefs, masked_depth)
+            if fused_lat:
+                # distance of all rows in one call; it fills losses[:, 5] and adds its weighted share to losses[:, 4]
+                zt = zt.to(device=self.dev, dtype=torch.float32)
+                lat_sums = ops.latent_cosine_fwd(tail.zp, zt, losses, self.w_latent)
+                if need_grad:
+                    tail = tail._replace(lat=(zt, lat_sums, self.w_latent / self._mean_rows(n)))
             if not need_grad:
-                if zt is not None:
+                if zt is not None and not fused_lat:
                     # latent term of a ranking-only evaluation: cosine distance of the projected latent (estimation.py:112-116)
                     lat = self._latent_distance(tail.zp, zt, n)
                     losses[:, 5] = lat
@@ -734,7 +767,10 @@ class RenderLoopEngine:
             # (lf_pose_loss_bwd writes entries 18..23; 0..17 come from the resampler's coefficient gradient below)
             g_cf = torch.empty(n, NCOEF, device=self.dev, dtype=torch.float32)
             self._loss_bwd(lg, coefs, gsums, glogits, g_cf, scratch)
-            if explicit:
+            if explicit and fused_lat:
+                # the decoder's backward stops at d/d(zp): _proj_pre_grad adds the latent term there and applies the epilogue
+                gp, g_leaf = None, self._decoder_bwd(glogits, dacts, dnorms, flags, n, fold_first=False)
+            elif explicit:
                 gp, g_leaf = self._decoder_bwd(glogits, dacts, dnorms, flags, n), None
             else:
                 gp, (g_leaf,) = None, torch.autograd.grad(logits, [tail.leaf], grad_outputs=[glogits])
@@ -798,6 +834,11 @@ class RenderLoopEngine:
         return self._factor_bwd(tail, gp, g_leaf, acts, norms, flags, n)
 
     def _proj_pre_grad(self, tail, gp, g_leaf, flags):
+        """d/d(projection pre-activation): the explicit decoder's gp as it is, else the epilogue backward of the gradient at the
+        projected latent -- joined there by the gradient of a fused latent term (tail.lat), in the same pass."""
+        if tail.lat is not None:
+            zt, lat_sums, gscale = tail.lat
+            return ops.latent_cosine_bwd_epi(ops.cl(g_leaf), tail.zp, tail.pnorm, zt, lat_sums, gscale, flags)
         return gp if gp is not None else ops._epilogue_bwd(ops.cl(g_leaf), tail.zp, tail.pnorm, flags)
 
     def _factor_fwd(self, act, rode, flags, need_grad, proj_gemm, n):
@@ -939,8 +980,10 @@ class RenderLoopEngine:
         ops._conv1x1_raw(dacts[-1], hpk, hb, n, hh * ww, hw.shape[1], 1, hh * ww * hw.shape[1], 0, hw.shape[0], logits, hhe, 0)
         return dacts, dnorms, logits
 
-    def _decoder_bwd(self, glogits, dacts, dnorms, flags, n):
-        """d/d(logits) -> d/d(projection pre-activation): the heads, then the decoder's data gradients in reverse."""
+    def _decoder_bwd(self, glogits, dacts, dnorms, flags, n, fold_first=True):
+        """d/d(logits) -> d/d(projection pre-activation): the heads, then the decoder's data gradients in reverse.
+        fold_first=False stops one step short, at d/d(projected latent): the first layer's data gradient without the projection's
+        epilogue backward (a fused latent term joins before it, _proj_pre_grad)."""
         # each launch folds in the LeakyReLU' / PixelNorm' of the activation it lands on (whole records of 16 / 32 / 64 channels;
         # otherwise a separate pass); dacts[0] is the projected latent itself
         L = _lib.lib()
@@ -958,7 +1001,9 @@ class RenderLoopEngine:
         for i in range(len(self.dec) - 1, -1, -1):
             w2, _b2, he2, _pk2, pkt2 = self.dec[i]
             cin2 = w2.shape[1]
-            if cin2 in (16, 32, 64):
+            if i == 0 and not fold_first:
+                g2 = ops.conv3x3_bwd_data(g2, pkt2, cin2, he2, None)
+            elif cin2 in (16, 32, 64):
                 g2 = ops.conv3x3_bwd_data(g2, pkt2, cin2, he2, (dacts[i], dnorms[i], flags))
             else:
                 g2 = ops._epilogue_bwd(ops.conv3x3_bwd_data(g2, pkt2, cin2, he2, None), dacts[i], dnorms[i], flags)
@@ -993,6 +1038,10 @@ class RenderLoopEngine:
 
     def _objective(self, total):
         return total.mean()
+
+    def _mean_rows(self, n):
+        """Rows the optimised mean of a row's loss runs over (_objective): the scale of a fused latent term's gradient."""
+        return n
 
     def _latent_distance(self, zp, zt, n):
         """Cosine distance of every hypothesis's projected latent to the target's latent code (estimation.py:112-116)."""

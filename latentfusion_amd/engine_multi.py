@@ -6,7 +6,9 @@ RenderLoopEngine.  Everything below the loss already works per hypothesis; what 
     gradients are those of the mean over the row's own target, so the optimised quantity is sum_t mean_{i in t} total_i;
   * the coefficient gradient of the resampler sums each row as a launch of n rows would (lf_resample3d_bwd_coef_part with
     part_n = n): its fixed-order block partition no longer follows the batch size;
-  * the latent term's cosine distance is evaluated per target slice.
+  * the latent term's cosine distance is evaluated per target slice (latent_kernel 'autograd'), or for all T * n rows in one
+    lf_latent_cosine_fwd launch ('fused': that kernel's partial sums follow the row's shape only, never the batch), its
+    gradient scaled by 1 / n of the row's own target.
 So per target the losses and camera gradients are bit-identical to RenderLoopEngine on that target's n rows alone for the
 kernels whose per-sample arithmetic does not depend on the batch.  On renderers with wide (>= 64-channel) layers, the released
 architecture included, that needs per_target_plan=True: lf_wino_fused_gemm picks its frequency split
@@ -82,13 +84,15 @@ class MultiTargetEngine(RenderLoopEngine):
     MAX_ROWS = 65535
 
     def __init__(self, photographer, z_obj, targets, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None,
-                 per_target_plan=False):
+                 per_target_plan=False, latent_kernel=None):
         """per_target_plan: every fp32 wide (>= 64-channel) Winograd launch of a call -- the camera blocks' convolutions and data
         gradients, and the 2-D decoder's under ops.wide_parts -- takes the frequency split of a launch of ONE target's n rows
         (lf_wino_fused_gemm_part, part_n = n), so on wide renderers too every target's losses and camera gradients are
         bit-identical to RenderLoopEngine on its rows alone.  False (default): the batch's own plan, as before.  On a renderer
         without wide layers the option changes nothing; with conv_mode 'f16x3' it is refused (NotImplementedError): that
-        form's input and gradient scales are maxima over the whole batch, which no launch plan undoes."""
+        form's input and gradient scales are maxima over the whole batch, which no launch plan undoes.
+        latent_kernel: as RenderLoopEngine's; 'fused' evaluates the latent term of all T * n rows in one launch, bit-identical
+        per target to RenderLoopEngine(latent_kernel='fused') on that target's rows."""
         self.per_target_plan = bool(per_target_plan)
         if self.per_target_plan and conv_mode == 'f16x3':
             raise NotImplementedError("per_target_plan with conv_mode 'f16x3': the split-precision kernels scale their inputs and "
@@ -113,7 +117,7 @@ class MultiTargetEngine(RenderLoopEngine):
             vols, index = distinct_volumes(check_volumes(z_obj, len(targets)))
             z_obj = vols[0]
         super().__init__(photographer, z_obj, targets[0], loss_weights, conv_mode=conv_mode, fuse_projection=fuse_projection,
-                         proj_kernel=proj_kernel)
+                         proj_kernel=proj_kernel, latent_kernel=latent_kernel)
         dev = self.dev
         # several objects: the distinct volumes back to back [K][S][S][S][C], self.z the first of them (a view: no second copy)
         self.zs = self.vol_of = None
@@ -179,6 +183,9 @@ class MultiTargetEngine(RenderLoopEngine):
     def _objective(self, total):
         # sum over the targets of each target's mean: every row's gradient is what its own single-target loop sees
         return total.view(self.T, self._n).mean(dim=1).sum()
+
+    def _mean_rows(self, n):
+        return self._n
 
     def _latent_distance(self, zp, zt, n):
         # (one cosine distance per target slice: the same reductions, over the same shapes, as the single-target engine)

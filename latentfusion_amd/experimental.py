@@ -196,8 +196,9 @@ class RenderLoopEngineX(_engine.RenderLoopEngine):
     FUSE_FORMS = ('fwd', 'bwd')
     _select_blocks = staticmethod(select_camera_blocks)
 
-    def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None):
-        super().__init__(photographer, z_obj, target_obs, loss_weights, conv_mode, fuse_projection, proj_kernel)
+    def __init__(self, photographer, z_obj, target_obs, loss_weights, conv_mode='auto', fuse_projection=None, proj_kernel=None,
+                 latent_kernel=None):
+        super().__init__(photographer, z_obj, target_obs, loss_weights, conv_mode, fuse_projection, proj_kernel, latent_kernel)
         self.streams, self._side_streams = 1, []
         self._packs_built = False
         self._graph = None

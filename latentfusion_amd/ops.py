@@ -883,6 +883,69 @@ def _epilogue_bwd(gy, y, norm, flags):
     return gp
 
 
+def _latent_args(zp, zt):
+    """(N, P, C, zt as the kernel reads it, its (n, pixel, channel) element strides) of the latent-term entry points: zp a
+    channels-last (N,C,h,w) device tensor, zt (N or 1, C, h, w) in any layout whose pixels h*w sit at one stride (NCHW-contiguous
+    and channels-last both do: no copy); anything else is made contiguous once."""
+    _req(zp, 'zp')
+    _req(zt, 'zt')
+    if zp.dim() != 4 or zt.dim() != 4 or tuple(zt.shape[1:]) != tuple(zp.shape[1:]) or zt.shape[0] not in (1, zp.shape[0]):
+        raise ValueError(f'zp {tuple(zp.shape)} / zt {tuple(zt.shape)}: expected (N,C,h,w) and (N or 1,C,h,w)')
+    if not zp.is_contiguous(memory_format=torch.channels_last):
+        raise ValueError('zp must be channels-last')
+    N, C, h, w = zp.shape
+    if not ((h == 1 or zt.stride(2) == w * zt.stride(3)) and min(zt.stride()) >= 0):
+        zt = zt.contiguous()
+    sp = zt.stride(3) if w > 1 else (zt.stride(2) if h > 1 else 1)
+    return N, h * w, C, zt, (zt.stride(0), sp, zt.stride(1))
+
+
+def latent_cosine_fwd(zp, zt, losses=None, w_latent=0.0):
+    """Cosine distance of every row of the projected latent zp (N,C,h,w channels-last) to the target code zt (N or 1,C,h,w)
+    (lf_latent_cosine_fwd): -> sums (N,4) = (dot, |zp|^2, |zt|^2, dist).  losses (N,8), when given, receives dist in column 5 and
+    w_latent * dist on top of column 4, in place."""
+    L = _lib.lib()
+    N, P, C, zt, (sn, sp, sc) = _latent_args(zp, zt)
+    if losses is not None:
+        _req(losses, 'losses')
+        if tuple(losses.shape) != (N, 8) or not losses.is_contiguous():
+            raise ValueError('losses must be a contiguous (N,8) tensor')
+    sums = torch.empty(N, 4, device=zp.device, dtype=torch.float32)
+    nbytes = L.lf_latent_cosine_scratch_bytes(N, P, C)
+    scratch = torch.empty(nbytes // 4 + 4, device=zp.device, dtype=torch.float32)
+    with _timed('latent_cosine_fwd', f'{N}x{P}x{C}'):
+        check(L.lf_latent_cosine_fwd(_ptr(zp), _ptr(zt), zt.shape[0], sn, sp, sc, _ptr(sums),
+                                     _ptr(losses) if losses is not None else None, w_latent, _ptr(scratch, True),
+                                     scratch.numel() * 4, N, P, C, _stream()), 'lf_latent_cosine_fwd')
+    return sums
+
+
+def latent_cosine_bwd_epi(g_in, zp, norm, zt, sums, gscale, flags, out=None):
+    """gp = Epi'(g_in + gscale * d(dist)/d(zp); zp, norm, flags) (lf_latent_cosine_bwd_epi): the latent term's gradient joins the
+    decoder's gradient g_in (None: the addend alone) at the projected latent and the projection's LeakyReLU' / PixelNorm' is
+    applied in the same pass.  out: None = a new tensor, or g_in itself for the in-place form."""
+    L = _lib.lib()
+    N, P, C, zt, (sn, sp, sc) = _latent_args(zp, zt)
+    _req(sums, 'sums')
+    if tuple(sums.shape) != (N, 4) or not sums.is_contiguous():
+        raise ValueError('sums must be the (N,4) output of latent_cosine_fwd')
+    for t, name in ((g_in, 'g_in'), (out, 'out')):
+        if t is not None:
+            _req(t, name)
+            if tuple(t.shape) != tuple(zp.shape) or not t.is_contiguous(memory_format=torch.channels_last):
+                raise ValueError(f'{name} must be channels-last and shaped like zp')
+    if norm is not None:
+        _req(norm, 'norm')
+        if norm.numel() != N * P or not norm.is_contiguous():
+            raise ValueError('norm must hold N*h*w contiguous values')
+    gp = out if out is not None else torch.empty_like(zp, memory_format=torch.preserve_format)
+    with _timed('latent_cosine_bwd_epi', f'{N}x{P}x{C}'):
+        check(L.lf_latent_cosine_bwd_epi(_ptr(g_in) if g_in is not None else None, _ptr(zp), _ptr(norm) if norm is not None else None,
+                                         _ptr(zt), zt.shape[0], sn, sp, sc, _ptr(sums), gscale, _ptr(gp), N, P, C, flags, SLOPE,
+                                         _stream()), 'lf_latent_cosine_bwd_epi')
+    return gp
+
+
 def _wino_ok(x, weight):
     """The Winograd kernel serves 3-D 16 -> 16 convolutions on volumes of at least one 2x8x16 tile row."""
     return (x.dim() == 5 and tuple(weight.shape[:2]) == (16, 16) and x.shape[1] == 16

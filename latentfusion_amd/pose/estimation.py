@@ -66,21 +66,25 @@ def load_schedules_from_config(config):
 class PoseEstimator:
     def __init__(self, *, model, ranking_size, loss_weights, loss_func=None, return_camera_history=False,
                  verbose=False, shard_hypotheses=False, use_engine=True, conv_mode='auto', fuse_projection=None,
-                 proj_kernel=None):
+                 proj_kernel=None, latent_kernel=None):
         """shard_hypotheses (an addition; the reference is single-process): under torch.distributed every rank
         renders and scores only its contiguous slice of the pose hypotheses; the per-hypothesis rows (loss
         [+ camera parameters]) are all-gathered once per iteration (parallel.gather_rows) and every rank ranks the
         full set, so the returned ranking is identical on all ranks and to a one-rank run.  Host-random draws
         (initial hypotheses, GMM samples) are taken from rank 0."""
         self.model = model
-        # use_engine / conv_mode / fuse_projection / proj_kernel (additions): the fused render-and-score engine (engine.py)
-        # evaluates the hypotheses when the renderer and the loss are of the kind it sequences; False selects the generic module
-        # path.  proj_kernel ('library' / 'mfma' / None = the engine's default): the ranking path's factor projection
-        from ..engine import PROJ_KERNELS
+        # use_engine / conv_mode / fuse_projection / proj_kernel / latent_kernel (additions): the fused render-and-score engine
+        # (engine.py) evaluates the hypotheses when the renderer and the loss are of the kind it sequences; False selects the
+        # generic module path.  proj_kernel ('library' / 'mfma' / None = the engine's default): the ranking path's factor
+        # projection; latent_kernel ('autograd' / 'fused' / None = the engine's default): what evaluates the 'latent' loss term
+        from ..engine import LATENT_KERNELS, PROJ_KERNELS
         if proj_kernel is not None and proj_kernel not in PROJ_KERNELS:
             raise ValueError(f'proj_kernel {proj_kernel!r}: one of {PROJ_KERNELS} or None')
+        if latent_kernel is not None and latent_kernel not in LATENT_KERNELS:
+            raise ValueError(f'latent_kernel {latent_kernel!r}: one of {LATENT_KERNELS} or None')
         self.use_engine, self.conv_mode, self.fuse_projection = use_engine, conv_mode, fuse_projection
         self.proj_kernel = proj_kernel
+        self.latent_kernel = latent_kernel
         self._engine_cache = None
         self.last_scored_on_engine = False
         self.shard_hypotheses = bool(shard_hypotheses)
@@ -165,9 +169,9 @@ class PoseEstimator:
         if wants_x:                                                # measured-and-rejected variants: experimental.py
             from ..experimental import RenderLoopEngineX
             return RenderLoopEngineX(ph, z_obj, target_obs, self.loss_weights, conv_mode=self.conv_mode, fuse_projection=fp,
-                                     proj_kernel=self.proj_kernel)
+                                     proj_kernel=self.proj_kernel, latent_kernel=self.latent_kernel)
         return RenderLoopEngine(ph, z_obj, target_obs, self.loss_weights, conv_mode=self.conv_mode, fuse_projection=fp,
-                                proj_kernel=self.proj_kernel)
+                                proj_kernel=self.proj_kernel, latent_kernel=self.latent_kernel)
 
     def _ranking_engine(self, z_obj, target_obs):
         """One engine per (object, target) for the ranking-only estimators; the cache keeps both alive, so an address
@@ -805,7 +809,8 @@ class GradientPoseEstimator(PoseEstimator):
                     eng = MultiTargetEngine(self.model.photographer, z_obj if z_of is None else z_of[b:e], dev_targets[b:e],
                                             self.loss_weights,
                                             conv_mode=self.conv_mode, fuse_projection=self.fuse_projection,
-                                            proj_kernel=self.proj_kernel, per_target_plan=self.per_target_plan)
+                                            proj_kernel=self.proj_kernel, per_target_plan=self.per_target_plan,
+                                            latent_kernel=self.latent_kernel)
                     out += self._run_batch(eng, dev_targets[b:e], zoomed[b:e])
                     del eng
                 return out
