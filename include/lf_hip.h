@@ -760,6 +760,39 @@ int lf_latent_cosine_bwd_epi(const float* g_in, const float* zp, const float* no
                              long zt_sp, long zt_sc, const float* sums, float gscale, float* gp, int N, long P, int C,
                              unsigned flags, float slope, void* stream);
 
+/* ---- pose metrics on model point clouds (csrc/points.hip) ------------------------------------------------------------------
+ * ADD-S's nearest-point search and the point-pair means of ADD / ADD-sym / proj2d, batched over camera pairs (reference
+ * pose/metrics.py:79-109: compute_point_add, compute_point_add_s over best_distance, compute_point_proj2d).  Points are packed
+ * xyz fp32 rows; strides are in floats and >= 0, and a stride of 0 shares one cloud between all batches / rows (one model
+ * cloud, B camera pairs).
+ *   lf_nn_dist   dist[b][i] = min_j |T1_b x1[b][i] - T2_b x2[b][j]|, i < M, j < Q, idx[b][i] = the smallest such j (int32),
+ *                mean[b] = mean_i dist[b][i].  T1 / T2: NULL or [B][12] row-major 3x4 affine maps, applied in fp32 as
+ *                fmaf(t0, x, fmaf(t1, y, fmaf(t2, z, t3))) per row.  dist, idx and mean may each be NULL, not all three.
+ *                Distances are coordinate differences, squared and summed (one multiply, two fmaf), the minimum taken over
+ *                d^2 and one root per query: not the Gram form |a|^2 + |b|^2 - 2ab of torch.cdist, which loses 3e-3 .. 1.4e-2
+ *                of a nearest distance on a model cloud in fp32.  A query's dist and idx bits depend on that query and its
+ *                batch's candidates only (not on B, M, its place in the batch or the run); an exact tie returns the smallest
+ *                j.  mean: one fp64 partial sum per 64 consecutive queries into `scratch` (lf_nn_dist_scratch_bytes(B, M, Q) bytes,
+ *                needed only with mean), then a fixed-order fp64 finish per batch, no atomics; mean[b] does not depend on B.
+ *                NaN: a query with a NaN coordinate gets dist = NaN and idx = -1, the other queries are untouched; a NaN among
+ *                a batch's candidates makes every query of that batch NaN / -1 (as torch.min would), the other batches are
+ *                untouched.  INFINITE coordinates, and finite ones whose squared differences overflow, are outside the
+ *                contract (no fault; dist is then inf or NaN and idx may be -1).
+ *   lf_points_pair_dist   mean[r] = mean_p |dehom(A_r (x_p, 1)) - dehom(Bm_r (x_p, 1))|, r < R, p < P; A, Bm: [R][rows][4]
+ *                row-major.  rows = 4 divides by the fourth component and compares 3-D points (ADD with obj_to_cam), rows = 3
+ *                divides by the third and compares 2-D points (proj2d with the 3x4 obj_to_image).  One launch plus the same
+ *                fixed-order finish; scratch: lf_points_pair_dist_scratch_bytes(R, P) bytes; a row's mean does not depend on R.
+ * Domain: B, M, Q, R, P >= 1, B * M < 2^31, R <= 65535, rows in {3, 4}, required pointers not NULL (else LF_EINVAL); every
+ * pointer 4-byte aligned and scratch 8-byte aligned (LF_EALIGN; the kernels read the packed rows with 4-byte loads and keep
+ * fp64 partial sums in scratch); a short scratch buffer is LF_ENOSPC.
+ * Nothing is launched or written in any of these cases. */
+size_t lf_nn_dist_scratch_bytes(int B, int M, int Q);
+int lf_nn_dist(const float* x1, long x1_sb, const float* T1, const float* x2, long x2_sb, const float* T2, float* dist, int* idx,
+               float* mean, void* scratch, size_t scratch_bytes, int B, int M, int Q, void* stream);
+size_t lf_points_pair_dist_scratch_bytes(int R, int P);
+int lf_points_pair_dist(const float* pts, long pts_sr, const float* A, const float* Bm, int rows, float* mean, void* scratch,
+                        size_t scratch_bytes, int R, int P, void* stream);
+
 /* Block-end rescale by exactly x2 (up = 1) or x0.5 (up = 0): nearest (linear = 0) or bi-/tri-linear
  * with align_corners=False (linear = 1) = Interpolate / F.interpolate(scale_factor=...) of
  * modules/__init__.py:18-36, blocks.py:160-162.  x: [N][D][H][W][C] (D = 1 for dims = 2); the output

@@ -145,6 +145,10 @@ SIGNATURES = {
     'lf_latent_cosine_fwd': (c_int, [P, P, c_int, c_long, c_long, c_long, P, P, c_float, P, c_size_t, c_int, c_long, c_int, P]),
     'lf_latent_cosine_bwd_epi': (c_int, [P, P, P, P, c_int, c_long, c_long, c_long, P, c_float, P, c_int, c_long, c_int, c_uint,
                                          c_float, P]),
+    'lf_nn_dist_scratch_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'lf_nn_dist': (c_int, [P, c_long, P, P, c_long, P, P, P, P, P, c_size_t, c_int, c_int, c_int, P]),
+    'lf_points_pair_dist_scratch_bytes': (c_size_t, [c_int, c_int]),
+    'lf_points_pair_dist': (c_int, [P, c_long, P, P, c_int, P, P, c_size_t, c_int, c_int, P]),
     'lf_epilogue_bwd_c16_scratch_bytes': (c_size_t, [c_long]),
     'lf_epilogue_bwd_c16': (c_int, [P, P, P, P, P, P, c_size_t, c_long, c_uint, c_float, c_int, P]),
     'lf_resample3d_fwd_io': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),

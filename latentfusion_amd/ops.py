@@ -946,6 +946,97 @@ def latent_cosine_bwd_epi(g_in, zp, norm, zt, sums, gscale, flags, out=None):
     return gp
 
 
+def _points_arg(t, name, last, dims):
+    """A float32 device tensor of `dims` dimensions (one of them allowed) whose trailing shape is `last`, else ValueError."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f'{name} must be a device tensor: the HIP path has no CPU fallback')
+    if t.dtype != torch.float32:
+        raise ValueError(f'{name} must be float32')
+    if t.dim() not in dims or tuple(t.shape[-len(last):]) != tuple(last) or t.numel() == 0:
+        raise ValueError(f'{name} must be shaped (..., {", ".join(map(str, last))}), got {tuple(t.shape)}')
+    return t
+
+
+def _points_cloud(t, name, B):
+    """(n,3) or (1,n,3): one cloud shared by the B batches (batch stride 0); (B,n,3): one per batch -> (tensor, stride)."""
+    if t.dim() == 3 and t.shape[0] not in (1, B):
+        raise ValueError(f'{name} has {t.shape[0]} batches, expected 1 or {B}')
+    t = t.contiguous()
+    return t, (t.shape[-2] * 3 if t.dim() == 3 and t.shape[0] == B and B > 1 else 0)
+
+
+def nn_dist(x1, x2, T1=None, T2=None, want=('dist',)):
+    """For every query x1[b][i] the distance to the nearest candidate T2_b x2[b][j] of T1_b x1[b][i] (lf_nn_dist): direct
+    coordinate differences in fp32, the smallest index on ties.  x1 (M,3) or (B,M,3), x2 (Q,3) or (B,Q,3); a 2-D (or
+    one-batch) cloud is shared by all batches.  T1 / T2: None or (B,3,4) affine maps.  want: any of 'dist' (B,M), 'idx' (B,M) int32
+    and 'mean' (B,); -> a dict of them (without the batch dimension when no argument has one)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('dist', 'idx', 'mean') for w in want):
+        raise ValueError("want must name some of 'dist', 'idx', 'mean'")
+    _points_arg(x1, 'x1', (3,), (2, 3))
+    _points_arg(x2, 'x2', (3,), (2, 3))
+    for t, name in ((T1, 'T1'), (T2, 'T2')):
+        if t is not None:
+            _points_arg(t, name, (3, 4), (3,))
+    tensors = [t for t in (x1, x2, T1, T2) if t is not None]
+    if any(t.device != x1.device for t in tensors):
+        raise ValueError('x1, x2, T1 and T2 must be on one device')
+    batches = {t.shape[0] for t in tensors if t.dim() == 3 and t.shape[0] != 1}
+    if len(batches) > 1:
+        raise ValueError(f'batch sizes differ: {sorted(batches)}')
+    batched = any(t.dim() == 3 for t in tensors)
+    B = batches.pop() if batches else 1
+    for t, name in ((T1, 'T1'), (T2, 'T2')):
+        if t is not None and t.shape[0] != B:
+            raise ValueError(f'{name} must hold one map per batch ({B})')
+    x1, s1 = _points_cloud(x1, 'x1', B)
+    x2, s2 = _points_cloud(x2, 'x2', B)
+    M, Q = x1.shape[-2], x2.shape[-2]
+    L = _lib.lib()
+    T1 = T1.contiguous() if T1 is not None else None
+    T2 = T2.contiguous() if T2 is not None else None
+    dev = x1.device
+    dist = torch.empty(B, M, device=dev, dtype=torch.float32) if 'dist' in want else None
+    idx = torch.empty(B, M, device=dev, dtype=torch.int32) if 'idx' in want else None
+    mean = torch.empty(B, device=dev, dtype=torch.float32) if 'mean' in want else None
+    nbytes = L.lf_nn_dist_scratch_bytes(B, M, Q)
+    scratch = torch.empty(nbytes // 4 + 4, device=dev, dtype=torch.float32)
+    with _timed('nn_dist', f'{B}x{M}x{Q}'):
+        check(L.lf_nn_dist(_ptr(x1), s1, _ptr(T1) if T1 is not None else None, _ptr(x2), s2, _ptr(T2) if T2 is not None else None,
+                           _ptr(dist) if dist is not None else None, _ptr(idx) if idx is not None else None,
+                           _ptr(mean) if mean is not None else None, _ptr(scratch, True), scratch.numel() * 4, B, M, Q,
+                           _stream()), 'lf_nn_dist')
+    out = {'dist': dist, 'idx': idx, 'mean': mean}
+    return {k: (out[k] if batched else out[k][0]) for k in want}
+
+
+def points_pair_dist(points, A, B):
+    """Mean distance of the model points under two projective maps per row (lf_points_pair_dist): points (P,3) shared by all rows
+    or (R,P,3); A, B (R,4,4) -> 3-D points after the division by the fourth component (ADD with obj_to_cam), or (R,3,4) -> 2-D
+    points after the division by the third (proj2d with obj_to_image).  -> (R,) means."""
+    _points_arg(points, 'points', (3,), (2, 3))
+    if not isinstance(A, torch.Tensor) or A.dim() != 3 or tuple(A.shape[1:]) not in ((4, 4), (3, 4)):
+        raise ValueError('A must be shaped (R,4,4) or (R,3,4)')
+    _points_arg(A, 'A', tuple(A.shape[1:]), (3,))
+    _points_arg(B, 'B', tuple(A.shape[1:]), (3,))
+    if B.shape[0] != A.shape[0]:
+        raise ValueError(f'A and B hold {A.shape[0]} and {B.shape[0]} rows')
+    if points.device != A.device or points.device != B.device:
+        raise ValueError('points, A and B must be on one device')
+    R, rows = A.shape[0], A.shape[1]
+    points, sr = _points_cloud(points, 'points', R)
+    P = points.shape[-2]
+    L = _lib.lib()
+    A, B = A.contiguous(), B.contiguous()
+    mean = torch.empty(R, device=points.device, dtype=torch.float32)
+    nbytes = L.lf_points_pair_dist_scratch_bytes(R, P)
+    scratch = torch.empty(nbytes // 4 + 4, device=points.device, dtype=torch.float32)
+    with _timed('points_pair_dist', f'{R}x{P}x{rows}'):
+        check(L.lf_points_pair_dist(_ptr(points), sr, _ptr(A), _ptr(B), rows, _ptr(mean), _ptr(scratch, True), scratch.numel() * 4,
+                                    R, P, _stream()), 'lf_points_pair_dist')
+    return mean
+
+
 def _wino_ok(x, weight):
     """The Winograd kernel serves 3-D 16 -> 16 convolutions on volumes of at least one 2x8x16 tile row."""
     return (x.dim() == 5 and tuple(weight.shape[:2]) == (16, 16) and x.shape[1] == 16
