@@ -830,7 +830,9 @@ int lf_camera_coefs_bwd(const float* gcoefs, const float* jac, float* gparams, i
  *   losses  [N][8]  (depth, ov_depth, iou, mask, weighted total, 0,0,0)
  *   gsums   [N][8]  d(mean_n total)/d(sums), consumed by lf_pose_loss_bwd
  * lf_pose_loss_bwd writes glogits [N][h*w][2] and gcoefs[N][24] entries 18..23 (0..17 untouched).
- * All reductions are fixed-order (no float atomics).  scratch: lf_pose_loss_scratch_bytes. */
+ * All reductions are fixed-order (no float atomics).  scratch: lf_pose_loss_scratch_bytes.
+ * One argument check serves the eight entry points below, and nothing is launched on a rejected call: a NULL pointer,
+ * N < 1, h <= 1, w <= 1, H <= 0 or W <= 0 -> LF_EINVAL; scratch_bytes below lf_pose_loss_scratch_bytes -> LF_ENOSPC. */
 size_t lf_pose_loss_scratch_bytes(int N, int h, int w, int H, int W);
 int lf_pose_loss_fwd(const float* logits, const float* coefs, const float* target_depth,
                      const float* target_mask, const float* weights, float* sums, float* losses,
@@ -861,8 +863,9 @@ int lf_pose_loss_bwd_depth(const float* depth_and_logits, const float* coefs, co
 /* Several target frames in one launch: N = T * n samples grouped by target, sample i scored against frame i / n of
  * target_depth / target_mask [T][H*W]; gsums is d(mean over the n samples OF THE SAME TARGET)/d(sums).  Otherwise as
  * lf_pose_loss_fwd / _fwd_masked / _bwd, and per target the outputs (sums, losses, gsums, glogits, gcoefs 18..23) are
- * bit-identical to the single-target entry point called on that target's n rows alone.  Scratch:
- * lf_pose_loss_scratch_bytes(N, h, w, H, W).  NULL pointers, T < 1, n < 1 or N != T * n -> LF_EINVAL. */
+ * bit-identical to the single-target entry point called on that target's n rows alone: those are this launch plan with
+ * T = 1, n = N.  Scratch: lf_pose_loss_scratch_bytes(N, h, w, H, W).  Beyond the check above, T < 1, n < 1 or
+ * N != T * n -> LF_EINVAL. */
 int lf_pose_loss_fwd_mt(const float* logits, const float* coefs, const float* target_depth,
                         const float* target_mask, const float* weights, float* sums, float* losses,
                         float* gsums, void* scratch, size_t scratch_bytes,

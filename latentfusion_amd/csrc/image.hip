@@ -443,193 +443,142 @@ extern "C" size_t lf_pose_loss_scratch_bytes(int N, int h, int w, int H, int W) 
   return ((size_t)N * LOSS_NBLK * NSUM + 2 * (size_t)N * H * W + 2 * (size_t)N * H * w) * sizeof(float);
 }
 
-static int pose_loss_fwd_launch(int mode, const float* logits, const float* coefs, const float* target_depth,
-                                const float* target_mask, const float* weights, float* sums, float* losses,
-                                float* gsums, void* scratch, size_t scratch_bytes,
-                                int N, int h, int w, int H, int W, void* stream) {
+// ---- the pose loss: ONE forward plan and ONE backward plan over T targets x n hypotheses (rows grouped by target) ----
+// A single target frame is T = 1.  The frame-reading kernels run once per target on that target's rows: the SAME kernels
+// whatever T is (a compile-time variant with a per-sample frame pointer changed the compiler's contraction order of the
+// bilinear sums in the existing pose_loss_fwd_kernel instantiations too: profiles/pose_loss_mt_variant_isa.txt), so every
+// row is bit-identical to a call on its own target's rows alone by construction.  The stages that do not read the frame
+// run once over all N rows; the finish kernel's row argument only forms the mean's factor, 1/n.
+// MODE (0 head logits, 1 masked ranking form, 2 metric depth crop) picks the instantiation, once per kernel:
+static auto pose_loss_fwd_kernel_of(int mode) {
+  return mode == 1 ? pose_loss_fwd_kernel<1> : mode == 2 ? pose_loss_fwd_kernel<2> : pose_loss_fwd_kernel<0>;
+}
+static auto pose_loss_bwd_pixels_kernel_of(int mode) {
+  return mode == 2 ? pose_loss_bwd_pixels_kernel<2> : pose_loss_bwd_pixels_kernel<0>;
+}
+static auto pose_loss_bwd_cols_kernel_of(int mode) {
+  return mode == 2 ? pose_loss_bwd_cols_kernel<2> : pose_loss_bwd_cols_kernel<0>;
+}
+
+// The argument check of all eight entry points; nothing is launched on a rejected call.
+static int pose_loss_args(std::initializer_list<const void*> pointers, size_t scratch_bytes, int N, int T, int n, int h, int w,
+                          int H, int W) {
+  for (const void* p : pointers)
+    if (!p) return LF_EINVAL;
+  if (T < 1 || n < 1 || (long)T * n != (long)N) return LF_EINVAL;
+  if (h <= 1 || w <= 1 || H <= 0 || W <= 0) return LF_EINVAL;
+  return scratch_bytes < lf_pose_loss_scratch_bytes(N, h, w, H, W) ? LF_ENOSPC : 0;
+}
+
+static int pose_loss_fwd(int mode, int N, int T, int n, const float* logits, const float* coefs, const float* target_depth,
+                         const float* target_mask, const float* weights, float* sums, float* losses, float* gsums,
+                         void* scratch, size_t scratch_bytes, int h, int w, int H, int W, void* stream) {
   lf_clear_error();
-  if (N <= 0 || h <= 1 || w <= 1 || H <= 0 || W <= 0) return LF_EINVAL;
-  if (scratch_bytes < lf_pose_loss_scratch_bytes(N, h, w, H, W)) return LF_ENOSPC;
-  hipStream_t s = (hipStream_t)stream;
   float* partial = (float*)scratch;
-  if (mode == 1)
-    hipLaunchKernelGGL(pose_loss_fwd_kernel<1>, dim3(LOSS_NBLK, N), dim3(LOSS_BLOCK), 0, s, logits, coefs, target_depth,
-                       target_mask, partial, LOSS_NBLK, h, w, H, W);
-  else if (mode == 2)
-    hipLaunchKernelGGL(pose_loss_fwd_kernel<2>, dim3(LOSS_NBLK, N), dim3(LOSS_BLOCK), 0, s, logits, coefs, target_depth,
-                       target_mask, partial, LOSS_NBLK, h, w, H, W);
-  else
-    hipLaunchKernelGGL(pose_loss_fwd_kernel<0>, dim3(LOSS_NBLK, N), dim3(LOSS_BLOCK), 0, s, logits, coefs, target_depth,
-                       target_mask, partial, LOSS_NBLK, h, w, H, W);
-  int st = lf_launch_status();
+  // the masked form is forward only (the estimators that use it do not differentiate): its gsums land in the scratch tail
+  if (mode == 1) gsums = scratch ? partial + (size_t)N * LOSS_NBLK * NSUM : nullptr;
+  int st = pose_loss_args({logits, coefs, target_depth, target_mask, weights, sums, losses, gsums, scratch}, scratch_bytes, N,
+                          T, n, h, w, H, W);
   if (st) return st;
-  hipLaunchKernelGGL(pose_loss_finish_kernel, dim3(N), dim3(64), 0, s, partial, LOSS_NBLK, weights, N, H * W, sums, losses,
-                     gsums);
+  hipStream_t s = (hipStream_t)stream;
+  for (int t = 0; t < T; ++t) {
+    const long r0 = (long)t * n;
+    hipLaunchKernelGGL(pose_loss_fwd_kernel_of(mode), dim3(LOSS_NBLK, n), dim3(LOSS_BLOCK), 0, s, logits + r0 * h * w * 2,
+                       coefs + r0 * NOUT, target_depth + (long)t * H * W, target_mask + (long)t * H * W,
+                       partial + r0 * LOSS_NBLK * NSUM, LOSS_NBLK, h, w, H, W);
+    if ((st = lf_launch_status())) return st;
+  }
+  hipLaunchKernelGGL(pose_loss_finish_kernel, dim3(N), dim3(64), 0, s, partial, LOSS_NBLK, weights, n, H * W, sums, losses, gsums);
   return lf_launch_status();
 }
 
+static int pose_loss_bwd(int mode, int N, int T, int n, const float* logits, const float* coefs, const float* target_depth,
+                         const float* target_mask, const float* gsums, float* glogits, float* gcoefs, void* scratch,
+                         size_t scratch_bytes, int h, int w, int H, int W, void* stream) {
+  lf_clear_error();
+  int st = pose_loss_args({logits, coefs, target_depth, target_mask, gsums, glogits, gcoefs, scratch}, scratch_bytes, N, T, n,
+                          h, w, H, W);
+  if (st) return st;
+  hipStream_t s = (hipStream_t)stream;
+  float* partial = (float*)scratch;
+  float* gd = partial + (size_t)N * LOSS_NBLK * NSUM;
+  float* gm = gd + (size_t)N * H * W;
+  float* Td = gm + (size_t)N * H * W;
+  float* Tm = Td + (size_t)N * H * w;
+  for (int t = 0; t < T; ++t) {
+    const long r0 = (long)t * n;
+    hipLaunchKernelGGL(pose_loss_bwd_pixels_kernel_of(mode), dim3(LOSS_NBLK, n), dim3(LOSS_BLOCK), 0, s, logits + r0 * h * w * 2,
+                       coefs + r0 * NOUT, target_depth + (long)t * H * W, target_mask + (long)t * H * W, gsums + r0 * NSUM,
+                       gd + r0 * H * W, gm + r0 * H * W, partial + r0 * LOSS_NBLK * NSUM, LOSS_NBLK, h, w, H, W);
+    if ((st = lf_launch_status())) return st;
+  }
+  // gcoefs[n][18..23] <- reduced (ax, bx, ay, by, a_depth, b_depth) gradients; [0..17] are left to the resampler
+  hipLaunchKernelGGL(reduce_partials_kernel, dim3(N), dim3(64), 0, s, partial, LOSS_NBLK, gcoefs, 6, NOUT, 18);
+  hipLaunchKernelGGL(pose_loss_bwd_rows_kernel, dim3((w + 255) / 256, H, N), dim3(256), 0, s, coefs, gd, gm, Td, Tm, w, H, W);
+  hipLaunchKernelGGL(pose_loss_bwd_cols_kernel_of(mode), dim3((w + 255) / 256, h, N), dim3(256), 0, s, logits, coefs, Td, Tm,
+                     glogits, h, w, H);
+  return lf_launch_status();
+}
+
+// The entry points fill in (mode, N, T, n): one target frame is (N, 1, N).
 extern "C" int lf_pose_loss_fwd(const float* logits, const float* coefs, const float* target_depth,
                                 const float* target_mask, const float* weights, float* sums, float* losses,
                                 float* gsums, void* scratch, size_t scratch_bytes,
                                 int N, int h, int w, int H, int W, void* stream) {
-  return pose_loss_fwd_launch(0, logits, coefs, target_depth, target_mask, weights, sums, losses, gsums, scratch,
-                              scratch_bytes, N, h, w, H, W, stream);
+  return pose_loss_fwd(0, N, 1, N, logits, coefs, target_depth, target_mask, weights, sums, losses, gsums, scratch, scratch_bytes,
+                       h, w, H, W, stream);
 }
 
-extern "C" int lf_pose_loss_fwd_depth(const float* depth_and_logits, const float* coefs, const float* target_depth,
-                                      const float* target_mask, const float* weights, float* sums, float* losses,
-                                      float* gsums, void* scratch, size_t scratch_bytes,
-                                      int N, int h, int w, int H, int W, void* stream) {
-  return pose_loss_fwd_launch(2, depth_and_logits, coefs, target_depth, target_mask, weights, sums, losses, gsums, scratch,
-                              scratch_bytes, N, h, w, H, W, stream);
+extern "C" int lf_pose_loss_bwd(const float* logits, const float* coefs, const float* target_depth,
+                                const float* target_mask, const float* gsums, float* glogits, float* gcoefs,
+                                void* scratch, size_t scratch_bytes, int N, int h, int w, int H, int W, void* stream) {
+  return pose_loss_bwd(0, N, 1, N, logits, coefs, target_depth, target_mask, gsums, glogits, gcoefs, scratch, scratch_bytes, h, w,
+                       H, W, stream);
 }
 
 extern "C" int lf_pose_loss_fwd_masked(const float* logits, const float* coefs, const float* target_depth,
                                        const float* target_mask, const float* weights, float* sums, float* losses,
                                        void* scratch, size_t scratch_bytes,
                                        int N, int h, int w, int H, int W, void* stream) {
-  // forward only (the estimators that use this form do not differentiate): gsums lands in the scratch tail
-  float* gs = (float*)scratch + (size_t)N * LOSS_NBLK * NSUM;
-  return pose_loss_fwd_launch(1, logits, coefs, target_depth, target_mask, weights, sums, losses, gs, scratch,
-                              scratch_bytes, N, h, w, H, W, stream);
+  return pose_loss_fwd(1, N, 1, N, logits, coefs, target_depth, target_mask, weights, sums, losses, nullptr, scratch,
+                       scratch_bytes, h, w, H, W, stream);
 }
 
-static int pose_loss_bwd_launch(int mode, const float* logits, const float* coefs, const float* target_depth,
-                                const float* target_mask, const float* gsums, float* glogits, float* gcoefs,
-                                void* scratch, size_t scratch_bytes, int N, int h, int w, int H, int W, void* stream);
-
-extern "C" int lf_pose_loss_bwd(const float* logits, const float* coefs, const float* target_depth,
-                                const float* target_mask, const float* gsums, float* glogits, float* gcoefs,
-                                void* scratch, size_t scratch_bytes, int N, int h, int w, int H, int W, void* stream) {
-  return pose_loss_bwd_launch(0, logits, coefs, target_depth, target_mask, gsums, glogits, gcoefs, scratch, scratch_bytes, N, h, w, H, W,
-                              stream);
+extern "C" int lf_pose_loss_fwd_depth(const float* depth_and_logits, const float* coefs, const float* target_depth,
+                                      const float* target_mask, const float* weights, float* sums, float* losses,
+                                      float* gsums, void* scratch, size_t scratch_bytes,
+                                      int N, int h, int w, int H, int W, void* stream) {
+  return pose_loss_fwd(2, N, 1, N, depth_and_logits, coefs, target_depth, target_mask, weights, sums, losses, gsums, scratch,
+                       scratch_bytes, h, w, H, W, stream);
 }
 
 extern "C" int lf_pose_loss_bwd_depth(const float* depth_and_logits, const float* coefs, const float* target_depth,
                                       const float* target_mask, const float* gsums, float* gcrop, float* gcoefs,
                                       void* scratch, size_t scratch_bytes, int N, int h, int w, int H, int W, void* stream) {
-  return pose_loss_bwd_launch(2, depth_and_logits, coefs, target_depth, target_mask, gsums, gcrop, gcoefs, scratch, scratch_bytes, N, h, w,
-                              H, W, stream);
-}
-
-static int pose_loss_bwd_launch(int mode, const float* logits, const float* coefs, const float* target_depth,
-                                const float* target_mask, const float* gsums, float* glogits, float* gcoefs,
-                                void* scratch, size_t scratch_bytes, int N, int h, int w, int H, int W, void* stream) {
-  lf_clear_error();
-  if (N <= 0 || h <= 1 || w <= 1 || H <= 0 || W <= 0) return LF_EINVAL;
-  if (scratch_bytes < lf_pose_loss_scratch_bytes(N, h, w, H, W)) return LF_ENOSPC;
-  hipStream_t s = (hipStream_t)stream;
-  float* partial = (float*)scratch;
-  float* gd = partial + (size_t)N * LOSS_NBLK * NSUM;
-  float* gm = gd + (size_t)N * H * W;
-  float* Td = gm + (size_t)N * H * W;
-  float* Tm = Td + (size_t)N * H * w;
-  if (mode == 2)
-    hipLaunchKernelGGL(pose_loss_bwd_pixels_kernel<2>, dim3(LOSS_NBLK, N), dim3(LOSS_BLOCK), 0, s, logits, coefs, target_depth,
-                       target_mask, gsums, gd, gm, partial, LOSS_NBLK, h, w, H, W);
-  else
-    hipLaunchKernelGGL(pose_loss_bwd_pixels_kernel<0>, dim3(LOSS_NBLK, N), dim3(LOSS_BLOCK), 0, s, logits, coefs, target_depth,
-                       target_mask, gsums, gd, gm, partial, LOSS_NBLK, h, w, H, W);
-  int st = lf_launch_status();
-  if (st) return st;
-  // gcoefs[n][18..23] <- reduced (ax, bx, ay, by, a_depth, b_depth) gradients; [0..17] are left to the resampler
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3(N), dim3(64), 0, s, partial, LOSS_NBLK, gcoefs, 6, NOUT, 18);
-  hipLaunchKernelGGL(pose_loss_bwd_rows_kernel, dim3((w + 255) / 256, H, N), dim3(256), 0, s, coefs, gd, gm, Td, Tm, w, H, W);
-  if (mode == 2)
-    hipLaunchKernelGGL(pose_loss_bwd_cols_kernel<2>, dim3((w + 255) / 256, h, N), dim3(256), 0, s, logits, coefs, Td, Tm, glogits,
-                       h, w, H);
-  else
-    hipLaunchKernelGGL(pose_loss_bwd_cols_kernel<0>, dim3((w + 255) / 256, h, N), dim3(256), 0, s, logits, coefs, Td, Tm, glogits,
-                       h, w, H);
-  return lf_launch_status();
-}
-
-// ---- several target frames in one call (T targets x n hypotheses, grouped by target) ----
-// The frame-reading kernels run once per target on that target's rows: the SAME kernels as the single-target entry points
-// (a compile-time variant with a per-sample frame pointer changed the compiler's contraction order of the bilinear sums in
-// the existing pose_loss_fwd_kernel instantiations too: profiles/pose_loss_mt_variant_isa.txt), so every row is
-// bit-identical to a single-target call by construction.  The stages that
-// do not read the frame run once over all N rows; the finish kernel's N argument only forms the mean's factor, here 1/n.
-static bool pose_loss_mt_args_ok(int N, int T, int n) {
-  return T >= 1 && n >= 1 && (long)T * n == (long)N;
-}
-
-static int pose_loss_fwd_mt_launch(int mode, const float* logits, const float* coefs, const float* target_depth,
-                                   const float* target_mask, const float* weights, float* sums, float* losses,
-                                   float* gsums, void* scratch, size_t scratch_bytes,
-                                   int N, int T, int n, int h, int w, int H, int W, void* stream) {
-  if (N <= 0 || h <= 1 || w <= 1 || H <= 0 || W <= 0) return LF_EINVAL;
-  if (scratch_bytes < lf_pose_loss_scratch_bytes(N, h, w, H, W)) return LF_ENOSPC;
-  hipStream_t s = (hipStream_t)stream;
-  float* partial = (float*)scratch;
-  for (int t = 0; t < T; ++t) {
-    const long r0 = (long)t * n;
-    const float* lg = logits + r0 * h * w * 2;
-    const float* cf = coefs + r0 * NOUT;
-    const float* td = target_depth + (long)t * H * W;
-    const float* tm = target_mask + (long)t * H * W;
-    float* pt = partial + r0 * LOSS_NBLK * NSUM;
-    if (mode == 1)
-      hipLaunchKernelGGL(pose_loss_fwd_kernel<1>, dim3(LOSS_NBLK, n), dim3(LOSS_BLOCK), 0, s, lg, cf, td, tm, pt, LOSS_NBLK, h, w, H, W);
-    else
-      hipLaunchKernelGGL(pose_loss_fwd_kernel<0>, dim3(LOSS_NBLK, n), dim3(LOSS_BLOCK), 0, s, lg, cf, td, tm, pt, LOSS_NBLK, h, w, H, W);
-    int st = lf_launch_status();
-    if (st) return st;
-  }
-  hipLaunchKernelGGL(pose_loss_finish_kernel, dim3(N), dim3(64), 0, s, partial, LOSS_NBLK, weights, n, H * W, sums, losses, gsums);
-  return lf_launch_status();
+  return pose_loss_bwd(2, N, 1, N, depth_and_logits, coefs, target_depth, target_mask, gsums, gcrop, gcoefs, scratch,
+                       scratch_bytes, h, w, H, W, stream);
 }
 
 extern "C" int lf_pose_loss_fwd_mt(const float* logits, const float* coefs, const float* target_depth,
                                    const float* target_mask, const float* weights, float* sums, float* losses,
                                    float* gsums, void* scratch, size_t scratch_bytes,
                                    int N, int T, int n, int h, int w, int H, int W, void* stream) {
-  lf_clear_error();
-  if (!logits || !coefs || !target_depth || !target_mask || !weights || !sums || !losses || !gsums || !scratch)
-    return LF_EINVAL;
-  if (!pose_loss_mt_args_ok(N, T, n)) return LF_EINVAL;
-  return pose_loss_fwd_mt_launch(0, logits, coefs, target_depth, target_mask, weights, sums, losses, gsums, scratch,
-                                 scratch_bytes, N, T, n, h, w, H, W, stream);
+  return pose_loss_fwd(0, N, T, n, logits, coefs, target_depth, target_mask, weights, sums, losses,
+                       gsums, scratch, scratch_bytes, h, w, H, W, stream);
 }
 
 extern "C" int lf_pose_loss_fwd_masked_mt(const float* logits, const float* coefs, const float* target_depth,
                                           const float* target_mask, const float* weights, float* sums, float* losses,
                                           void* scratch, size_t scratch_bytes,
                                           int N, int T, int n, int h, int w, int H, int W, void* stream) {
-  lf_clear_error();
-  if (!logits || !coefs || !target_depth || !target_mask || !weights || !sums || !losses || !scratch) return LF_EINVAL;
-  if (!pose_loss_mt_args_ok(N, T, n)) return LF_EINVAL;
-  float* gs = (float*)scratch + (size_t)N * LOSS_NBLK * NSUM;      // (as lf_pose_loss_fwd_masked: gsums in the scratch tail)
-  return pose_loss_fwd_mt_launch(1, logits, coefs, target_depth, target_mask, weights, sums, losses, gs, scratch,
-                                 scratch_bytes, N, T, n, h, w, H, W, stream);
+  return pose_loss_fwd(1, N, T, n, logits, coefs, target_depth, target_mask, weights, sums, losses,
+                       nullptr, scratch, scratch_bytes, h, w, H, W, stream);
 }
 
 extern "C" int lf_pose_loss_bwd_mt(const float* logits, const float* coefs, const float* target_depth,
                                    const float* target_mask, const float* gsums, float* glogits, float* gcoefs,
                                    void* scratch, size_t scratch_bytes, int N, int T, int n, int h, int w, int H, int W,
                                    void* stream) {
-  lf_clear_error();
-  if (!logits || !coefs || !target_depth || !target_mask || !gsums || !glogits || !gcoefs || !scratch) return LF_EINVAL;
-  if (!pose_loss_mt_args_ok(N, T, n)) return LF_EINVAL;
-  if (N <= 0 || h <= 1 || w <= 1 || H <= 0 || W <= 0) return LF_EINVAL;
-  if (scratch_bytes < lf_pose_loss_scratch_bytes(N, h, w, H, W)) return LF_ENOSPC;
-  hipStream_t s = (hipStream_t)stream;
-  float* partial = (float*)scratch;
-  float* gd = partial + (size_t)N * LOSS_NBLK * NSUM;
-  float* gm = gd + (size_t)N * H * W;
-  float* Td = gm + (size_t)N * H * W;
-  float* Tm = Td + (size_t)N * H * w;
-  for (int t = 0; t < T; ++t) {
-    const long r0 = (long)t * n;
-    hipLaunchKernelGGL(pose_loss_bwd_pixels_kernel<0>, dim3(LOSS_NBLK, n), dim3(LOSS_BLOCK), 0, s, logits + r0 * h * w * 2,
-                       coefs + r0 * NOUT, target_depth + (long)t * H * W, target_mask + (long)t * H * W, gsums + r0 * NSUM,
-                       gd + r0 * H * W, gm + r0 * H * W, partial + r0 * LOSS_NBLK * NSUM, LOSS_NBLK, h, w, H, W);
-    int st = lf_launch_status();
-    if (st) return st;
-  }
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3(N), dim3(64), 0, s, partial, LOSS_NBLK, gcoefs, 6, NOUT, 18);
-  hipLaunchKernelGGL(pose_loss_bwd_rows_kernel, dim3((w + 255) / 256, H, N), dim3(256), 0, s, coefs, gd, gm, Td, Tm, w, H, W);
-  hipLaunchKernelGGL(pose_loss_bwd_cols_kernel<0>, dim3((w + 255) / 256, h, N), dim3(256), 0, s, logits, coefs, Td, Tm, glogits,
-                     h, w, H);
-  return lf_launch_status();
+  return pose_loss_bwd(0, N, T, n, logits, coefs, target_depth, target_mask, gsums, glogits, gcoefs,
+                       scratch, scratch_bytes, h, w, H, W, stream);
 }

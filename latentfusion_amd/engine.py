@@ -74,39 +74,46 @@ def camera_coefs(camera, cube_size, crop_h, crop_w):
                               int(crop_h), int(crop_w))
 
 
-def _pose_loss_fwd(lg, cf, tdepth, tmask, weights, H, W, masked=False, tn=None):
-    """THE launch of the fused pose loss of logits lg [N][h*w][2]: (losses (N,8), gsums, scratch).  tn = (T, n): rows grouped by
-    target against [T][H*W] frames (the _mt entry points); masked: the forward-only ranking form (no gsums are formed)."""
-    L = _lib.lib()
+_LOSS_FORMS = {'logits': '', 'masked': '_masked', 'depth': '_depth'}
+
+
+def _pose_loss_entry(direction, mode, tn):
+    """Name of the pose-loss entry point of a form ('logits' | 'masked' | 'depth') for one target frame (tn None) or for rows
+    grouped by target (tn = (T, n)).  (A form the library does not export fails where it is looked up.)"""
+    return 'lf_pose_loss_' + direction + _LOSS_FORMS[mode] + ('_mt' if tn is not None else '')
+
+
+def _pose_loss_scratch(lg, H, W):
     N, _, h, w = lg.shape
-    nbytes = L.lf_pose_loss_scratch_bytes(N, h, w, H, W)
-    scratch = torch.empty(nbytes // 4 + 1, device=lg.device, dtype=torch.float32)
-    sums = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
+    nbytes = _lib.lib().lf_pose_loss_scratch_bytes(N, h, w, H, W)
+    return torch.empty(nbytes // 4 + 1, device=lg.device, dtype=torch.float32)
+
+
+def _pose_loss_fwd(lg, cf, tdepth, tmask, weights, H, W, mode='logits', tn=None, sums=None):
+    """THE launch of the fused pose loss of lg [N][h*w][2]: (losses (N,8), gsums, scratch).  mode: 'logits' (head outputs),
+    'masked' (the forward-only ranking form: no gsums are formed) or 'depth' (metric depth crop + mask logit); tn = (T, n): rows
+    grouped by target against [T][H*W] frames (the _mt entry points); sums: an (N,8) buffer of the caller's to keep them."""
+    name = _pose_loss_entry('fwd', mode, tn)
+    N, _, h, w = lg.shape
+    scratch = _pose_loss_scratch(lg, H, W)
+    if sums is None:
+        sums = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
     losses = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
     gsums = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
-    a = (lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), weights.data_ptr(), sums.data_ptr(), losses.data_ptr())
-    b = (scratch.data_ptr(), scratch.numel() * 4, N) + (tn or ()) + (h, w, H, W, _s())
-    if masked and tn is None:
-        check(L.lf_pose_loss_fwd_masked(*a, *b), 'lf_pose_loss_fwd_masked')
-    elif masked:
-        check(L.lf_pose_loss_fwd_masked_mt(*a, *b), 'lf_pose_loss_fwd_masked_mt')
-    elif tn is None:
-        check(L.lf_pose_loss_fwd(*a, gsums.data_ptr(), *b), 'lf_pose_loss_fwd')
-    else:
-        check(L.lf_pose_loss_fwd_mt(*a, gsums.data_ptr(), *b), 'lf_pose_loss_fwd_mt')
+    out = () if mode == 'masked' else (gsums.data_ptr(),)
+    check(getattr(_lib.lib(), name)(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), weights.data_ptr(),
+                                    sums.data_ptr(), losses.data_ptr(), *out, scratch.data_ptr(), scratch.numel() * 4,
+                                    N, *(tn or ()), h, w, H, W, _s()), name)
     return losses, gsums, scratch
 
 
-def _pose_loss_bwd(lg, cf, tdepth, tmask, gsums, glogits, gcoefs, scratch, H, W, tn=None):
+def _pose_loss_bwd(lg, cf, tdepth, tmask, gsums, glogits, gcoefs, scratch, H, W, tn=None, mode='logits'):
     """THE launch of the loss backward: d/d(logits) and coefficient entries 18..23 (0..17 of gcoefs are not written)."""
-    L = _lib.lib()
+    name = _pose_loss_entry('bwd', mode, tn)
     N, _, h, w = lg.shape
-    a = (lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), gsums.data_ptr(), glogits.data_ptr(), gcoefs.data_ptr(),
-         scratch.data_ptr(), scratch.numel() * 4, N) + (tn or ()) + (h, w, H, W, _s())
-    if tn is None:
-        check(L.lf_pose_loss_bwd(*a), 'lf_pose_loss_bwd')
-    else:
-        check(L.lf_pose_loss_bwd_mt(*a), 'lf_pose_loss_bwd_mt')
+    check(getattr(_lib.lib(), name)(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), gsums.data_ptr(),
+                                    glogits.data_ptr(), gcoefs.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
+                                    N, *(tn or ()), h, w, H, W, _s()), name)
 
 
 class _PoseLoss(torch.autograd.Function):
@@ -1026,7 +1033,7 @@ class RenderLoopEngine:
     #      (engine_multi.MultiTargetEngine replaces them with their several-target forms) ----
     def _loss_fwd(self, lg, coefs, masked_depth):
         """Fused pose loss of the logits lg [n][h*w][2] against the target frame: (losses, gsums, scratch)."""
-        return _pose_loss_fwd(lg, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W, masked_depth)
+        return _pose_loss_fwd(lg, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W, 'masked' if masked_depth else 'logits')
 
     def _loss_bwd(self, lg, coefs, gsums, glogits, g_cf, scratch):
         """d/d(logits) and coefficient entries 18..23 of the loss formed by _loss_fwd."""

@@ -171,7 +171,8 @@ class MultiTargetEngine(RenderLoopEngine):
 
     # ---- the per-target pieces ----
     def _loss_fwd(self, lg, coefs, masked_depth):
-        return _pose_loss_fwd(lg, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W, masked_depth, (self.T, self._n))
+        return _pose_loss_fwd(lg, coefs, self.tdepth, self.tmask, self.weights, self.H, self.W, 'masked' if masked_depth else 'logits',
+                              (self.T, self._n))
 
     def _loss_bwd(self, lg, coefs, gsums, glogits, g_cf, scratch):
         _pose_loss_bwd(lg, coefs, self.tdepth, self.tmask, gsums, glogits, g_cf, scratch, self.H, self.W, (self.T, self._n))

@@ -515,14 +515,13 @@ class GradientPoseEstimator(PoseEstimator):
         camera = self._sync_cameras_from_rank0(camera)
         ranking = []
         stats, history = self._optimize_camera(z_obj, target_obs, camera, iters=self.num_iters, ranking=ranking)
-        best = Camera.cat([c for c, _, _ in ranking])
-        if self.track_stats and self.return_camera_history:
-            return best, stats, history
-        if self.track_stats:
-            return best, stats
-        if self.return_camera_history:
-            return best, history
-        return best
+        return self._result(ranking, stats, history)
+
+    def _result(self, ranking, stats, history):
+        """What estimate() returns for one target: the ranked cameras, then stat_history / camera_history per the flags."""
+        out = (Camera.cat([c for c, _, _ in ranking]),) + ((stats,) if self.track_stats else ())
+        out += (history,) if self.return_camera_history else ()
+        return out if len(out) > 1 else out[0]
 
     # one iteration = render N samples + loss + backward to the camera parameters
     def loss_and_grad(self, z_obj, target_obs, cameras, step=0, z_target_latent=None):
@@ -570,32 +569,33 @@ class GradientPoseEstimator(PoseEstimator):
         st['shard'], st['template_full_cpu'] = shard, full_cpu
         return st
 
+    def _record(self, target_obs, ranking=None, template_cpu=None):
+        """The per-target part of a loop state: everything the bookkeeping of one target (_bookkeep) reads and writes.  `rows`:
+        the target's rows among those the loop reads back."""
+        return {'target': target_obs, 'target_q': target_obs.camera.quaternion, 'ranking': [] if ranking is None else ranking,
+                'converge_count': 0, 'stat_history': {}, 'camera_history': [], 'template_cpu': template_cpu, 'rows': slice(None)}
+
+    def _row_state(self, params):
+        """The per-row part of a loop state: one optimiser and one plateau scheduler over all rows of `params`."""
+        return {'params': params, 'opt': BatchedOptimizer(self.optimizer, params), 'step': 0,
+                'sched': _PlateauLR(len(params[0]), self.learning_rate, self.lr_reduce_patience, self.lr_reduce_threshold,
+                                    self.lr_reduce_factor)}
+
     def _start_local(self, z_obj, target_obs, cameras, ranking):
+        """The loop state of one target.  It is its own single record: the loop over T targets (_run_batch) keeps a list of T
+        records next to the shared per-row part, and reads a state without one as [state]."""
         engine = self._engine_for(z_obj, target_obs)
         if engine is not None:
             from ..engine import camera_params
             P = camera_params(cameras).detach().clone().contiguous()          # (N,10) master copy on the device
             P.requires_grad_(True)
             cam = cameras._like(log_quaternion=P[:, 0:3], translation=P[:, 3:6], viewport=P[:, 6:10])   # views of P
-            return {
-                'engine': engine, 'P': P, 'z_obj': z_obj, 'target': target_obs, 'cam': cam, 'params': [P],
-                'opt': BatchedOptimizer(self.optimizer, [P]),
-                'sched': _PlateauLR(len(cameras), self.learning_rate, self.lr_reduce_patience,
-                                    self.lr_reduce_threshold, self.lr_reduce_factor),
-                'ranking': [] if ranking is None else ranking, 'step': 0, 'converge_count': 0,
-                'stat_history': {}, 'camera_history': [], 'target_q': target_obs.camera.quaternion,
-                'template_cpu': cameras.to('cpu'),
-            }
+            # group: the rows-per-target argument of the engine's forward_backward (none for the one-target engine)
+            return {**self._record(target_obs, ranking, cameras.to('cpu')), **self._row_state([P]),
+                    'engine': engine, 'P': P, 'z_obj': z_obj, 'cam': cam, 'group': ()}
         cam = pu.parameterize_camera(cameras, optimize_viewport=True)     # batched leaves (N,3),(N,3),(N,4)
-        params = [cam.log_quaternion, cam.translation, cam.viewport]
-        return {
-            'z_obj': z_obj, 'target': target_obs, 'cam': cam, 'params': params,
-            'opt': BatchedOptimizer(self.optimizer, params),
-            'sched': _PlateauLR(len(cameras), self.learning_rate, self.lr_reduce_patience, self.lr_reduce_threshold,
-                                self.lr_reduce_factor),
-            'ranking': [] if ranking is None else ranking, 'step': 0, 'converge_count': 0,
-            'stat_history': {}, 'camera_history': [], 'target_q': target_obs.camera.quaternion,
-        }
+        return {**self._record(target_obs, ranking), **self._row_state([cam.log_quaternion, cam.translation, cam.viewport]),
+                'z_obj': z_obj, 'cam': cam}
 
     def iterate(self, st):
         """One pose-optimisation iteration: render the N samples, loss, backward to the camera
@@ -614,40 +614,49 @@ class GradientPoseEstimator(PoseEstimator):
         loss_dict, optim_loss, rank_loss, optim_weights = self.loss_and_grad(st['z_obj'], target_obs, cam, step,
                                                                            z_target_latent)
         shard = st.get('shard')
-        if shard is not None:
+        detached = cam.uncrop().detach().clone()
+        if shard is not None:                                        # the ranking sees all ranks' rows, the statistics this rank's
             from .. import parallel
             rows = torch.cat((rank_loss.unsqueeze(1), cam.log_quaternion.detach(), cam.translation.detach()), dim=1)
-            rows = parallel.gather_rows(rows.contiguous(), shard[2]).cpu()
-            rank_all = rows[:, 0].tolist()                            # the one D2H sync per iteration
-            rank_host = rank_all[shard[0]:shard[1]]
-            detached_all = st['template_full_cpu']._like(log_quaternion=rows[:, 1:4].clone(), translation=rows[:, 4:7].clone(),
-                                                         viewport=None)
-            if self.return_camera_history:
-                st['camera_history'].append((rows[:, 0].clone(), detached_all))
-            delta = self._track_best_items(st['ranking'], step, list(detached_all), rank_all)
-            detached = cam.uncrop().detach().clone()
+            rows = parallel.gather_rows(rows.contiguous(), shard[2]).cpu()     # the one D2H sync per iteration
+            rank_cpu = rows[:, 0]
+            rank_host = rank_cpu[shard[0]:shard[1]].tolist()
+            ranked = st['template_full_cpu']._like(log_quaternion=rows[:, 1:4].clone(), translation=rows[:, 4:7].clone(),
+                                                   viewport=None)
         else:
-            rank_host = rank_loss.tolist()                            # the one D2H sync per iteration
-            detached = cam.uncrop().detach().clone()
-            if self.return_camera_history:
-                st['camera_history'].append((rank_loss.cpu(), detached.to('cpu')))
-            delta = self._track_best_items(st['ranking'], step, list(detached.to('cpu')), rank_host)
-        if self.track_stats:
-            angle = three.quaternion.angular_distance(detached.quaternion, st['target_q']).squeeze()
-            trans = torch.norm(detached.translation - target_obs.camera.translation, dim=1).squeeze()
-            self._record_stat_dict(st['stat_history'], {
-                **{f'{k}_loss': v.detach().cpu() for k, v in loss_dict.items()},
-                **{f'{k}_weight': v for k, v in optim_weights.items()},
-                'delta': delta, 'converge_count': st['converge_count'], 'angle_dist': angle.cpu(),
-                'trans_dist': trans.cpu(), 'optim_loss': optim_loss.cpu(), 'rank_loss': rank_loss.cpu()})
+            rank_cpu = rank_loss.cpu()                                # the one D2H sync per iteration
+            rank_host = rank_cpu.tolist()
+            ranked = detached.to('cpu')
+        converged = self._bookkeep(st, step, rank_cpu, ranked, optim_weights, {k: v.detach() for k, v in loss_dict.items()},
+                                   optim_loss, stat_rows=(rank_loss, detached))
         st['opt'].step(st['sched'].lr)
         st['sched'].step(rank_host)
-        if delta < self.converge_threshold:
-            st['converge_count'] += 1
-        elif delta > self.converge_threshold:
-            st['converge_count'] = 0
         st['step'] += 1
-        return st['converge_count'] >= self.converge_patience
+        return converged
+
+    def _bookkeep(self, rec, step, rank, cams, weights, comp=None, optim_loss=None, stat_rows=None):
+        """The host bookkeeping of ONE target after iteration `step`, on its record `rec`: ranking, camera history, statistics
+        and the convergence counter, from the target's host rows -- rank loss (n,), cameras (n) and, read under track_stats
+        only, loss components {name: (n,)} and optimised loss (n,) -- and the iteration's loss weights.  stat_rows = (rank,
+        cams): the rows of the statistics where they are not the ranked ones (the module path ranks host copies, of all ranks'
+        rows when sharded).  Returns whether the target has converged."""
+        if self.return_camera_history:
+            rec['camera_history'].append((rank.clone(), cams))
+        delta = self._track_best_items(rec['ranking'], step, list(cams), rank.tolist())
+        if self.track_stats:
+            rank, sc = (rank, cams) if stat_rows is None else stat_rows
+            dev = sc.translation.device
+            angle = three.quaternion.angular_distance(sc.quaternion, rec['target_q'].to(dev)).squeeze()
+            trans = torch.norm(sc.translation - rec['target'].camera.translation.to(dev), dim=1).squeeze()
+            self._record_stat_dict(rec['stat_history'], {
+                **{f'{k}_loss': v for k, v in comp.items()}, **{f'{k}_weight': v for k, v in weights.items()},
+                'delta': delta, 'converge_count': rec['converge_count'], 'angle_dist': angle, 'trans_dist': trans,
+                'optim_loss': optim_loss, 'rank_loss': rank})
+        if delta < self.converge_threshold:
+            rec['converge_count'] += 1
+        elif delta > self.converge_threshold:
+            rec['converge_count'] = 0
+        return rec['converge_count'] >= self.converge_patience
 
     def _engine_weights(self, st, step):
         optim_weights = copy.copy(self.loss_weights)
@@ -657,19 +666,24 @@ class GradientPoseEstimator(PoseEstimator):
         return optim_weights
 
     def _engine_launch(self, st, step):
-        """Enqueues forward + backward of iteration `step` and the asynchronous read-back of its losses and
-        parameters (pinned buffer + event); nothing here waits for the GPU."""
-        eng, P = st['engine'], st['P']
+        """Enqueues forward + backward of iteration `step` over all rows of the state and the asynchronous read-back of their
+        losses and parameters (pinned buffer + event); nothing here waits for the GPU."""
+        eng, P, recs = st['engine'], st['P'], st.get('records', (st,))
         optim_weights = self._engine_weights(st, step)
         with torch.no_grad():
             z_target_latent = None
             if optim_weights.get('latent', 0.0) != 0.0 or self.loss_weights.get('latent', 0.0) != 0.0:
-                # the target's latent code under every hypothesis (reference :606-608): encoder + renderer, no gradient
-                z_target_latent = self.model.compute_latent_code(st['target'], st['cam'])
-            if self.engine_graph and z_target_latent is None and not self.loss_schedules and hasattr(eng, 'forward_backward_graph'):
+                # each target's latent code under its own hypotheses (reference :606-608): encoder + renderer, no gradient
+                codes = [self.model.compute_latent_code(r['target'], r['cam']) for r in recs]
+                z_target_latent = codes[0] if len(codes) == 1 else torch.cat(
+                    [z.expand(len(r['cam']), *z.shape[1:]) if z.shape[0] == 1 else z for z, r in zip(codes, recs)])
+            # (the graph replay is the one-target engine's: MultiTargetEngine has the method only to refuse it)
+            if (self.engine_graph and z_target_latent is None and not self.loss_schedules and not st['group']
+                    and hasattr(eng, 'forward_backward_graph')):
                 losses, gparams = eng.forward_backward_graph(st['cam'], P)
             else:
-                losses, gparams = eng.forward_backward(st['cam'], need_grad=True, z_target_latent=z_target_latent, params=P)
+                losses, gparams = eng.forward_backward(st['cam'], *st['group'], need_grad=True, z_target_latent=z_target_latent,
+                                                       params=P)
             dev = torch.cat((losses[:, :6], P.detach()), dim=1)
             if st.get('shard') is not None:                           # (N_local,15) -> (N,15) over the ranks
                 from .. import parallel
@@ -684,13 +698,13 @@ class GradientPoseEstimator(PoseEstimator):
         return {'step': step, 'gparams': gparams, 'host': slot[key], 'event': ev, 'weights': optim_weights}
 
     def _iterate_engine(self, st):
-        """Same iteration on the fused engine, software-pipelined against the host: the optimiser step of
-        iteration t needs only the learning rates decided after t-1, so it and the whole forward/backward of
-        t+1 are enqueued BEFORE the host waits for iteration t's losses (ranking, plateau scheduler,
-        convergence test).  Every quantity is computed exactly as in the sequential order; if the loop stops
-        at t the already-enqueued forward/backward of t+1 is simply never read.  ONE device->host transfer
-        (losses + parameters) per iteration."""
-        eng, P, step, target_obs = st['engine'], st['P'], st['step'], st['target']
+        """Same iteration on the fused engine over the T records of a state (one target: the state itself), software-pipelined
+        against the host: the optimiser step of iteration t needs only the learning rates decided after t-1, so it and the
+        whole forward/backward of t+1 are enqueued BEFORE the host waits for iteration t's losses (ranking, plateau
+        scheduler, convergence test).  Every quantity is computed exactly as in the sequential order; if the loop stops at t
+        the already-enqueued forward/backward of t+1 is simply never read.  ONE device->host transfer (losses + parameters)
+        per iteration, all targets.  Returns True when every target has converged."""
+        eng, P, step = st['engine'], st['P'], st['step']
         cur = st.pop('inflight', None)
         if cur is None or cur['step'] != step:
             cur = self._engine_launch(st, step)
@@ -700,32 +714,27 @@ class GradientPoseEstimator(PoseEstimator):
             st['inflight'] = self._engine_launch(st, step + 1)        # keeps the GPU busy while the host ranks
         cur['event'].synchronize()                                    # the one D2H sync per iteration
         host = cur['host'].clone()
-        optim_weights = cur['weights']
         comp = {k: host[:, i] for i, k in enumerate(eng.LOSS_KEYS)}
         if self.loss_weights.get('latent', 0.0) != 0.0 or 'latent' in self.loss_schedules:
             comp['latent'] = host[:, 5]
         rank = sum(self.loss_weights.get(k, 0.0) * v for k, v in comp.items())
+        shard = st.get('shard')                                       # (sharded: the records see all N gathered rows)
+        converged = True
+        for rec in st.get('records', (st,)):
+            if not rec.get('done'):
+                r = rec['rows']
+                tpl = rec['template_cpu'] if shard is None else st['template_full_cpu']
+                cams = tpl._like(log_quaternion=host[r, 6:9].clone(), translation=host[r, 9:12].clone(), viewport=None)
+                stats = {'comp': {k: v[r] for k, v in comp.items()}, 'optim_loss': host[r, 4]} if self.track_stats else {}
+                done = self._bookkeep(rec, step, rank[r], cams, cur['weights'], **stats)
+                if st.get('freeze'):                                  # (_run_batch: a converged target's record stops growing)
+                    rec['done'] = done
+                converged = converged and done
+        # (a frozen target's rows keep their own plateau state and parameters: nothing it returns reads them again)
         rank_host = rank.tolist()
-        shard = st.get('shard')
-        tpl = st['template_cpu'] if shard is None else st['template_full_cpu']
-        detached = tpl._like(log_quaternion=host[:, 6:9].clone(), translation=host[:, 9:12].clone(), viewport=None)
-        if self.return_camera_history:
-            st['camera_history'].append((rank.clone(), detached))
-        delta = self._track_best_items(st['ranking'], step, list(detached), rank_host)
-        if self.track_stats:
-            angle = three.quaternion.angular_distance(detached.quaternion, st['target_q'].cpu()).squeeze()
-            trans = torch.norm(detached.translation - target_obs.camera.translation.cpu(), dim=1).squeeze()
-            self._record_stat_dict(st['stat_history'], {
-                **{f'{k}_loss': v for k, v in comp.items()}, **{f'{k}_weight': v for k, v in optim_weights.items()},
-                'delta': delta, 'converge_count': st['converge_count'], 'angle_dist': angle, 'trans_dist': trans,
-                'optim_loss': host[:, 4].clone(), 'rank_loss': rank.clone()})
         st['sched'].step(rank_host if shard is None else rank_host[shard[0]:shard[1]])
-        if delta < self.converge_threshold:
-            st['converge_count'] += 1
-        elif delta > self.converge_threshold:
-            st['converge_count'] = 0
         st['step'] += 1
-        return st['converge_count'] >= self.converge_patience
+        return converged
 
     def _optimize_camera(self, z_obj, target_obs, cameras, iters, ranking):
         st = self.start(z_obj, target_obs, cameras, ranking)
@@ -837,93 +846,21 @@ class GradientPoseEstimator(PoseEstimator):
             return False
         return all(k in RenderLoopEngine.LOSS_KEYS + ('latent',) for k in self.loss_schedules)
 
-    def _batch_launch(self, st, step):
-        """_engine_launch for the batched loop: forward + backward of all targets' rows of iteration `step` and the
-        asynchronous read-back of their losses and parameters."""
-        eng, P, n = st['engine'], st['P'], st['n']
-        optim_weights = self._engine_weights(st, step)
-        with torch.no_grad():
-            zt = None
-            if optim_weights.get('latent', 0.0) != 0.0 or self.loss_weights.get('latent', 0.0) != 0.0:
-                # each target's latent code under its own hypotheses (the single-target loop's call, per target)
-                codes = [self.model.compute_latent_code(tg, c) for tg, c in zip(st['targets'], st['cam_t'])]
-                zt = torch.cat([z.expand(n, *z.shape[1:]) if z.shape[0] == 1 else z for z in codes])
-            losses, gparams = eng.forward_backward(st['cam'], n, need_grad=True, z_target_latent=zt, params=P)
-            dev = torch.cat((losses[:, :6], P.detach()), dim=1)
-        slot = st.setdefault('pinned', {})
-        key = step & 1
-        if key not in slot or slot[key].shape != dev.shape:
-            slot[key] = torch.empty(dev.shape, dtype=dev.dtype, pin_memory=True)
-        slot[key].copy_(dev, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        return {'step': step, 'gparams': gparams, 'host': slot[key], 'event': ev, 'weights': optim_weights}
-
     def _run_batch(self, eng, targets, zoomed):
-        """The loop of _optimize_camera / _iterate_engine over T targets at once (one D2H transfer per iteration, the next
-        iteration enqueued before the host ranks this one); returns the per-target results of estimate()."""
+        """The loop of _optimize_camera over T targets at once: the iteration of iterate() (_iterate_engine) on a state with T
+        records, which freezes a target once it has converged; returns the per-target results of estimate()."""
         from ..engine import camera_params
         T, n = len(targets), len(zoomed[0])
         P = torch.cat([camera_params(c) for c in zoomed]).detach().clone().contiguous()
         P.requires_grad_(True)
         cam = Camera.cat(zoomed)._like(log_quaternion=P[:, 0:3], translation=P[:, 3:6], viewport=P[:, 6:10])
-        st = {'engine': eng, 'P': P, 'n': n, 'cam': cam, 'targets': targets,
-              'cam_t': [cam[t * n:(t + 1) * n] for t in range(T)]}
-        opt = BatchedOptimizer(self.optimizer, [P])
-        sched = _PlateauLR(T * n, self.learning_rate, self.lr_reduce_patience, self.lr_reduce_threshold, self.lr_reduce_factor)
-        per = [{'ranking': [], 'converge_count': 0, 'stat_history': {}, 'camera_history': [], 'done': False,
-                'template_cpu': zoomed[t].to('cpu'), 'target_q': targets[t].camera.quaternion} for t in range(T)]
-        inflight = None
-        for step in range(self.num_iters):
-            cur = inflight if inflight is not None else self._batch_launch(st, step)
-            P.grad = cur['gparams']
-            opt.step(sched.lr)                                        # lr after scheduler.step(loss[t-1])
-            inflight = self._batch_launch(st, step + 1) if step + 1 < self.num_iters else None
-            cur['event'].synchronize()                                # the one D2H sync per iteration, all targets
-            host = cur['host'].clone()
-            optim_weights = cur['weights']
-            comp = {k: host[:, i] for i, k in enumerate(eng.LOSS_KEYS)}
-            if self.loss_weights.get('latent', 0.0) != 0.0 or 'latent' in self.loss_schedules:
-                comp['latent'] = host[:, 5]
-            rank = sum(self.loss_weights.get(k, 0.0) * v for k, v in comp.items())
-            for t, pt in enumerate(per):
-                if pt['done']:
-                    continue
-                r = slice(t * n, (t + 1) * n)
-                rank_t = rank[r]
-                detached = pt['template_cpu']._like(log_quaternion=host[r, 6:9].clone(), translation=host[r, 9:12].clone(),
-                                                    viewport=None)
-                if self.return_camera_history:
-                    pt['camera_history'].append((rank_t.clone(), detached))
-                delta = self._track_best_items(pt['ranking'], step, list(detached), rank_t.tolist())
-                if self.track_stats:
-                    angle = three.quaternion.angular_distance(detached.quaternion, pt['target_q'].cpu()).squeeze()
-                    trans = torch.norm(detached.translation - targets[t].camera.translation.cpu(), dim=1).squeeze()
-                    self._record_stat_dict(pt['stat_history'], {
-                        **{f'{k}_loss': v[r] for k, v in comp.items()}, **{f'{k}_weight': v for k, v in optim_weights.items()},
-                        'delta': delta, 'converge_count': pt['converge_count'], 'angle_dist': angle, 'trans_dist': trans,
-                        'optim_loss': host[r, 4].clone(), 'rank_loss': rank_t.clone()})
-                if delta < self.converge_threshold:
-                    pt['converge_count'] += 1
-                elif delta > self.converge_threshold:
-                    pt['converge_count'] = 0
-                pt['done'] = pt['converge_count'] >= self.converge_patience
-            # (a frozen target's rows keep their own plateau state and parameters: nothing it returns reads them again)
-            sched.step(rank.tolist())
-            if all(pt['done'] for pt in per):
+        rows = [slice(t * n, (t + 1) * n) for t in range(T)]
+        st = {**self._row_state([P]), 'engine': eng, 'P': P, 'cam': cam, 'group': (n,), 'max_steps': self.num_iters, 'freeze': True,
+              'records': [{**self._record(tg, None, c.to('cpu')), 'cam': cam[r], 'rows': r} for tg, c, r in zip(targets, zoomed, rows)]}
+        for _ in range(self.num_iters):
+            if self._iterate_engine(st):
                 break
-        out = []
-        for pt in per:
-            best = Camera.cat([c for c, _, _ in pt['ranking']])
-            if self.track_stats and self.return_camera_history:
-                out.append((best, pt['stat_history'], pt['camera_history']))
-            elif self.track_stats:
-                out.append((best, pt['stat_history']))
-            elif self.return_camera_history:
-                out.append((best, pt['camera_history']))
-            else:
-                out.append(best)
-        return out
+        return [self._result(rec['ranking'], rec['stat_history'], rec['camera_history']) for rec in st['records']]
 
     @classmethod
     def _record_stat(cls, history, key, value):

@@ -31,33 +31,24 @@ class _PoseLossTerms(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, crop, coefs, tdepth, tmask, H, W):
-        from .. import _lib, ops
-        L = _lib.lib()
+        from .. import ops
+        from ..engine import _pose_loss_fwd
         lg = ops.cl(crop)                                          # channels-last == [N][h*w][2]
-        n, _, h, w = lg.shape
-        nbytes = L.lf_pose_loss_scratch_bytes(n, h, w, H, W)
-        scratch = torch.empty(nbytes // 4 + 1, device=lg.device, dtype=torch.float32)
-        sums = torch.empty(n, 8, device=lg.device, dtype=torch.float32)
-        losses = torch.empty(n, 8, device=lg.device, dtype=torch.float32)
-        gsums = torch.empty(n, 8, device=lg.device, dtype=torch.float32)
+        sums = torch.empty(lg.shape[0], 8, device=lg.device, dtype=torch.float32)
         ones = torch.ones(4, device=lg.device, dtype=torch.float32)
         cf = coefs.detach().contiguous()
         with ops._timed('pose_loss_terms'):
-            _lib.check(L.lf_pose_loss_fwd_depth(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), ones.data_ptr(),
-                                                sums.data_ptr(), losses.data_ptr(), gsums.data_ptr(), scratch.data_ptr(),
-                                                scratch.numel() * 4, n, h, w, H, W, torch.cuda.current_stream().cuda_stream),
-                       'lf_pose_loss_fwd_depth')
+            losses, _, _ = _pose_loss_fwd(lg, cf, tdepth, tmask, ones, H, W, 'depth', sums=sums)
         ctx.save_for_backward(lg, cf, tdepth, tmask, sums)
-        ctx.dims = (n, h, w, H, W)
+        ctx.dims = (H, W)
         ctx.set_materialize_grads(False)
         return losses[:, 0].clone(), losses[:, 1].clone(), losses[:, 2].clone(), losses[:, 3].clone()
 
     @staticmethod
     def backward(ctx, g_depth, g_ov, g_iou, g_mask):
-        from .. import _lib
-        L = _lib.lib()
+        from ..engine import _pose_loss_bwd, _pose_loss_scratch
         lg, cf, tdepth, tmask, S = ctx.saved_tensors
-        n, h, w, H, W = ctx.dims
+        (H, W), n = ctx.dims, lg.shape[0]
         z = torch.zeros(n, device=lg.device, dtype=torch.float32)
         g_depth, g_ov, g_iou, g_mask = (z if g is None else g.float() for g in (g_depth, g_ov, g_iou, g_mask))
         # d(terms)/d(sums), the algebra of pose_loss_finish_kernel with the incoming per-sample gradients as weights
@@ -71,13 +62,9 @@ class _PoseLossTerms(torch.autograd.Function):
                           g_iou * d_uni,
                           g_iou * (-d_uni - torch.where(S[:, 4] > 1e-4, 1.0 / S[:, 4], torch.zeros_like(uni))),
                           z, g_mask * inv_hw, z), dim=1).contiguous()
-        nbytes = L.lf_pose_loss_scratch_bytes(n, h, w, H, W)
-        scratch = torch.empty(nbytes // 4 + 1, device=lg.device, dtype=torch.float32)
         gcrop = torch.empty_like(lg)
         gcoefs = torch.zeros(n, 24, device=lg.device, dtype=torch.float32)
-        _lib.check(L.lf_pose_loss_bwd_depth(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), gs.data_ptr(),
-                                            gcrop.data_ptr(), gcoefs.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
-                                            n, h, w, H, W, torch.cuda.current_stream().cuda_stream), 'lf_pose_loss_bwd_depth')
+        _pose_loss_bwd(lg, cf, tdepth, tmask, gs, gcrop, gcoefs, _pose_loss_scratch(lg, H, W), H, W, mode='depth')
         return gcrop, gcoefs, None, None, None, None
 
 

@@ -108,6 +108,16 @@ def test_estimate_batch_module_path_fallback_and_drawn_cameras():
         assert torch.equal(g.log_quaternion, w.log_quaternion) and torch.equal(g.translation, w.translation)
 
 
+def test_estimate_batch_of_one_target_equals_estimate():
+    """T = 1 through the batched driver: the same loop as estimate(), on MultiTargetEngine with one record."""
+    model, z_obj, targets, cams = _setup()
+    est = _estimator(model, num_iters=3)
+    want = est.estimate(z_obj, targets[0], camera=cams[0].clone())
+    got = est.estimate_batch(z_obj, targets[:1], cameras=[cams[0].clone()])
+    assert est.last_batch_groups == [1] and len(got) == 1
+    _assert_same(got[0], want)
+
+
 def test_estimate_batch_refuses_sharding():
     model, z_obj, targets, cams = _setup()
     est = _estimator(model, shard_hypotheses=True)
