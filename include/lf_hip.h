@@ -793,6 +793,41 @@ size_t lf_points_pair_dist_scratch_bytes(int R, int P);
 int lf_points_pair_dist(const float* pts, long pts_sr, const float* A, const float* Bm, int rows, float* mean, void* scratch,
                         size_t scratch_bytes, int R, int P, void* stream);
 
+/* ---- initial pose from depth and mask (csrc/depth_init.hip) -------------------------------------------------------------------
+ * The translation the estimators start from, for B frames in one call (reference pose/initialization.py:8-86:
+ * _masks_to_viewports, _erode_mask, _reject_outliers_mad, _estimate_camera_dist, estimate_translation): the centre of the mask's
+ * bounding box and the mid-range of the MAD-filtered masked depth.
+ *   depth [B][H][W] fp32; mask [B][H][W], fp32 (mask_u8 = 0) or bytes (mask_u8 = 1), foreground iff != 0 (a NaN is foreground,
+ *   as under .bool()); intr [intr_n][4] = (fu, fv, u0, v0), intr_n = 1 (shared) or B; intr and trans are both given or both
+ *   NULL (intr_n is then ignored).
+ * Per image b, all in fp32:
+ *   1. (xmin, ymin, xmax, ymax) = bounding box of the foreground of the UN-eroded mask, n_mask its pixel count,
+ *      cu = (xmax + xmin) / 2, cv = (ymax + ymin) / 2.
+ *   2. a pixel is valid iff it is foreground and depth > 0 (drops NaN, 0 and negatives, keeps +inf) and, with
+ *      erode_radius = r > 0, every tap (dx, dy), dx^2 + dy^2 <= r^2, that lies inside the frame is foreground (taps outside
+ *      count as foreground): the erosion the reference computes and, by its guard, discards -- r = 0 reproduces the reference.
+ *   3. median = the valid depth of rank (n_valid - 1) / 2 (the lower median, as torch.median).
+ *   4. mad = the value of the same rank among |d - median|; NaN when median is +inf (inf - inf is then among them).
+ *   5. d is kept iff |d - median| / mad < m: one division, one compare, so 0/0 and x/0 keep nothing.
+ *   6. z = (min_kept + max_kept) / 2.
+ *   7. trans[b] = ((cu - u0) / fu * z, (cv - v0) / fv * z, z): a division, then a multiplication.
+ *   stats[b][8]  = (z, median, mad, min_kept, max_kept, cu, cv, 0)
+ *   counts[b][8] = (n_mask, n_valid, n_kept, xmin, ymin, xmax, ymax, 0)
+ * Degenerate images are reported, never a fault: n_mask = 0 gives the box (-1, -1, -1, -1) and cu = cv = NaN; n_valid = 0
+ * gives median = mad = NaN; n_kept = 0 gives z = min_kept = max_kept = trans[b] = NaN.  Subnormal depths are outside the
+ * contract.  A memset and two launches whatever B is: a compaction pass (bounding box and valid depths into scratch, integer
+ * atomics only) and one workgroup per image that finds both medians by an 8-bit-digit radix select on the bit patterns.  Every
+ * output is an order statistic, a minimum / maximum, a count or one correctly rounded operation on those: the bits depend on
+ * the image alone, not on B, the run or the order in which the atomics arrive.
+ * Domain: B, H, W >= 1, B * H * W < 2^31, 0 <= erode_radius <= 8, m > 0 (a NaN m is refused), mask_u8 in {0, 1}, intr_n in
+ * {1, B}, required pointers not NULL (else LF_EINVAL); every pointer 4-byte aligned and scratch 8-byte aligned (LF_EALIGN);
+ * fewer than lf_depth_init_scratch_bytes(B, H, W) bytes of scratch is LF_ENOSPC (the query returns 0 outside the domain).
+ * Nothing is launched or written in any of these cases. */
+size_t lf_depth_init_scratch_bytes(int B, int H, int W);
+int lf_depth_init(const float* depth, const void* mask, int mask_u8, const float* intr, int intr_n, float m, int erode_radius,
+                  float* trans, float* stats, int* counts, void* scratch, size_t scratch_bytes, int B, int H, int W,
+                  void* stream);
+
 /* Block-end rescale by exactly x2 (up = 1) or x0.5 (up = 0): nearest (linear = 0) or bi-/tri-linear
  * with align_corners=False (linear = 1) = Interpolate / F.interpolate(scale_factor=...) of
  * modules/__init__.py:18-36, blocks.py:160-162.  x: [N][D][H][W][C] (D = 1 for dims = 2); the output

@@ -141,14 +141,15 @@ class Observation:
                             for i in inds], dim=0)
         return cls(color, depth, mask, cameras, **meta)
 
-    def estimate_camera(self) -> Camera:
-        """Camera with the translation estimated from depth + mask (reference :284-287)."""
+    def estimate_camera(self, kernel=None, erode_radius=0) -> Camera:
+        """Camera with the translation estimated from depth + mask (reference :284-287).  kernel, erode_radius: as
+        pose.initialization.estimate_translation ('fused': one HIP call for all frames of the observation)."""
         from .pose.initialization import estimate_initial_pose
         return estimate_initial_pose(self.depth, self.mask, self.camera.intrinsic, self.camera.width,
-                                     self.camera.height).to(self.device)
+                                     self.camera.height, kernel=kernel, erode_radius=erode_radius).to(self.device)
 
-    def zoom_estimate(self, target_dist, target_size):
-        return self.zoom(target_dist, target_size, camera=self.estimate_camera())
+    def zoom_estimate(self, target_dist, target_size, kernel=None, erode_radius=0):
+        return self.zoom(target_dist, target_size, camera=self.estimate_camera(kernel=kernel, erode_radius=erode_radius))
 
     def uncrop(self, camera=None):
         camera = self.camera if camera is None else camera

@@ -1037,6 +1037,76 @@ def points_pair_dist(points, A, B):
     return mean
 
 
+def _frames_arg(t, name, dtypes):
+    """(B,1,H,W) or (B,H,W) device tensor of one of `dtypes` -> its (B,H,W) view, else ValueError."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f'{name} must be a device tensor: the HIP path has no CPU fallback')
+    if t.dtype not in dtypes:
+        raise ValueError(f'{name} must be one of {", ".join(str(d) for d in dtypes)}, got {t.dtype}')
+    if t.dim() not in (3, 4) or (t.dim() == 4 and t.shape[1] != 1) or t.numel() == 0:
+        raise ValueError(f'{name} must be shaped (B,1,H,W) or (B,H,W), got {tuple(t.shape)}')
+    return t[:, 0] if t.dim() == 4 else t
+
+
+def _aligned4(t):
+    """`t` contiguous and on a 4-byte boundary (a byte mask sliced at an odd offset is copied)."""
+    t = t.contiguous()
+    return t if t.device.type != 'cuda' or t.data_ptr() % 4 == 0 else t.clone()
+
+
+def depth_init(depth, mask, intrinsic=None, m=3.0, erode_radius=0):
+    """The estimators' initial translation for B frames in one call (lf_depth_init; pose/initialization.py): the centre of the
+    mask's bounding box and the mid-range of the MAD-filtered masked depth, bit for bit what _masks_to_viewports,
+    _reject_outliers_mad(m) and estimate_translation compute per frame on the host.  depth, mask: (B,1,H,W) or (B,H,W); depth
+    float32, mask float32, bool or uint8 (foreground iff != 0); intrinsic: None or (B or 1, 3, >= 3) float32.  erode_radius = r > 0
+    restricts the depths to the mask eroded by a disk of radius r (the frame's outside counts as foreground); the bounding box
+    stays the un-eroded mask's.  -> {'trans': (B,3), only with intrinsic; 'stats': (B,8) = (z, median, mad, min_kept, max_kept,
+    cu, cv, 0); 'counts': (B,8) int32 = (n_mask, n_valid, n_kept, xmin, ymin, xmax, ymax, 0)}.  Degenerate frames are reported
+    (n_mask / n_valid / n_kept = 0 with NaN in their stats and trans rows), not raised: nothing here synchronises."""
+    d3 = _frames_arg(depth, 'depth', (torch.float32,))
+    k3 = _frames_arg(mask, 'mask', (torch.float32, torch.bool, torch.uint8))
+    if tuple(d3.shape) != tuple(k3.shape):
+        raise ValueError(f'depth and mask differ in shape: {tuple(depth.shape)} and {tuple(mask.shape)}')
+    if k3.device != d3.device:
+        raise ValueError('depth and mask must be on one device')
+    B, H, W = d3.shape
+    if B * H * W >= 2 ** 31:
+        raise ValueError(f'{B} x {H} x {W} pixels: at most 2^31 - 1 per call')
+    if isinstance(m, bool) or not isinstance(m, (int, float)) or not m > 0:
+        raise ValueError(f'm must be a positive number, got {m!r}')
+    if isinstance(erode_radius, bool) or not isinstance(erode_radius, int) or not 0 <= erode_radius <= 8:
+        raise ValueError(f'erode_radius must be an integer in 0..8, got {erode_radius!r}')
+    if intrinsic is not None:
+        if not isinstance(intrinsic, torch.Tensor) or not intrinsic.is_cuda or intrinsic.device != d3.device:
+            raise ValueError('intrinsic must be a device tensor on the device of depth')
+        if intrinsic.dtype != torch.float32:
+            raise ValueError('intrinsic must be float32')
+        if intrinsic.dim() != 3 or intrinsic.shape[0] not in (1, B) or intrinsic.shape[1] != 3 or intrinsic.shape[2] < 3:
+            raise ValueError(f'intrinsic must be shaped ({B} or 1, 3, >= 3), got {tuple(intrinsic.shape)}')
+    L = _lib.lib()
+    dev = d3.device
+    d3 = _aligned4(d3)
+    u8 = k3.dtype != torch.float32
+    k3 = _aligned4(k3.view(torch.uint8) if k3.dtype == torch.bool else k3)
+    intr = trans = None
+    if intrinsic is not None:
+        intr = torch.stack((intrinsic[:, 0, 0], intrinsic[:, 1, 1], intrinsic[:, 0, 2], intrinsic[:, 1, 2]), dim=-1).contiguous()
+        trans = torch.empty(B, 3, device=dev, dtype=torch.float32)
+    stats = torch.empty(B, 8, device=dev, dtype=torch.float32)
+    counts = torch.empty(B, 8, device=dev, dtype=torch.int32)
+    nbytes = L.lf_depth_init_scratch_bytes(B, H, W)
+    scratch = torch.empty(nbytes // 4 + 4, device=dev, dtype=torch.float32)
+    with _timed('depth_init', f'{B}x{H}x{W}'):
+        check(L.lf_depth_init(_ptr(d3), _ptr(k3), int(u8), _ptr(intr) if intr is not None else None,
+                              intr.shape[0] if intr is not None else 1, float(m), erode_radius,
+                              _ptr(trans) if trans is not None else None, _ptr(stats), _ptr(counts), _ptr(scratch, True),
+                              scratch.numel() * 4, B, H, W, _stream()), 'lf_depth_init')
+    out = {'stats': stats, 'counts': counts}
+    if trans is not None:
+        out['trans'] = trans
+    return out
+
+
 def _wino_ok(x, weight):
     """The Winograd kernel serves 3-D 16 -> 16 convolutions on volumes of at least one 2x8x16 tile row."""
     return (x.dim() == 5 and tuple(weight.shape[:2]) == (16, 16) and x.shape[1] == 16

@@ -66,7 +66,7 @@ def load_schedules_from_config(config):
 class PoseEstimator:
     def __init__(self, *, model, ranking_size, loss_weights, loss_func=None, return_camera_history=False,
                  verbose=False, shard_hypotheses=False, use_engine=True, conv_mode='auto', fuse_projection=None,
-                 proj_kernel=None, latent_kernel=None):
+                 proj_kernel=None, latent_kernel=None, init_kernel='composed'):
         """shard_hypotheses (an addition; the reference is single-process): under torch.distributed every rank
         renders and scores only its contiguous slice of the pose hypotheses; the per-hypothesis rows (loss
         [+ camera parameters]) are all-gathered once per iteration (parallel.gather_rows) and every rank ranks the
@@ -85,6 +85,13 @@ class PoseEstimator:
         self.use_engine, self.conv_mode, self.fuse_projection = use_engine, conv_mode, fuse_projection
         self.proj_kernel = proj_kernel
         self.latent_kernel = latent_kernel
+        # init_kernel (an addition; also an [args] key of the TOML): what computes the initial pose the estimators draw their
+        # hypotheses around -- 'composed' (the host functions of pose/initialization.py, per target) or 'fused' (one
+        # ops.depth_init call for all targets of an estimate_batch, the same bits; needs a GPU and raises without one)
+        from .initialization import KERNELS as INIT_KERNELS
+        if init_kernel not in INIT_KERNELS:
+            raise ValueError(f'init_kernel {init_kernel!r}: one of {INIT_KERNELS}')
+        self.init_kernel = init_kernel
         self._engine_cache = None
         self.last_scored_on_engine = False
         self.shard_hypotheses = bool(shard_hypotheses)
@@ -105,6 +112,36 @@ class PoseEstimator:
         from . import initialization
         return initialization.estimate_initial_pose(target_obs.depth, target_obs.mask, target_obs.camera.intrinsic,
                                                     target_obs.camera.width, target_obs.camera.height)
+
+    def initial_pose_batch(self, targets, kernel=None):
+        """One initial Camera per target (each on its target's device).  kernel: 'composed' (initial_pose per target) /
+        'fused' (the T frames stacked, one estimate_initial_pose call on the HIP kernels: the same bits) / None = the
+        estimator's init_kernel."""
+        from . import initialization
+        kernel = initialization.select_kernel(self.init_kernel if kernel is None else kernel)
+        targets = list(targets)
+        if kernel == 'composed':
+            return [self.initial_pose(t) for t in targets]
+        if not targets:
+            return []
+        c0 = targets[0].camera
+        for i, t in enumerate(targets):
+            if tuple(t.depth.shape[1:]) != tuple(targets[0].depth.shape[1:]) or (t.camera.width, t.camera.height) != (c0.width, c0.height):
+                raise ValueError(f'target {i} differs from target 0 in frame size: one fused call takes frames of one size')
+        dev = c0.intrinsic.device
+        cams = initialization.estimate_initial_pose(torch.cat([t.depth.to(dev) for t in targets], dim=0),
+                                                    torch.cat([t.mask.to(dev) for t in targets], dim=0),
+                                                    torch.cat([t.camera.intrinsic.to(dev) for t in targets], dim=0),
+                                                    c0.width, c0.height, kernel='fused')
+        out, at = [], 0
+        for t in targets:
+            out.append(cams[at:at + len(t)].to(t.camera.intrinsic.device))
+            at += len(t)
+        return out
+
+    def _initial_pose(self, target_obs):
+        """initial_pose under the estimator's init_kernel."""
+        return self.initial_pose(target_obs) if self.init_kernel == 'composed' else self.initial_pose_batch([target_obs])[0]
 
     def estimate(self, z_obj, target_obs, **kwargs):
         if len(target_obs) > 1:
@@ -228,7 +265,7 @@ class MetropolisPoseEstimator(PoseEstimator):
             camera_init = camera = kwargs['cameras']
             camera = camera.to(self.device)
         else:
-            camera_init = kwargs['camera'] if 'camera' in kwargs else self.initial_pose(target_obs)
+            camera_init = kwargs['camera'] if 'camera' in kwargs else self._initial_pose(target_obs)
             camera = pu.sample_cameras_with_estimate(self.num_samples, camera_init).to(self.device)
         error = torch.full((len(camera),), 100.0, device=self.device)
         temp_weight = 1.0 / camera_init.translation[:, -1].mean().item()
@@ -281,7 +318,7 @@ class CrossEntropyPoseEstimator(PoseEstimator):
         if kwargs.get('cameras', None):
             cameras, camera_init = kwargs['cameras'], kwargs['cameras'][0]
         else:
-            camera_init = kwargs['camera'] if 'camera' in kwargs else self.initial_pose(target_obs)
+            camera_init = kwargs['camera'] if 'camera' in kwargs else self._initial_pose(target_obs)
             cameras = pu.sample_cameras_with_estimate(n=self.num_gmm_components * self.num_samples,
                                                       camera_est=camera_init, upright=self.init_upright,
                                                       hemisphere=self.init_hemisphere)
@@ -509,7 +546,7 @@ class GradientPoseEstimator(PoseEstimator):
         if 'camera' in kwargs:
             camera = kwargs['camera']
         else:
-            camera = pu.sample_cameras_with_estimate(n=self.num_samples, camera_est=self.initial_pose(target_obs))
+            camera = pu.sample_cameras_with_estimate(n=self.num_samples, camera_est=self._initial_pose(target_obs))
         target_obs = target_obs.to(self.device)
         camera = camera.zoom(None, self.model.input_size, self.model.camera_dist).to(self.device)
         camera = self._sync_cameras_from_rank0(camera)
@@ -797,7 +834,7 @@ class GradientPoseEstimator(PoseEstimator):
         if self.shard_hypotheses:
             raise NotImplementedError('estimate_batch does not shard hypotheses over ranks')
         if cameras is None:
-            cameras = [pu.sample_cameras_with_estimate(n=self.num_samples, camera_est=self.initial_pose(t)) for t in targets]
+            cameras = [pu.sample_cameras_with_estimate(n=self.num_samples, camera_est=c) for c in self.initial_pose_batch(targets)]
         if not self._multi_engine_applies(z_obj if z_of is None else z_of[0]):     # (the volumes agree in device)
             self.last_batch_groups = [1] * len(targets)
             return [self.estimate(z_obj if z_of is None else z_of[i], t, camera=c)

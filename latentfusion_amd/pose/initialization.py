@@ -65,7 +65,58 @@ def _estimate_camera_dist(depth, mask):
     return zs
 
 
-def estimate_translation(depth, mask, intrinsic):
+KERNELS = ('composed', 'fused')
+KERNEL = 'composed'        # what estimate_translation / estimate_initial_pose run when kernel is None: 'composed' (the host functions
+#                            above, per frame, as the reference) or 'fused' (one ops.depth_init call for the whole batch, the same bits)
+
+
+def select_kernel(kernel):
+    """Resolved `kernel` of estimate_translation: None -> the module switch KERNEL; anything but KERNELS is refused."""
+    kernel = KERNEL if kernel is None else kernel
+    if kernel not in KERNELS:
+        raise ValueError(f'kernel {kernel!r}: one of {KERNELS}')
+    return kernel
+
+
+def _compute_device(*tensors):
+    """Where the fused path runs: the device of the first device-resident input, else the current GPU.  No GPU: an error."""
+    for t in tensors:
+        if t.is_cuda:
+            return t.device
+    if not torch.cuda.is_available():
+        raise RuntimeError("kernel 'fused' needs a GPU: the initial pose's HIP kernels have no CPU form (use kernel='composed')")
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _translation_fused(depth, mask, intrinsic, erode_radius, check):
+    """(B,3) translation on intrinsic's device from one ops.depth_init call; check: one copy of the counts to the host."""
+    from .. import ops
+    if intrinsic.dim() != 3:
+        raise ValueError(f'intrinsic must be shaped (B or 1, 3, 3), got {tuple(intrinsic.shape)}')
+    dev = _compute_device(depth, mask, intrinsic)
+    out = ops.depth_init(depth.to(dev), mask.to(dev), intrinsic.to(dev).float(), m=3.0, erode_radius=erode_radius)
+    if check:
+        counts = out['counts'][:, :3].tolist()                                  # the one device-to-host copy
+        bad = [i for i, c in enumerate(counts) if c[0] == 0 or c[2] == 0]
+        if bad:
+            rows = ', '.join(f'{i} (n_mask={counts[i][0]}, n_valid={counts[i][1]}, n_kept={counts[i][2]})' for i in bad)
+            raise ValueError(f'no initial pose for row(s) {rows}: the mask is empty or no masked depth survives the MAD filter')
+    return out['trans'].to(intrinsic.device)
+
+
+def estimate_translation(depth, mask, intrinsic, kernel=None, erode_radius=0, check=True):
+    """kernel: 'composed' / 'fused' / None = KERNEL.  'fused' moves the inputs to the GPU if they are not there and makes one
+    ops.depth_init call for the batch; with check (one device-to-host copy of the counts) a frame without foreground or without
+    a kept depth raises ValueError naming the rows, without it nothing synchronises and such rows are NaN.  erode_radius > 0
+    (fused only) takes the depths from the mask eroded by that disk; the composed path reproduces the reference, which
+    discards its erosion."""
+    kernel = select_kernel(kernel)
+    if isinstance(erode_radius, bool) or not isinstance(erode_radius, int) or not 0 <= erode_radius <= 8:
+        raise ValueError(f'erode_radius must be an integer in 0..8, got {erode_radius!r}')
+    if kernel == 'fused':
+        return _translation_fused(depth, mask, intrinsic, erode_radius, check).unbind(-1)
+    if erode_radius > 0:
+        raise ValueError("erode_radius needs kernel='fused': the composed path reproduces the reference's discarded erosion")
     z_cam = _estimate_camera_dist(depth, mask)
     uv = _masks_to_centroids(mask)
     u0, v0 = intrinsic[..., 0, 2], intrinsic[..., 1, 2]
@@ -73,9 +124,10 @@ def estimate_translation(depth, mask, intrinsic):
     return (uv[:, 0] - u0) / fu * z_cam, (uv[:, 1] - v0) / fv * z_cam, z_cam
 
 
-def estimate_initial_pose(depth, mask, intrinsic, width, height) -> Camera:
-    """Camera with the estimated translation and identity rotation (initialization.py:89-99)."""
-    translation = torch.stack(estimate_translation(depth, mask, intrinsic), dim=-1)
+def estimate_initial_pose(depth, mask, intrinsic, width, height, kernel=None, erode_radius=0, check=True) -> Camera:
+    """Camera with the estimated translation and identity rotation (initialization.py:89-99); kernel, erode_radius, check: as
+    estimate_translation."""
+    translation = torch.stack(estimate_translation(depth, mask, intrinsic, kernel, erode_radius, check), dim=-1)
     rotation = three.quaternion.identity(intrinsic.shape[0], intrinsic.device)
     extrinsic = three.to_extrinsic_matrix(translation, rotation)
     return Camera(intrinsic, extrinsic, height=height, width=width)
