@@ -6,7 +6,8 @@ process at the headline shape, next to the plain data-gradient launch of the sam
           [-DWINO_PJ_ABL=k] latentfusion_amd/csrc/conv_wino.hip -o scratch/v.so        (one per variant)
     python tools/projbwd_ab.py scratch/a.so scratch/b.so ...
 
-Every variant is compared with the first (max |diff| -- ablation builds are wrong on purpose) and timed round-robin."""
+Every variant is compared with the first (max |diff| -- ablation builds are wrong on purpose) and timed round-robin.
+The kernel's fused part is csrc/wino16_projbwd.inc; the WINO_PJ_ABL bits are described at the top of csrc/wino16_math.h."""
 import ctypes
 import os
 import sys

@@ -5,6 +5,10 @@ library's flags, disassembles both, and diffs every kernel symbol the parent's c
 instruction (addresses dropped, encodings kept).  Kernels that only the working tree has are listed, not compared.
 
     python tools/resample_isa_diff.py [--rev HEAD] [--out profiles/resample_indexed_isa.txt] [--src FILE.hip[=PARENT.hip] ...]
+                                      [--define NAME=VALUE ...]
+
+--define adds -DNAME=VALUE to the parent's and the tree's compile alike, so builds that only a switch selects are compared
+too (profiles/wino_body_split_isa.txt: --src conv_wino.hip, once plain and once per ablation, e.g. --define WINO_ABL=64).
 
 --src names other files of csrc/ (each with its per-file flags of csrc/build.py), e.g. the wide Winograd family
 (profiles/wide_wino_shared_isa.txt: --src wino_fused.hip wino_fused_f16x3.hip wino_gemm.hip).  FILE.hip=PARENT.hip says
@@ -42,11 +46,11 @@ def _objdump():
     return 'llvm-objdump'
 
 
-def disassemble(tree, workdir, tag, src='resample.hip'):
+def disassemble(tree, workdir, tag, src='resample.hip', defines=()):
     """{symbol: [instruction lines]} of the gfx950 code object of csrc/`src` in `tree`."""
     co = os.path.join(workdir, tag + '.' + src + '.co')
     cmd = [hip_build._hipcc(), '-x', 'hip', '--cuda-device-only', '--no-gpu-bundle-output', '-c', os.path.join(tree, CSRC, src), '-o', co]
-    cmd += [f for f in hip_build.FLAGS if f != '-fPIC'] + hip_build.EXTRA.get(src, [])
+    cmd += [f for f in hip_build.FLAGS if f != '-fPIC'] + hip_build.EXTRA.get(src, []) + ['-D' + d for d in defines]
     subprocess.run(cmd, check=True)
     text = subprocess.run([_objdump(), '-d', '--no-leading-addr', co], check=True, stdout=subprocess.PIPE).stdout.decode()
     syms, cur = {}, None
@@ -66,6 +70,7 @@ def main():
     ap.add_argument('--rev', default='HEAD')
     ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'resample_indexed_isa.txt'))
     ap.add_argument('--src', nargs='+', default=['resample.hip'], help='files of csrc/ to compare')
+    ap.add_argument('--define', action='append', default=[], metavar='NAME=VALUE', help='-D for the parent and the tree compile')
     a = ap.parse_args()
     rev = subprocess.run(['git', '-C', ROOT, 'rev-parse', '--short', a.rev], check=True, stdout=subprocess.PIPE).stdout.decode().strip()
     lines, diff, nsym = [], [], 0
@@ -79,12 +84,13 @@ def main():
             src, _, old_src = item.partition('=')
             origin.setdefault(old_src or src, []).append(src)
         for old_src, srcs in origin.items():
-            old = disassemble(parent, tmp, 'parent', old_src)
+            old = disassemble(parent, tmp, 'parent', old_src, a.define)
             new = {}
             for src in srcs:
-                new.update(disassemble(ROOT, tmp, 'tree', src))
+                new.update(disassemble(ROOT, tmp, 'tree', src, a.define))
             lines += [f'# {os.path.join(CSRC, old_src)}: kernel symbols of revision {rev} against {", ".join(srcs)} of the working tree, gfx950, '
-                      f'flags {" ".join(hip_build.FLAGS + hip_build.EXTRA.get(old_src, []))}', '# symbol: instructions (parent / tree)']
+                      f'flags {" ".join(hip_build.FLAGS + hip_build.EXTRA.get(old_src, []) + ["-D" + d for d in a.define])}',
+                      '# symbol: instructions (parent / tree)']
             for name in sorted(old):
                 lines.append(f'#   {name}: {len(old[name])} / {len(new.get(name, []))}')
                 diff += list(difflib.unified_diff(old[name], new.get(name, []), 'parent:' + name, 'tree:' + name, lineterm='', n=2))

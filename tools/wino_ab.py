@@ -11,7 +11,8 @@ round-robin: forward (bias + LeakyReLU + PixelNorm), data-gradient fused with th
 forward with the factor projection riding on it (lf_conv3d_c16_wino_projfwd).  A whole liblf_hip.so works as a variant
 too (the parent commit's against this one's), and `path@0` / `path@1` selects the scalar / packed transforms of that
 library through lf_set_tuning(7, .) before each of its calls; `path@8=0` / `path@8=1` (any `key=value`, comma-separated) the
-generic kernels / the compile-time epilogue forms.  The plain data gradient (no previous layer) is timed as well."""
+generic kernels / the compile-time epilogue forms.  The plain data gradient (no previous layer) is timed as well.
+Ablation variants are builds with -DWINO_ABL=bits; every bit is described at the top of csrc/wino16_math.h."""
 import ctypes
 import os
 import sys

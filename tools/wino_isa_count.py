@@ -8,7 +8,9 @@
 
 Per kernel: VALU and MFMA instructions, packed / scalar fp32 adds and subtractions, s_nop, VGPRs, spills, scratch.  The
 four z-frequency instantiations of wino_compute each run on one wave, so a count / 4 is per wave and tile (plus the
-per-launch prologue).  profiles/wino_pack_isa.txt is this tool's output for the parent and the packed form."""
+per-launch prologue).  profiles/wino_pack_isa.txt is this tool's output for the parent and the packed form.
+conv_wino.hip is the one translation unit of these kernels (wino16_math.h, wino16_compute.h and the two wino16_proj*.inc
+next to it are included by it); the comment at wino_epi_* in csrc/wino16_math.h reads the pinned epilogue roundings off this listing."""
 import re
 import sys
 

@@ -5,6 +5,9 @@ every wave when the kernel is compiled with -DWINO_ABL=16):
     hipcc -x hip --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fno-gpu-rdc -shared -DWINO_ABL=16 \
           latentfusion_amd/csrc/conv_wino.hip -o /tmp/wino_ts.so
     python tools/wino_timeline.py /tmp/wino_ts.so
+
+The stamps are the TS(k) of the tile loop in conv_wino.hip (and, with -DWINO_ABL=48, the CTS(k) inside wino_compute,
+csrc/wino16_compute.h); both macros and their slots are described at the top of csrc/wino16_math.h.
 """
 import ctypes
 import os
