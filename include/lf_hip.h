@@ -828,6 +828,48 @@ int lf_depth_init(const float* depth, const void* mask, int mask_u8, const float
                   float* trans, float* stats, int* counts, void* scratch, size_t scratch_bytes, int B, int H, int W,
                   void* stream);
 
+/* ---- observation preprocessing (csrc/obs_prepare.hip) ---------------------------------------------------------------------------
+ * Observation.zoom -> prepare -> normalize for B frames in ONE launch, whatever B is; no scratch, no atomics (reference
+ * modules/geometry.py:20-44,287-354 crop_to_viewport / Camera.zoom, observation.py:225-282 zoom / prepare / normalize,
+ * recon/models.py Sculptor.encode for the stacked form).
+ *   color [B][C][H][W] fp32 (C >= 0; color and color_out are ignored and may be NULL when C = 0); depth [B][H][W] fp32;
+ *   mask [B][H][W], fp32 (mask_u8 = 0) or bytes (mask_u8 = 1; a byte counts as its value converted to float); boxes [B][4] =
+ *   (x0, y0, x1, y1) in frame pixels, fp32 ON THE DEVICE, the un-truncated viewport of Camera.zoom_viewport; zn, zf [B]: the
+ *   camera's znear - 0.01 and zfar + 0.01 (required with LF_OBS_NORMALIZE, otherwise ignored); T: the target size.
+ *   stages: LF_OBS_PREPARE | LF_OBS_NORMALIZE, any combination; the crop always runs.
+ * Lattice of frame b, per axis (x: corners x0, x1, size W, index i = output column; y: y0, y1, H, output row), every
+ * operation rounded on its own in fp32 unless it says fp64:
+ *   1. c0 = truncf(x0), c1 = truncf(x1)                           (quirk Q15: toward zero; equals the host's fp64 trunc)
+ *   2. start = (float)((double)c0 / (double)W), end = (float)((double)c1 / (double)W)      (one fp64 division each)
+ *   3. T = 1: l = start.  T > 1: step = (end - start) / (float)(T - 1)                     (a subtraction, an IEEE division);
+ *      i <  T / 2 (integer division):  l = start + step * (float)i                         (a multiplication, an addition)
+ *      i >= T / 2:                     l = end - step * (float)(T - 1 - i)                 (a multiplication, a subtraction)
+ *      so point 0 is exactly start and point T - 1 exactly end whenever step is finite, as in every linspace; the bits in
+ *      between are this form's own, NOT those of ATen's linspace.
+ *   4. g = l * 2, then g - 1                                        (the grid value of F.grid_sample, align_corners=False)
+ * Per output pixel (row oy, column ox) the pixel coordinate is lf_unnorm2d(g) and the taps, their validity under zeros
+ * padding and the bilinear weights come from csrc/sample2d_taps.h exactly as in lf_grid_sample2d_fwd: colour is bilinear,
+ * depth and mask are nearest (round-half-even).  A non-finite coordinate takes whatever that header yields; nothing is ever
+ * read outside the frame, and each frame is read only where its box lies.  Then, with m the CROPPED mask value, every
+ * operation rounded separately:
+ *   LF_OBS_PREPARE    colour: c * 2, - 1, * m, + 1, / 2, clamp [0, 1]         (gan_denormalize(gan_normalize(c) * m))
+ *                     depth:  d * m
+ *   LF_OBS_NORMALIZE  colour: c * 2, - 1                                        (gan_normalize)
+ *                     depth:  d - zn, / (zf - zn) (one subtraction per frame, one IEEE division), clamp [0, 1], * 2, - 1
+ *   clamp is torch.clamp: a NaN stays NaN.  The mask output is the cropped mask under every stage.
+ * Outputs: color_out [B][C][T][T], depth_out [B][T][T], mask_out [B][T][T].  stack (optional, NULL = none): the encoder input
+ * written directly, row b at stack + b * stack_row_stride (in floats, >= the planes written) holds the planes
+ * [colour (C) | depth if stack_depth = 1 | mask * 2 - 1] of T * T floats each, with the values of the three outputs; floats of
+ * a row beyond those planes are not touched.
+ * Domain: B, H, W, T >= 1, C >= 0, mask_u8 and stack_depth in {0, 1}, no stage bit beyond the two, zn and zf given with
+ * LF_OBS_NORMALIZE, required pointers not NULL, B * max(C, 1) * H * W < 2^31 and B * (C + 2) * T^2 < 2^31 (else LF_EINVAL);
+ * every pointer 4-byte aligned (LF_EALIGN).  Nothing is launched or written in any of these cases. */
+#define LF_OBS_PREPARE   1
+#define LF_OBS_NORMALIZE 2
+int lf_obs_prepare(const float* color, const float* depth, const void* mask, int mask_u8, const float* boxes, const float* zn,
+                   const float* zf, float* color_out, float* depth_out, float* mask_out, float* stack, long stack_row_stride,
+                   int stack_depth, int B, int C, int H, int W, int T, int stages, void* stream);
+
 /* Block-end rescale by exactly x2 (up = 1) or x0.5 (up = 0): nearest (linear = 0) or bi-/tri-linear
  * with align_corners=False (linear = 1) = Interpolate / F.interpolate(scale_factor=...) of
  * modules/__init__.py:18-36, blocks.py:160-162.  x: [N][D][H][W][C] (D = 1 for dims = 2); the output

@@ -23,6 +23,7 @@ LF_MAP_C2O = 1
 LF_MAP_COEFS = 20
 LF_FUSE_MEAN, LF_FUSE_MAX, LF_FUSE_ABSMAX, LF_FUSE_MEDIAN = 0, 1, 2, 3
 LF_IBR_PAIR_FLOATS, LF_IBR_PAIR_SPLIT, LF_IBR_VIEW_FLOATS, LF_IBR_VIEW_SPLIT = 32, 16, 16, 8   # camera records of lf_ibr_reproject_*
+LF_OBS_PREPARE, LF_OBS_NORMALIZE = 1, 2   # stages of lf_obs_prepare
 LF_AMAX_FLOATS = 2048          # floats of a max-abs side-channel buffer (include/lf_hip.h)
 
 P = c_void_p
@@ -151,6 +152,7 @@ SIGNATURES = {
     'lf_points_pair_dist': (c_int, [P, c_long, P, P, c_int, P, P, c_size_t, c_int, c_int, P]),
     'lf_depth_init_scratch_bytes': (c_size_t, [c_int, c_int, c_int]),
     'lf_depth_init': (c_int, [P, P, c_int, P, c_int, c_float, c_int, P, P, P, P, c_size_t, c_int, c_int, c_int, P]),
+    'lf_obs_prepare': (c_int, [P, P, P, c_int, P, P, P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_epilogue_bwd_c16_scratch_bytes': (c_size_t, [c_long]),
     'lf_epilogue_bwd_c16': (c_int, [P, P, P, P, P, P, c_size_t, c_long, c_uint, c_float, c_int, P]),
     'lf_resample3d_fwd_io': (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P]),

@@ -17,6 +17,50 @@ def gan_denormalize(t):
     return ((t + 1.0) / 2.0).clamp(0, 1)
 
 
+KERNELS = ('composed', 'fused')
+KERNEL = 'composed'        # what Observation.zoom runs when kernel is None: 'composed' (Camera.zoom per map: the reference's host loop
+#                            over the frames around lf_grid_sample2d_fwd) or 'fused' (one ops.observation_prepare call, device tensors only)
+
+
+def _resolve_kernel(kernel):
+    kernel = KERNEL if kernel is None else kernel
+    if kernel not in KERNELS:
+        raise ValueError(f'Unknown observation kernel {kernel!r} (one of {KERNELS})')
+    return kernel
+
+
+def _depth_bounds(camera, eps=0.01):
+    """(zn, zf) of Camera.normalize_depth, (B,) each: the same torch expressions."""
+    return (camera.znear - eps).float().contiguous(), (camera.zfar + eps).float().contiguous()
+
+
+def fused_preprocess(observation, target_dist, target_size, camera=None, prepare=False, normalize=False, stack=None):
+    """zoom (-> prepare -> normalize) of a device observation as ONE ops.observation_prepare call, without a device-to-host copy:
+    the boxes of Camera.zoom_viewport stay on the device.  -> (Observation with the flags of the stages set, the stacked encoder
+    input or None)."""
+    from . import ops
+    camera = observation.camera if camera is None else camera
+    tensors = [t for t in (observation.color, observation.depth, observation.mask) if t is not None]
+    if not all(t.is_cuda for t in tensors):
+        if not torch.cuda.is_available():
+            raise RuntimeError("kernel 'fused' needs a GPU: the preprocessing HIP kernel has no CPU form (use kernel='composed')")
+        raise ValueError("kernel='fused' needs device tensors (move the observation with .to(device); the composed path serves "
+                         "host tensors)")
+    dev = observation.depth.device
+    camera = camera.to(dev)
+    boxes = camera.zoom_viewport(target_size, target_dist)
+    new_camera = camera._like(viewport=boxes)
+    zn, zf = _depth_bounds(new_camera) if normalize else (None, None)
+    out = ops.observation_prepare(observation.color, observation.depth, observation.mask, boxes.detach().float().contiguous(), target_size,
+                                  zn=zn, zf=zf, prepare=prepare, normalize=normalize, stack=stack)
+    flags = dict(is_zoomed=True)
+    if prepare:
+        flags['is_prepared'] = True
+    if normalize:
+        flags['is_normalized'] = True
+    return observation._new(out['color'], out['depth'], out['mask'], new_camera, **flags), out.get('stack')
+
+
 class Observation:
     def __init__(self, color, depth, mask, camera, **kwargs):
         self.color = color.unsqueeze(0) if color is not None and color.dim() == 3 else color
@@ -78,9 +122,13 @@ class Observation:
         return self._new(self.color.expand(n, -1, -1, -1), self.depth.expand(n, -1, -1, -1),
                          self.mask.expand(n, -1, -1, -1), self.camera.repeat(n))
 
-    def zoom(self, target_dist, target_size, camera: Camera = None):
+    def zoom(self, target_dist, target_size, camera: Camera = None, kernel=None):
         """Crop every map to the canonical zoomed viewport (reference :225-236; argument order of
-        Camera.zoom is (size, dist) but the box is symmetric in the two)."""
+        Camera.zoom is (size, dist) but the box is symmetric in the two).  kernel: None (the module's KERNEL) |
+        'composed' | 'fused' (one ops.observation_prepare call for all maps and frames; device tensors only, no device-to-host
+        copy; its crop lattice is the one include/lf_hip.h states, not ATen's linspace bit for bit)."""
+        if _resolve_kernel(kernel) == 'fused':
+            return fused_preprocess(self, target_dist, target_size, camera=camera)[0]
         camera = self.camera if camera is None else camera
         color, new_camera = camera.zoom(self.color, target_size, target_dist, scale_mode='bilinear')
         depth, _ = camera.zoom(self.depth, target_size, target_dist, scale_mode='nearest')
@@ -148,8 +196,12 @@ class Observation:
         return estimate_initial_pose(self.depth, self.mask, self.camera.intrinsic, self.camera.width,
                                      self.camera.height, kernel=kernel, erode_radius=erode_radius).to(self.device)
 
-    def zoom_estimate(self, target_dist, target_size, kernel=None, erode_radius=0):
-        return self.zoom(target_dist, target_size, camera=self.estimate_camera(kernel=kernel, erode_radius=erode_radius))
+    def zoom_estimate(self, target_dist, target_size, kernel=None, erode_radius=0, zoom_kernel=None):
+        """kernel, erode_radius: of the initial pose (estimate_camera); zoom_kernel: of the crop (zoom).  With both 'fused' the
+        chain from raw device frames to zoomed maps copies nothing to the host but the initial pose's count check."""
+        _resolve_kernel(zoom_kernel)
+        return self.zoom(target_dist, target_size, camera=self.estimate_camera(kernel=kernel, erode_radius=erode_radius),
+                         kernel=zoom_kernel)
 
     def uncrop(self, camera=None):
         camera = self.camera if camera is None else camera

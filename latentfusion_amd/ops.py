@@ -1107,6 +1107,85 @@ def depth_init(depth, mask, intrinsic=None, m=3.0, erode_radius=0):
     return out
 
 
+OBS_STACKS = (None, 'color_mask', 'color_depth_mask')
+
+
+def observation_prepare(color, depth, mask, boxes, target_size, zn=None, zf=None, prepare=False, normalize=False, stack=None):
+    """Observation.zoom -> prepare -> normalize for B frames in one launch (lf_obs_prepare; observation.py, include/lf_hip.h for
+    the arithmetic op by op).  color: (B,C,H,W) float32 or None (no colour planes); depth, mask: (B,1,H,W) or (B,H,W), depth
+    float32, mask float32, bool or uint8 (a byte counts as its value); boxes: (B,4) float32 = (x0, y0, x1, y1) in frame pixels,
+    the un-truncated viewport of Camera.zoom_viewport, ON THE DEVICE; target_size = T.  The crop always runs (colour bilinear,
+    depth and mask nearest, zeros padding); prepare / normalize add the chains of Observation.prepare / normalize, the latter
+    needs zn, zf: (B,) float32 = the camera's znear - 0.01 and zfar + 0.01.  stack: None, 'color_mask' or 'color_depth_mask'
+    also writes the encoder input [colour | depth | mask * 2 - 1] (Sculptor.encode's concatenation).
+    -> {'color': (B,C,T,T) or None, 'depth': (B,1,T,T), 'mask': (B,1,T,T), 'stack': (B,planes,T,T) when asked}.
+    Every argument is checked before the library is touched, and nothing here synchronises."""
+    d3 = _frames_arg(depth, 'depth', (torch.float32,))
+    k3 = _frames_arg(mask, 'mask', (torch.float32, torch.bool, torch.uint8))
+    if tuple(d3.shape) != tuple(k3.shape):
+        raise ValueError(f'depth and mask differ in shape: {tuple(depth.shape)} and {tuple(mask.shape)}')
+    dev = d3.device
+    if k3.device != dev:
+        raise ValueError('depth and mask must be on one device')
+    B, H, W = d3.shape
+    C = 0
+    if color is not None:
+        if not isinstance(color, torch.Tensor) or not color.is_cuda or color.device != dev:
+            raise ValueError('color must be a device tensor on the device of depth (or None): the HIP path has no CPU fallback')
+        if color.dtype != torch.float32:
+            raise ValueError(f'color must be float32, got {color.dtype}')
+        if color.dim() != 4 or color.shape[0] != B or tuple(color.shape[2:]) != (H, W):
+            raise ValueError(f'color must be shaped ({B}, C, {H}, {W}), got {tuple(color.shape)}')
+        C = color.shape[1]
+    if isinstance(target_size, bool) or not isinstance(target_size, int) or target_size < 1:
+        raise ValueError(f'target_size must be a positive integer, got {target_size!r}')
+    T = target_size
+    if B * max(C, 1) * H * W >= 2 ** 31 or B * (C + 2) * T * T >= 2 ** 31:
+        raise ValueError(f'{B} frames of {max(C, 1)} x {H} x {W} -> {C + 2} x {T} x {T}: at most 2^31 - 1 values per call')
+    if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda or boxes.device != dev:
+        raise ValueError('boxes must be a device tensor on the device of depth')
+    if boxes.dtype != torch.float32 or tuple(boxes.shape) != (B, 4):
+        raise ValueError(f'boxes must be float32 shaped ({B}, 4), got {boxes.dtype} {tuple(boxes.shape)}')
+    for name, flag in (('prepare', prepare), ('normalize', normalize)):
+        if not isinstance(flag, bool):
+            raise ValueError(f'{name} must be a bool, got {flag!r}')
+    for name, z in (('zn', zn), ('zf', zf)):
+        if z is None:
+            if normalize:
+                raise ValueError(f'normalize needs {name}')
+            continue
+        if not isinstance(z, torch.Tensor) or not z.is_cuda or z.device != dev:
+            raise ValueError(f'{name} must be a device tensor on the device of depth')
+        if z.dtype != torch.float32 or tuple(z.shape) != (B,):
+            raise ValueError(f'{name} must be float32 shaped ({B},), got {z.dtype} {tuple(z.shape)}')
+    if isinstance(stack, (list, dict, set)) or stack not in OBS_STACKS:
+        raise ValueError(f'stack {stack!r}: one of {OBS_STACKS}')
+    L = _lib.lib()
+    d3 = _aligned4(d3)
+    u8 = k3.dtype != torch.float32
+    k3 = _aligned4(k3.view(torch.uint8) if k3.dtype == torch.bool else k3)
+    color = _aligned4(color) if C > 0 else None
+    boxes = _aligned4(boxes)
+    zn, zf = (_aligned4(zn), _aligned4(zf)) if normalize else (None, None)
+    color_out = torch.empty(B, C, T, T, device=dev, dtype=torch.float32) if C > 0 else None
+    depth_out = torch.empty(B, 1, T, T, device=dev, dtype=torch.float32)
+    mask_out = torch.empty(B, 1, T, T, device=dev, dtype=torch.float32)
+    with_depth = stack == 'color_depth_mask'
+    planes = C + 1 + int(with_depth)
+    stacked = torch.empty(B, planes, T, T, device=dev, dtype=torch.float32) if stack is not None else None
+    stages = (_lib.LF_OBS_PREPARE if prepare else 0) | (_lib.LF_OBS_NORMALIZE if normalize else 0)
+    with _timed('obs_prepare', f'{B}x{C}x{H}x{W}->{T}'):
+        check(L.lf_obs_prepare(_ptr(color) if color is not None else None, _ptr(d3), _ptr(k3), int(u8), _ptr(boxes),
+                               _ptr(zn) if zn is not None else None, _ptr(zf) if zf is not None else None,
+                               _ptr(color_out) if color_out is not None else None, _ptr(depth_out), _ptr(mask_out),
+                               _ptr(stacked) if stacked is not None else None, planes * T * T, int(with_depth), B, C, H, W, T,
+                               stages, _stream()), 'lf_obs_prepare')
+    out = {'color': color_out, 'depth': depth_out, 'mask': mask_out}
+    if stacked is not None:
+        out['stack'] = stacked
+    return out
+
+
 def _wino_ok(x, weight):
     """The Winograd kernel serves 3-D 16 -> 16 convolutions on volumes of at least one 2x8x16 tile row."""
     return (x.dim() == 5 and tuple(weight.shape[:2]) == (16, 16) and x.shape[1] == 16

@@ -4,7 +4,8 @@ from pathlib import Path
 
 import torch
 
-from ..observation import Observation
+from ..observation import KERNELS as PREPROCESS_KERNELS
+from ..observation import Observation, fused_preprocess
 from . import models
 
 
@@ -26,18 +27,26 @@ class _Frozen:
 
 
 class LatentFusionModel:
+    preprocess_kernel = 'composed'      # (also what an instance made without __init__ runs)
+
     @classmethod
-    def from_checkpoint(cls, checkpoint, device='cpu', ibr_kernel=None):
+    def from_checkpoint(cls, checkpoint, device='cpu', ibr_kernel=None, preprocess_kernel='composed'):
         if isinstance(checkpoint, (Path, str)):
             checkpoint = torch.load(checkpoint, map_location='cpu', weights_only=False)
         sculptor, fuser, photographer, _, generator = models.load_models(checkpoint, device=device, return_generator=True)
         return cls(sculptor, fuser, photographer, checkpoint['args']['camera_dist'], device, generator=generator,
-                   ibr_kernel=ibr_kernel)
+                   ibr_kernel=ibr_kernel, preprocess_kernel=preprocess_kernel)
 
-    def __init__(self, sculptor, fuser, photographer, camera_dist, device, generator=None, ibr_kernel=None):
-        """ibr_kernel: how the colour paths reproject (ibr.reproject_views): None = ibr.KERNEL, 'composed' or 'fused'."""
+    def __init__(self, sculptor, fuser, photographer, camera_dist, device, generator=None, ibr_kernel=None,
+                 preprocess_kernel='composed'):
+        """ibr_kernel: how the colour paths reproject (ibr.reproject_views): None = ibr.KERNEL, 'composed' or 'fused'.
+        preprocess_kernel: how preprocess_observation runs: 'composed' (zoom, prepare, normalize step by step) or 'fused' (one
+        ops.observation_prepare call for a device observation none of whose meta flags is set; anything else stays composed)."""
+        if preprocess_kernel not in PREPROCESS_KERNELS:
+            raise ValueError(f'preprocess_kernel {preprocess_kernel!r}: one of {PREPROCESS_KERNELS}')
         self.device = device
         self.ibr_kernel = ibr_kernel
+        self.preprocess_kernel = preprocess_kernel
         self.sculptor, self.fuser, self.photographer = sculptor.to(device), fuser.to(device), photographer.to(device)
         self.generator = generator.to(device) if generator is not None else None
         self.camera_dist = camera_dist
@@ -83,7 +92,15 @@ class LatentFusionModel:
             return observation.zoom(self.camera_dist, self.input_size)
         return observation
 
+    def _fused_applies(self, observation):
+        """One fused call serves a device observation that is neither zoomed, prepared nor normalized."""
+        meta = observation.meta
+        return (self.preprocess_kernel == 'fused' and not (meta['is_zoomed'] or meta['is_prepared'] or meta['is_normalized'])
+                and observation.depth.is_cuda)
+
     def preprocess_observation(self, observation):
+        if self._fused_applies(observation):
+            return fused_preprocess(observation, self.camera_dist, self.input_size, prepare=True, normalize=True)[0]
         if not observation.meta['is_zoomed']:
             observation = observation.zoom(self.camera_dist, self.input_size)
         if not observation.meta['is_prepared']:
@@ -94,10 +111,18 @@ class LatentFusionModel:
 
     def build_latent_object(self, observation: Observation):
         """Reference views -> fused latent volume (1,1,C,S,S,S)."""
-        observation = self.preprocess_observation(observation.to(self.device))
+        observation = observation.to(self.device)
+        x = None
+        if self._fused_applies(observation) and self.sculptor.input_color and self.sculptor.input_mask:
+            # the kernel also writes the encoder's stacked input: Sculptor.encode skips its concatenation
+            stack = 'color_depth_mask' if self.sculptor.input_depth else 'color_mask'
+            observation, x = fused_preprocess(observation, self.camera_dist, self.input_size, prepare=True, normalize=True,
+                                              stack=stack)
+        else:
+            observation = self.preprocess_observation(observation)
         with torch.no_grad():
             z_obj, _ = self.sculptor.encode(self.fuser, camera=observation.camera, color=observation.color.unsqueeze(0),
-                                            depth=observation.depth.unsqueeze(0), mask=observation.mask.unsqueeze(0))
+                                            depth=observation.depth.unsqueeze(0), mask=observation.mask.unsqueeze(0), x=x)
         return z_obj
 
     def compute_latent_code(self, observation, camera):

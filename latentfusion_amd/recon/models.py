@@ -133,17 +133,23 @@ class Sculptor(_Checkpointed):
             z_obj_mid.append(z)
         return self.output_block(z), z_cam_mid, z_obj_mid
 
-    def encode(self, fuser, camera, color, depth=None, mask=None, data_parallel=False):
+    def encode(self, fuser, camera, color, depth=None, mask=None, data_parallel=False, x=None):
+        """x: the stacked input (B*V, in_channels, H, W) = [colour | depth | mask * 2 - 1] when the caller holds it already
+        (ops.observation_prepare writes it); default: concatenated here from colour, depth and mask."""
         device = next(self.parameters()).device
         num_views = color.shape[1] if color.dim() == 5 else 1
-        parts = []
-        if self.input_color:
-            parts.append(bv2b(color) if color.dim() == 5 else color)
-        if self.input_depth:
-            parts.append(bv2b(depth) if depth.dim() == 5 else depth)
-        if self.input_mask:
-            parts.append(gan_normalize(bv2b(mask) if mask.dim() == 5 else mask))
-        x = torch.cat(parts, dim=1).to(device)
+        if x is None:
+            parts = []
+            if self.input_color:
+                parts.append(bv2b(color) if color.dim() == 5 else color)
+            if self.input_depth:
+                parts.append(bv2b(depth) if depth.dim() == 5 else depth)
+            if self.input_mask:
+                parts.append(gan_normalize(bv2b(mask) if mask.dim() == 5 else mask))
+            x = torch.cat(parts, dim=1)
+        elif x.dim() != 4 or x.shape[1] != self.in_channels:
+            raise ValueError(f'x must be shaped (B*V, {self.in_channels}, H, W), got {tuple(x.shape)}')
+        x = x.to(device)
         z_obj, z_cam_mid, z_obj_mid = self(x, camera.to(device))
         z_obj = b2bv(z_obj, num_views)
         z_cam_mid = [b2bv(z, num_views) for z in z_cam_mid]
