@@ -828,6 +828,47 @@ int lf_depth_init(const float* depth, const void* mask, int mask_u8, const float
                   float* trans, float* stats, int* counts, void* scratch, size_t scratch_bytes, int B, int H, int W,
                   void* stream);
 
+/* ---- training losses (csrc/train_loss.hip) --------------------------------------------------------------------------------------
+ * The loss tail of the generator's training step in three launches forward and one backward, no device-to-host copy, no float
+ * atomics (reference losses.py:33-57 HardPixelLoss, losses.py:94-99 beta_prior_loss, train_reconstruct.py:491-521 the terms).
+ * Two parts; either may be absent, not both.
+ * Hard-pixel part (absent when x = NULL; B, C, H, W, base, k and the part's other pointers are then ignored):
+ *   x, y [B][C][H][W] fp32; base 0 = L1, 1 = smooth-L1 with beta 1; l[b][p] = mean_c base(x, y), every operation rounded on
+ *   its own (no FMA contraction): L1 |x - y|; smooth-L1 d = |x - y|, d < 1 ? 0.5f * d * d : d - 0.5f.  For C = 1 these are the
+ *   bits of F.l1_loss / F.smooth_l1_loss(reduction='none'); for C > 1 the channels are added in the order 0 .. C-1 and divided
+ *   by C.  A NaN loss counts as the positive quiet NaN, above +inf.
+ *   k = 0: no mining, the term is the mean over all B*C*H*W elements.  1 <= k <= H*W: per image the k largest l[b][.] are
+ *   kept and the term is their mean over B*k.  One radix select per image on the bit patterns gives thresh[b] = t_b, the k-th
+ *   largest value, sel[b][2] = (n_gt = the count above it, n_tie = k - n_gt); of the pixels equal to t_b the n_tie of lowest
+ *   pixel index are kept.  img_sum[b] = the kept sum of image b.  (k = 0: thresh = 0, sel = (H*W, 0).)  An image's sum is split
+ *   by (H, W) alone and finished in fp64: image b of a batch has the bits of a call on that image alone.
+ * Mask part (absent when mlogit = NULL; Mn, alpha, beta, log_beta are then ignored): mlogit = z, mtarget = t [Mn] fp32.
+ *   mask_recon = mean of max(z, 0) - z * t + log1p(exp(-|z|)).
+ *   mask_beta  = mean of clamp(-((alpha - 1) * log(clamp(m, 1e-4)) + (beta - 1) * log(clamp(1 - m, 1e-4)) - log_beta), min 0),
+ *   m = sigmoid(z) rounded to fp32 and 1 - m formed from that value; log_beta = lgamma(alpha) + lgamma(beta) -
+ *   lgamma(alpha + beta) comes from the host.  Elements in fp32, sums in fp64 in an order that follows Mn alone.
+ * terms[4] = (recon, mask_recon, mask_beta, 0) on the device, 0 for an absent part.
+ * lf_recon_loss_bwd reads g_terms[3] = d/d(terms) FROM DEVICE MEMORY and the forward's thresh and sel and writes
+ *   gx [B][C][H][W]: exactly 0 outside the selection, inside g_terms[0] / (B*k*C) * base' (B*H*W*C for k = 0), base' =
+ *   sign(x - y) for L1 and for smooth-L1 at d >= 1, (x - y) otherwise;
+ *   gmlogit [Mn] = g_terms[1] * (m - t) / Mn + g_terms[2] * dbeta/dm * m * (1 - m) / Mn, dbeta/dm zero where the outer clamp is
+ *   active and, per factor, where its inner clamp is.
+ *   One workgroup per image walks the pixels in index order (the tied pixels are ranked by a ballot prefix count), so two
+ *   calls give the same bits.
+ * Scratch: lf_recon_loss_scratch_bytes(B, C, H, W, Mn) bytes; B = C = H = W = 0 there stands for an absent hard-pixel part,
+ * Mn = 0 for an absent mask part.  It returns 0 outside the domain and never touches the device.
+ * Domain (else LF_EINVAL): terms, scratch (fwd), g_terms (bwd) and the pointers of every present part not NULL; a part
+ * present; B, C, H, W >= 1, C <= 4, H*W < 2^31 - 1, 0 <= k <= H*W, base in {0, 1}; 1 <= Mn <= 2^40; ceil(B*H*W / 256) +
+ * ceil(Mn / 2048) and B + ceil(Mn / 4096) workgroups at most 2^31 - 1.  Every pointer 4-byte aligned, scratch 8-byte aligned
+ * (LF_EALIGN).  Less scratch than the query says is LF_ENOSPC.  Nothing is launched or written in any of these cases. */
+size_t lf_recon_loss_scratch_bytes(int B, int C, int H, int W, long Mn);
+int lf_recon_loss_fwd(const float* x, const float* y, int base, int k, const float* mlogit, const float* mtarget, float alpha,
+                      float beta, float log_beta, float* thresh, int* sel, float* img_sum, float* terms, void* scratch,
+                      size_t scratch_bytes, int B, int C, int H, int W, long Mn, void* stream);
+int lf_recon_loss_bwd(const float* g_terms, const float* x, const float* y, int base, int k, const float* thresh, const int* sel,
+                      const float* mlogit, const float* mtarget, float alpha, float beta, float log_beta, float* gx,
+                      float* gmlogit, int B, int C, int H, int W, long Mn, void* stream);
+
 /* ---- observation preprocessing (csrc/obs_prepare.hip) ---------------------------------------------------------------------------
  * Observation.zoom -> prepare -> normalize for B frames in ONE launch, whatever B is; no scratch, no atomics (reference
  * modules/geometry.py:20-44,287-354 crop_to_viewport / Camera.zoom, observation.py:225-282 zoom / prepare / normalize,

@@ -152,6 +152,11 @@ SIGNATURES = {
     'lf_points_pair_dist': (c_int, [P, c_long, P, P, c_int, P, P, c_size_t, c_int, c_int, P]),
     'lf_depth_init_scratch_bytes': (c_size_t, [c_int, c_int, c_int]),
     'lf_depth_init': (c_int, [P, P, c_int, P, c_int, c_float, c_int, P, P, P, P, c_size_t, c_int, c_int, c_int, P]),
+    'lf_recon_loss_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_long]),
+    'lf_recon_loss_fwd': (c_int, [P, P, c_int, c_int, P, P, c_float, c_float, c_float, P, P, P, P, P, c_size_t, c_int, c_int,
+                                  c_int, c_int, c_long, P]),
+    'lf_recon_loss_bwd': (c_int, [P, P, P, c_int, c_int, P, P, P, P, c_float, c_float, c_float, P, P, c_int, c_int, c_int, c_int,
+                                  c_long, P]),
     'lf_obs_prepare': (c_int, [P, P, P, c_int, P, P, P, P, P, P, P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'lf_epilogue_bwd_c16_scratch_bytes': (c_size_t, [c_long]),
     'lf_epilogue_bwd_c16': (c_int, [P, P, P, P, P, P, c_size_t, c_long, c_uint, c_float, c_int, P]),

@@ -16,15 +16,51 @@ def reduce_loss(loss, reduction='mean', dim=None):
     raise ValueError(f'Unknown reduction {reduction!r}')
 
 
+# How the training losses are evaluated: 'composed' = the ATen chain below (the default, CPU and device alike); 'fused' = the HIP
+# kernels of ops.recon_losses (device tensors only, opt-in through `kernel=` / GeneratorStep's `loss_kernel=`)
+KERNEL = 'composed'
+KERNELS = ('composed', 'fused')
+
+
+def select_kernel(kernel, name='kernel'):
+    """`kernel` or, for None, the module switch; anything else than the two names is a ValueError."""
+    kernel = KERNEL if kernel is None else kernel
+    if not isinstance(kernel, str) or kernel not in KERNELS:
+        raise ValueError(f'{name} {kernel!r}: one of {KERNELS}')
+    return kernel
+
+
+def fused_base(base_loss):
+    """The name ops.recon_losses knows a base-loss module by, or None when the fused kernels do not provide it."""
+    if type(base_loss) is nn.L1Loss:
+        return 'l1'
+    if type(base_loss) is nn.SmoothL1Loss and base_loss.beta == 1.0:
+        return 'smooth_l1'
+    return None
+
+
 class HardPixelLoss(nn.Module):
     """Mean (or sum) of the k largest per-pixel losses of every image (losses.py:33-56): the base loss is
-    evaluated per element, reduced over channels, and the k hardest pixels of each (B*V) image are kept."""
+    evaluated per element, reduced over channels, and the k hardest pixels of each (B*V) image are kept.
+    kernel: None (= KERNEL), 'composed' or 'fused' (ops.recon_losses: device tensors, reduction='mean', L1 or smooth-L1 with
+    beta 1).  `k` is read at every call, so a trainer may schedule it."""
 
-    def __init__(self, base_loss, k, reduction='mean', **kwargs):
+    def __init__(self, base_loss, k, reduction='mean', kernel=None, **kwargs):
         super().__init__()
         self.base_loss = base_loss(reduction='none', **kwargs)
         self.k = k
         self.reduction = reduction
+        self.kernel = None if kernel is None else select_kernel(kernel)
+        if self.kernel == 'fused':
+            self._fused_base()
+
+    def _fused_base(self):
+        base = fused_base(self.base_loss)
+        if self.reduction != 'mean' or base is None:
+            raise ValueError(f"kernel='fused' provides reduction='mean' over nn.L1Loss or nn.SmoothL1Loss (beta 1), not "
+                             f"reduction={self.reduction!r} over {type(self.base_loss).__name__}: use the composed path "
+                             f"(kernel='composed')")
+        return base
 
     def forward(self, x, y):
         if x.dim() > 4:
@@ -35,6 +71,12 @@ class HardPixelLoss(nn.Module):
             raise ValueError('x must be in BCHW format')
         if y.dim() != 4:
             raise ValueError('y must be in BCHW format')
+        if select_kernel(self.kernel) == 'fused':
+            base = self._fused_base()
+            if not (x.is_cuda and y.is_cuda):
+                raise ValueError("kernel='fused' needs device tensors: on the CPU use the composed path (kernel='composed')")
+            from . import ops
+            return ops.recon_losses(x, y, base, self.k)[0]
         loss = self.base_loss(x, y)
         loss = reduce_loss(loss, dim=1, reduction=self.reduction).reshape(x.size(0), -1)
         loss, _ = torch.topk(loss, k=self.k, dim=1, largest=True)
@@ -65,16 +107,18 @@ def beta_prior_loss(tensor, alpha, beta, reduction='mean', eps=1e-4):
     return reduce_loss((-loss).clamp(min=0), reduction=reduction)
 
 
-def get_recon_criterion(loss_type, k=2000):
-    """trainutils.py:114-133 (the VGG perceptual variant needs torchvision weights and is not provided)."""
+def get_recon_criterion(loss_type, k=2000, kernel=None):
+    """trainutils.py:114-133 (the VGG perceptual variant needs torchvision weights and is not provided).  kernel: passed on to
+    HardPixelLoss; the other criteria are plain torch modules."""
+    select_kernel(kernel)
     if loss_type == 'smooth_l1':
         return nn.SmoothL1Loss()
     if loss_type == 'l1':
         return nn.L1Loss()
     if loss_type == 'hard_l1':
-        return HardPixelLoss(nn.L1Loss, k=k)
+        return HardPixelLoss(nn.L1Loss, k=k, kernel=kernel)
     if loss_type == 'hard_smooth_l1':
-        return HardPixelLoss(nn.SmoothL1Loss, k=k)
+        return HardPixelLoss(nn.SmoothL1Loss, k=k, kernel=kernel)
     if loss_type == 'binary_cross_entropy':
         return nn.BCEWithLogitsLoss(reduction='none')
     raise ValueError(f'Unknown recon_loss_type {loss_type!r}.')

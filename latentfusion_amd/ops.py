@@ -1186,6 +1186,140 @@ def observation_prepare(color, depth, mask, boxes, target_size, zn=None, zf=None
     return out
 
 
+RECON_BASES = ('l1', 'smooth_l1')
+
+
+def _recon_args(x, y, base, k, mask_logits, mask_target, beta_param):
+    """The argument rules of recon_losses / recon_losses_fwd; raises ValueError, touches neither the library nor the device."""
+    if x is None and mask_logits is None:
+        raise ValueError('recon_losses needs x / y, mask_logits / mask_target or both')
+    dev = None
+    if x is not None:
+        for name, t in (('x', x), ('y', y)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f'{name} must be a device tensor: the HIP path has no CPU fallback (use the composed path)')
+            if not t.is_floating_point():
+                raise ValueError(f'{name} must be a floating-point tensor, got {t.dtype}')
+        if x.dim() != 4 or tuple(x.shape) != tuple(y.shape) or x.numel() == 0:
+            raise ValueError(f'x and y must be shaped (B,C,H,W) alike, got {tuple(x.shape)} and {tuple(y.shape)}')
+        if y.device != x.device:
+            raise ValueError('x and y must be on one device')
+        dev = x.device
+        B, C, H, W = x.shape
+        if not 1 <= C <= 4:
+            raise ValueError(f'{C} channels: 1 to 4')
+        if H * W >= 2 ** 31 - 1 or B * H * W >= 2 ** 31 * 256:
+            raise ValueError(f'{B} images of {H} x {W} pixels are too many for one call')
+        if isinstance(base, (list, dict, set)) or base not in RECON_BASES:
+            raise ValueError(f'base {base!r}: one of {RECON_BASES}')
+        if isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= H * W:
+            raise ValueError(f'k must be an integer in 0..{H * W} (0 = no mining), got {k!r}')
+    elif y is not None:
+        raise ValueError('y without x')
+    if mask_logits is not None:
+        for name, t in (('mask_logits', mask_logits), ('mask_target', mask_target)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise ValueError(f'{name} must be a device tensor: the HIP path has no CPU fallback (use the composed path)')
+            if not t.is_floating_point():
+                raise ValueError(f'{name} must be a floating-point tensor, got {t.dtype}')
+        if tuple(mask_logits.shape) != tuple(mask_target.shape) or mask_logits.numel() == 0:
+            raise ValueError(f'mask_logits and mask_target differ in shape or are empty: {tuple(mask_logits.shape)} and '
+                             f'{tuple(mask_target.shape)}')
+        if mask_target.device != mask_logits.device or (dev is not None and mask_logits.device != dev):
+            raise ValueError('all tensors must be on one device')
+        if mask_logits.numel() > 2 ** 40:
+            raise ValueError('mask_logits is too large for one call')
+        if isinstance(beta_param, bool) or not isinstance(beta_param, (int, float)) or not beta_param > 0:
+            raise ValueError(f'beta_param must be a positive number, got {beta_param!r}')
+    elif mask_target is not None:
+        raise ValueError('mask_target without mask_logits')
+
+
+def _recon_beta(beta_param):
+    """(alpha, beta, log_beta) as the library takes them; the prior of the training step is symmetric."""
+    if beta_param is None:
+        return 1.0, 1.0, 0.0
+    from . import losses
+    return float(beta_param), float(beta_param), float(losses._log_beta(float(beta_param), float(beta_param)))
+
+
+def _opt_ptr(t):
+    return _ptr(t) if t is not None else None
+
+
+def recon_losses_fwd(x, y, base, k, mask_logits=None, mask_target=None, beta_param=None):
+    """lf_recon_loss_fwd on prepared tensors (fp32, contiguous): -> {'terms': (4,) = (recon, mask_recon, mask_beta, 0), and with
+    x: 'thresh': (B,), 'sel': (B,2) int32 = (n_gt, n_tie), 'img_sum': (B,)}.  Three launches, nothing synchronises."""
+    _recon_args(x, y, base, k, mask_logits, mask_target, beta_param)
+    L = _lib.lib()
+    dev = x.device if x is not None else mask_logits.device
+    B, C, H, W = x.shape if x is not None else (0, 0, 0, 0)
+    Mn = mask_logits.numel() if mask_logits is not None else 0
+    a, b, lb = _recon_beta(beta_param if mask_logits is not None else None)
+    out = {'terms': torch.empty(4, device=dev, dtype=torch.float32)}
+    if x is not None:
+        out['thresh'] = torch.empty(B, device=dev, dtype=torch.float32)
+        out['sel'] = torch.empty(B, 2, device=dev, dtype=torch.int32)
+        out['img_sum'] = torch.empty(B, device=dev, dtype=torch.float32)
+    nbytes = L.lf_recon_loss_scratch_bytes(B, C, H, W, Mn)
+    scratch = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.float64)
+    with _timed('recon_loss_fwd', f'{B}x{C}x{H}x{W} k={k} Mn={Mn}'):
+        check(L.lf_recon_loss_fwd(_opt_ptr(x), _opt_ptr(y), RECON_BASES.index(base) if x is not None else 0,
+                                  k if x is not None else 0, _opt_ptr(mask_logits), _opt_ptr(mask_target), a, b, lb,
+                                  _opt_ptr(out.get('thresh')), _opt_ptr(out.get('sel')), _opt_ptr(out.get('img_sum')),
+                                  _ptr(out['terms']), _ptr(scratch, True), scratch.numel() * 8, B, C, H, W, Mn, _stream()),
+              'lf_recon_loss_fwd')
+    return out
+
+
+def recon_losses_bwd(g_terms, x, y, base, k, thresh, sel, mask_logits=None, mask_target=None, beta_param=None):
+    """lf_recon_loss_bwd: g_terms (>= 3,) fp32 ON THE DEVICE -> (gx or None, gmlogit or None).  One launch."""
+    L = _lib.lib()
+    B, C, H, W = x.shape if x is not None else (0, 0, 0, 0)
+    Mn = mask_logits.numel() if mask_logits is not None else 0
+    a, b, lb = _recon_beta(beta_param if mask_logits is not None else None)
+    gx = torch.empty_like(x) if x is not None else None
+    gz = torch.empty_like(mask_logits) if mask_logits is not None else None
+    with _timed('recon_loss_bwd', f'{B}x{C}x{H}x{W} k={k} Mn={Mn}'):
+        check(L.lf_recon_loss_bwd(_ptr(g_terms), _opt_ptr(x), _opt_ptr(y), RECON_BASES.index(base) if x is not None else 0,
+                                  k if x is not None else 0, _opt_ptr(thresh), _opt_ptr(sel), _opt_ptr(mask_logits),
+                                  _opt_ptr(mask_target), a, b, lb, _opt_ptr(gx), _opt_ptr(gz), B, C, H, W, Mn, _stream()),
+              'lf_recon_loss_bwd')
+    return gx, gz
+
+
+class _ReconLosses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, y, z, t, base, k, beta_param):
+        out = recon_losses_fwd(x, y, base, k, z, t, beta_param)
+        ctx.save_for_backward(x, y, z, t, out.get('thresh'), out.get('sel'))
+        ctx.cfg = (base, k, beta_param)
+        return out['terms']
+
+    @staticmethod
+    def backward(ctx, g):
+        x, y, z, t, thresh, sel = ctx.saved_tensors
+        base, k, beta_param = ctx.cfg
+        gx, gz = recon_losses_bwd(g.float().contiguous(), x, y, base, k, thresh, sel, z, t, beta_param)
+        return (gx if ctx.needs_input_grad[0] else None, None, gz if ctx.needs_input_grad[2] else None, None, None, None, None)
+
+
+def recon_losses(x, y, base, k, mask_logits=None, mask_target=None, beta_param=None):
+    """The loss tail of the generator's training step in one call (lf_recon_loss_fwd / _bwd; losses.py HardPixelLoss,
+    beta_prior_loss, recon/training.py): -> terms (3,) on the device = (recon, mask_recon, mask_beta), differentiable w.r.t. x
+    and mask_logits (y and mask_target are constants).  x, y: (B,C,H,W), C <= 4, or both None (mask terms alone); base: 'l1' or
+    'smooth_l1' (beta 1); k = 0: the mean over all elements, 1 <= k <= H*W: the mean of every image's k largest per-pixel
+    losses (mean over channels); of the pixels equal to an image's k-th largest loss those of lowest index carry the
+    gradient.  mask_logits, mask_target: any shape alike, or both None; beta_param: the symmetric Beta prior's parameter, needed
+    with the mask part.  The term of an absent part is 0.  Every argument is checked before the library is touched."""
+    _recon_args(x, y, base, k, mask_logits, mask_target, beta_param)
+    if x is not None:
+        x, y = x.float().contiguous(), y.detach().float().contiguous()
+    if mask_logits is not None:
+        mask_logits, mask_target = mask_logits.float().contiguous(), mask_target.detach().float().contiguous()
+    return _ReconLosses.apply(x, y, mask_logits, mask_target, base, k, beta_param)[:3]
+
+
 def _wino_ok(x, weight):
     """The Winograd kernel serves 3-D 16 -> 16 convolutions on volumes of at least one 2x8x16 tile row."""
     return (x.dim() == 5 and tuple(weight.shape[:2]) == (16, 16) and x.shape[1] == 16

@@ -20,6 +20,11 @@ import torch.nn.functional as F
 from .. import _lib, losses, ops, parallel
 
 
+# depth loss type -> (base of ops.recon_losses, hard-pixel mining) under loss_kernel='fused'
+_FUSED_DEPTH_TYPES = {'l1': ('l1', False), 'smooth_l1': ('smooth_l1', False), 'hard_l1': ('l1', True),
+                      'hard_smooth_l1': ('smooth_l1', True)}
+
+
 class FlatParameters:
     """Re-homes the parameters of `modules` into one contiguous buffer (views keep their shapes)."""
 
@@ -86,8 +91,11 @@ class GeneratorStep:
                  g_depth_recon_loss_type='hard_smooth_l1', g_depth_recon_loss_weight=25.0, g_depth_recon_loss_k=16384,
                  g_mask_recon_loss_type='binary_cross_entropy', g_mask_recon_loss_weight=25.0, g_mask_recon_loss_k=2000,
                  g_mask_beta_loss_weight=0.0, g_mask_beta_loss_param=0.01, batch_groups=1, generator_input_depth=False,
-                 depth_noise_std=0.0, process_group=None, use_amp=False):
-        """use_amp: the reference's `--use-amp` (trainutils.py:41,243-246; train_reconstruct.py:455,524-532): the generator's
+                 depth_noise_std=0.0, process_group=None, use_amp=False, loss_kernel=None):
+        """loss_kernel: None (= losses.KERNEL), 'composed' (the ATen chain of losses.py) or 'fused' (ONE ops.recon_losses call for
+        depth_recon, mask_recon and mask_beta: lf_recon_loss_fwd / _bwd; needs the released recipe's binary_cross_entropy mask
+        term).
+        use_amp: the reference's `--use-amp` (trainutils.py:41,243-246; train_reconstruct.py:455,524-532): the generator's
         forward runs under autocast.  Here the policy is bf16 (ops.autocast): same exponent range as fp32, so the
         reference's GradScaler has nothing to do and is not reproduced; master weights, gradients' accumulation, losses and
         Adam stay fp32."""
@@ -102,6 +110,15 @@ class GeneratorStep:
         self.depth_criterion = losses.get_recon_criterion(g_depth_recon_loss_type, g_depth_recon_loss_k)
         self.mask_criterion = losses.get_recon_criterion(g_mask_recon_loss_type, g_mask_recon_loss_k)
         self.mask_loss_type = g_mask_recon_loss_type
+        self.loss_kernel = losses.select_kernel(loss_kernel, 'loss_kernel')
+        self.depth_loss_type = g_depth_recon_loss_type
+        if self.loss_kernel == 'fused':
+            if g_mask_recon_loss_type != 'binary_cross_entropy':
+                raise ValueError(f"loss_kernel='fused' needs g_mask_recon_loss_type='binary_cross_entropy', got "
+                                 f"{g_mask_recon_loss_type!r}: use loss_kernel='composed'")
+            if g_depth_recon_loss_type not in _FUSED_DEPTH_TYPES:
+                raise ValueError(f"loss_kernel='fused' provides the depth terms {tuple(_FUSED_DEPTH_TYPES)}, got "
+                                 f"{g_depth_recon_loss_type!r}: use loss_kernel='composed'")
         self.w_depth, self.w_mask, self.w_beta = g_depth_recon_loss_weight, g_mask_recon_loss_weight, g_mask_beta_loss_weight
         self.beta_param, self.batch_groups = g_mask_beta_loss_param, batch_groups
         self.generator_input_depth, self.depth_noise_std = generator_input_depth, depth_noise_std
@@ -124,6 +141,8 @@ class GeneratorStep:
         out = {}
         dev = z_obj.device
         zero = torch.zeros((), device=dev)
+        if self.loss_kernel == 'fused' and ('depth' in y or 'mask' in y):
+            return self._fused_losses(y, b_out, zero), y
         out['depth_recon'] = losses.reduce_loss(self.depth_criterion(y['depth'], b_out['depth'])) \
             if 'depth' in y else zero
         if 'mask' in y:
@@ -135,6 +154,24 @@ class GeneratorStep:
         out['total'] = (self.w_depth * out['depth_recon'] + self.w_mask * out['mask_recon']
                         + self.w_beta * out['mask_beta']) / self.batch_groups
         return out, y
+
+    def _fused_losses(self, y, b_out, zero):
+        """The three terms from one ops.recon_losses call; a head the photographer does not have leaves its part out."""
+        x = t = z = zt = None
+        base, mined = _FUSED_DEPTH_TYPES[self.depth_loss_type]
+        k = 0
+        if 'depth' in y:
+            x, t = y['depth'], b_out['depth']
+            x, t = x.reshape(-1, *x.shape[-3:]), t.reshape(-1, *t.shape[-3:])
+            k = int(self.depth_criterion.k) if mined else 0                      # read per call: the trainer schedules it
+        if 'mask' in y:
+            z, zt = y['mask_logits'], b_out['mask']
+        terms = ops.recon_losses(x, t, base, k, z, zt, self.beta_param)
+        out = {'depth_recon': terms[0] if x is not None else zero,
+               'mask_recon': terms[1] if z is not None else zero, 'mask_beta': terms[2] if z is not None else zero}
+        out['total'] = (self.w_depth * out['depth_recon'] + self.w_mask * out['mask_recon']
+                        + self.w_beta * out['mask_beta']) / self.batch_groups
+        return out
 
     def run_iteration(self, batch, train=True, is_step=True, zero_grad=True):
         """Returns the dictionary of (detached) loss terms.  Gradients of successive calls with

@@ -128,15 +128,17 @@ def main():
     ap.add_argument('--skip-classes', action='store_true', help='no per-class weight-gradient A/B')
     ap.add_argument('--modes', default='on,off,on', help='WIDE_WGRAD settings timed in turn (on / off)')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--loss-kernel', choices=('composed', 'fused'), default='composed',
+                    help='loss tail: the ATen chain or ops.recon_losses (GeneratorStep(loss_kernel=...))')
     a = ap.parse_args()
     dev = 'cuda:0'
     from latentfusion_amd import ops_train, synth
     from latentfusion_amd.recon import training
     model, _ = synth.build_released_model(device=dev, seed=0)
-    step = training.GeneratorStep(model.sculptor, model.fuser, model.photographer, use_amp=a.amp)
+    step = training.GeneratorStep(model.sculptor, model.fuser, model.photographer, use_amp=a.amp, loss_kernel=a.loss_kernel)
     batch = _batch(model, a.views_in, a.views_out, dev)
     out = {'arch': 'released', 'params_M': sum(q.numel() for q in step.flat.params) / 1e6, 'objects': 1,
-           'views_in': a.views_in, 'views_out': a.views_out, 'amp': a.amp, 'device': torch.cuda.get_device_name(0)}
+           'views_in': a.views_in, 'views_out': a.views_out, 'amp': a.amp, 'loss_kernel': a.loss_kernel, 'device': torch.cuda.get_device_name(0)}
     saved = ops_train.WIDE_WGRAD
     for on in [m == 'on' for m in a.modes.split(',')]:   # on / off / on: the second "on" shows drift within the process
         ops_train.WIDE_WGRAD = on
