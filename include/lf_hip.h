@@ -56,7 +56,8 @@ int lf_device_name(char* buf, int buflen);
  *   CameraToObjectTransform.forward   modules/geometry.py:625-657
  * The sampling grid is never materialised; it is evaluated per voxel from `coef`:
  *   LF_MAP_O2C: g = c0 + c1*a + c2*b + c3*k + c4*a*k + c5*b*k, (a,b,k) = (x/(W-1), y/(H-1),
- *               z/(D-1)), c_j = coef[n][3*j .. 3*j+2] (x,y,z components)        -> 18 floats
+ *               z/(D-1)) -- torch.linspace(0, 1, size), 0 on an axis of size 1 --,
+ *               c_j = coef[n][3*j .. 3*j+2] (x,y,z components)                  -> 18 floats
  *   LF_MAP_C2O: l = (lx,ly,lz,1) with lx = -1 + 2x/(W-1) (lattice in [-1,1]),
  *               gx = (A0.l)/(A3.l), gy = (A1.l)/(A3.l), gz = A2.l, A_r = coef[n][4*r..] -> 16 floats
  * vol_n == 1 broadcasts one volume to all N samples (Photographer.decode, recon/models.py:489-494).

@@ -17,9 +17,10 @@ struct Tap {
 };
 
 // i-th point of torch.linspace(0, 1, size): start + step*i in the first half, end - step*(size-1-i) in the
-// second (ATen's symmetric formula), step = 1/(size-1) computed once on the host
+// second (ATen's symmetric formula), step = 1/(size-1) computed once on the host.  linspace(0, 1, 1) is [0]: the only point of
+// a size-1 axis counts as first half (max(size / 2, 1) is size / 2 for every other size; one scalar instruction)
 __device__ __forceinline__ float lattice01(int i, int size, float step) {
-  return (i < size / 2) ? step * (float)i : 1.f - step * (float)(size - 1 - i);
+  return (i < max(size / 2, 1)) ? step * (float)i : 1.f - step * (float)(size - 1 - i);
 }
 
 

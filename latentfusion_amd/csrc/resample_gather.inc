@@ -58,10 +58,17 @@ __global__ void __launch_bounds__(256) GATHER_KERNEL(resample_fwd)(
                       v111 * w111;
       __builtin_nontemporal_store(r, (f32x4*)(orow + co));     // streamed output: keep L2 for the gathered volume
     } else {
-      const float r = base[(long)(r00 + t.x0) * C + co] * w000 + base[(long)(r00 + t.x1) * C + co] * w001 +
-                      base[(long)(r01 + t.x0) * C + co] * w010 + base[(long)(r01 + t.x1) * C + co] * w011 +
-                      base[(long)(r10 + t.x0) * C + co] * w100 + base[(long)(r10 + t.x1) * C + co] * w101 +
-                      base[(long)(r11 + t.x0) * C + co] * w110 + base[(long)(r11 + t.x1) * C + co] * w111;
+      // the roundings of resample_fwd_c16's fmac chain, spelled out (first product rounded, the other seven fused in corner
+      // order): a 16-channel volume that is not 16-byte aligned lands here and gets the bits of the aligned call; left to the
+      // compiler's contraction the same sum fused the first product and rounded the second
+      float r = base[(long)(r00 + t.x0) * C + co] * w000;
+      r = __builtin_fmaf(base[(long)(r00 + t.x1) * C + co], w001, r);
+      r = __builtin_fmaf(base[(long)(r01 + t.x0) * C + co], w010, r);
+      r = __builtin_fmaf(base[(long)(r01 + t.x1) * C + co], w011, r);
+      r = __builtin_fmaf(base[(long)(r10 + t.x0) * C + co], w100, r);
+      r = __builtin_fmaf(base[(long)(r10 + t.x1) * C + co], w101, r);
+      r = __builtin_fmaf(base[(long)(r11 + t.x0) * C + co], w110, r);
+      r = __builtin_fmaf(base[(long)(r11 + t.x1) * C + co], w111, r);
       orow[co] = r;
     }
   }

@@ -15,11 +15,12 @@ struct SplatTap { int x0, y0, z0, x1, y1, z1; float w[8]; };     // w index = z*
 // What splat_eval and splat_eval_quad both compute, written once AS TEXT: the forms of the splat are bit-identical only while both
 // round the same operations in the same order.  The pieces expand under the `#pragma clang fp contract(off)` of the function that
 // uses them (the pragma is lexical: a helper function, lattice01 of resample.hip included, would be compiled with contraction on).
-// lattice coordinates a, b, k in [0,1] of voxel (x, y, z): torch.linspace(0, 1, S) by ATen's symmetric formula
-#define SPLAT_LATTICE                                                                   \
-  const float a = (x < W / 2) ? st.w * (float)x : 1.f - st.w * (float)(W - 1 - x);      \
-  const float b = (y < H / 2) ? st.h * (float)y : 1.f - st.h * (float)(H - 1 - y);      \
-  const float k = (z < D / 2) ? st.d * (float)z : 1.f - st.d * (float)(D - 1 - z)
+// lattice coordinates a, b, k in [0,1] of voxel (x, y, z): torch.linspace(0, 1, S) by ATen's symmetric formula; the only point of
+// a size-1 axis counts as first half ([0]), as in lattice01 of resample.hip
+#define SPLAT_LATTICE                                                                           \
+  const float a = (x < max(W / 2, 1)) ? st.w * (float)x : 1.f - st.w * (float)(W - 1 - x);      \
+  const float b = (y < max(H / 2, 1)) ? st.h * (float)y : 1.f - st.h * (float)(H - 1 - y);      \
+  const float k = (z < max(D / 2, 1)) ? st.d * (float)z : 1.f - st.d * (float)(D - 1 - z)
 // axis c of the object -> camera map (ak = a * k, bk = b * k)
 #define SPLAT_O2C_ROW(c) (((((cf[c] + cf[3 + (c)] * a) + cf[6 + (c)] * b) + cf[9 + (c)] * k) + cf[12 + (c)] * ak) + cf[15 + (c)] * bk)
 // row r of the camera -> object matrix on the lattice in [-1,1]

@@ -11,6 +11,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from resample_cases import c2o_coefs, o2c_coefs
+
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 O2C, C2O = 0, 1
@@ -19,41 +21,6 @@ O2C, C2O = 0, 1
 def _lib():
     from latentfusion_amd import _lib
     return _lib.lib()
-
-
-def _rot(gen):
-    q = torch.randn(4, generator=gen, dtype=torch.float64)
-    w, x, y, z = (q / q.norm()).tolist()
-    return torch.tensor([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
-                         [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
-                         [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]], dtype=torch.float64)
-
-
-def o2c_coefs(N, gen, scales, persp=0.1, shift=0.1):
-    """(N,20) blocks: g = t + s R (2 (a,b,k) - 1) + perspective-like a*k, b*k terms."""
-    cf = torch.zeros(N, 20, dtype=torch.float64)
-    for n in range(N):
-        R, s = _rot(gen), scales[n % len(scales)]
-        t = (torch.rand(3, generator=gen, dtype=torch.float64) - 0.5) * 2 * shift
-        M = 2 * s * R
-        cf[n, 0:3] = t - s * R.sum(dim=1)
-        cf[n, 3:6], cf[n, 6:9], cf[n, 9:12] = M[:, 0], M[:, 1], M[:, 2]
-        cf[n, 12:15] = (torch.rand(3, generator=gen, dtype=torch.float64) - 0.5) * 2 * persp
-        cf[n, 15:18] = (torch.rand(3, generator=gen, dtype=torch.float64) - 0.5) * 2 * persp
-    return cf
-
-
-def c2o_coefs(N, gen, scales, persp=0.15):
-    cf = torch.zeros(N, 20, dtype=torch.float64)
-    for n in range(N):
-        R, s = _rot(gen), scales[n % len(scales)]
-        A = torch.zeros(4, 4, dtype=torch.float64)
-        A[:3, :3] = s * R
-        A[:3, 3] = (torch.rand(3, generator=gen, dtype=torch.float64) - 0.5) * 0.2
-        A[3, :3] = (torch.rand(3, generator=gen, dtype=torch.float64) - 0.5) * 2 * persp
-        A[3, 3] = 1.0
-        cf[n, :16] = A.reshape(-1)
-    return cf
 
 
 def grid64(cf, kind, D, H, W):
