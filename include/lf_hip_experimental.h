@@ -33,7 +33,10 @@ extern "C" {
  * block: LeakyReLU | PixelNorm with bias and norm_out; data gradient with the previous layer's LeakyReLU' / PixelNorm'; plain data
  * gradient; no amax_out) runs the kernel compiled for that combination, with the registers this frees spent on un-fenced address
  * arithmetic and a resident bias (default), 0 = every call runs the generic kernel, 2 = the compiled forms without that spending
- * (bit-identical results for every value; profiles/wino_forms_ab.json).  Calls that match no combination, and every call under
+ * (bit-identical results for every value; profiles/wino_forms_ab.json).  The compiled forms also exist with a z-staged halo:
+ * the z input transform is applied once per halo point when the halo is written to LDS, not by every overlapping tile that
+ * reads it.  Under 1 a form runs z-staged where that measured faster (profiles/wino_zstage_ab.json); 3 = every compiled form
+ * on the raw-plane halo, 4 = every compiled form z-staged (bit-identical again).  Calls that match no combination, and every call under
  * key 7 = 0, run the generic kernel whatever the value.
  * Returns the previous value or LF_EINVAL. */
 int lf_set_tuning(int key, int value);

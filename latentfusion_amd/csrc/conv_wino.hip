@@ -44,7 +44,10 @@ namespace {
 // OPT (fixed forms only) = 1: the registers a fixed form frees are spent on dropping the two optimiser fences that exist only
 // because hoisting used to spill (hrel[] in fetch_half, the projection's lane index) and on keeping the bias quarter resident
 // across tiles; 0 = fences and per-tile bias read as in the generic kernel (lf_set_tuning(8, 2), for the A/B).
-template <bool SPLIT, int FUSE = 0, bool PACK = false, int FORM = WF_GENERIC, int OPT = 0>
+// ZST (fixed forms only) = 1: z-staged halo.  The halo buffer holds the four z-FREQUENCY planes of the tile instead of its four
+// raw z planes: the z input transform runs once per halo point in halo_commit instead of once per overlapping (y,x) tile in
+// the MFMA phase, which then reads one value where it read two (section 6).  Same operations on the same operands: bit-identical.
+template <bool SPLIT, int FUSE = 0, bool PACK = false, int FORM = WF_GENERIC, int OPT = 0, int ZST = 0>
 __device__ __forceinline__ void conv3d_c16_wino_body(
     const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
     float* __restrict__ y, float* __restrict__ norm_out,
@@ -55,6 +58,7 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
   static_assert(FORM == WF_GENERIC || (!SPLIT && FUSE != 2 && PACK), "fixed forms: the packed all-fp32 kernels only");
   static_assert(OPT == 0 || OPT == 1, "");
   static_assert(FORM != WF_GENERIC || OPT == 0, "the generic kernel stays as it is");
+  static_assert(ZST == 0 || (ZST == 1 && FORM != WF_GENERIC), "z-staged halo: the fixed forms only");
   // ---- 1. form pinning ----
   // a fixed form pins the arguments it is defined by: every test on them below folds at compile time
   constexpr bool HAS_BIAS = FORM == WF_FWD_BLOCK;              // (fixed forms; the generic form tests the pointer)
@@ -95,26 +99,31 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
   // voxel slot p>>2.  (360 slots per half is a multiple of 8, so the swizzle is the same in both halves.)
   // Per piece a lane keeps only its byte offset relative to the half's first voxel; x / y range violations (possible
   // only in the first / last tile of a row or column of tiles) are five flag bits per piece in one register, z range
-  // violations fall outside the buffer descriptor's range on their own and read zeros. ----
+  // violations fall outside the buffer descriptor's range on their own and read zeros.
+  // ZST: a lane owns the SAME (y, x, quarter) in all four z planes, so that it can combine them: piece it = 3 lz' + k is item
+  // i = (fa + 4k) * 64 + lane of the 10 x 18 plane (720 items, k < 3) in z plane lz' of the half; the quarter is (i & 3) ^ s with
+  // the swizzle s of the EVEN planes (a plane is 45 groups of four slots, so bit 1 of s alternates from plane to plane: an odd
+  // plane's copy goes to LDS position i ^ 2, halo_commit). ----
   enum { F_XLO = 1, F_XHI = 2, F_YLO = 4, F_YHI = 8, F_PAD = 16, F_ALL6 = 0x2108421 };
   const int xlim = W - (tiles_x - 1) * TXw + 1, ylim = H - (tiles_y - 1) * TYw + 1;   // first invalid lx / ly in the last tile
   int hrel[NITw];
   unsigned hflags = 0;
 #pragma unroll
   for (int it = 0; it < NITw; ++it) {
-    const int p = (fa + 4 * it) * 64 + lane;
+    const int p = ZST ? (fa + 4 * (it % NITZw)) * 64 + lane : (fa + 4 * it) * 64 + lane;
     const int vs = p >> 2;
     const int row = vs / HXw, rem = vs - row * HXw;
     const int xl = rem / 9, xa = rem - xl * 9;
-    const int lx = 2 * xa + xl, ly = row % HYw, lz = row / HYw;
+    const int lx = 2 * xa + xl, ly = ZST ? row : row % HYw, lz = ZST ? it / NITZw : row / HYw;
     const int sw = (((vs >> 2) & 1) << 1) | ((ly >> 1) & 1);
     const int q = (p & 3) ^ sw;
-    const bool pad = vs >= HALFw;
+    const bool pad = vs >= (ZST ? PLANEw : HALFw);
     hrel[it] = pad ? 0 : ((lz * H + ly) * W + lx) * 64 + q * 16;
     const unsigned f = pad ? F_PAD : ((lx == 0 ? F_XLO : 0) | (lx >= xlim ? F_XHI : 0) | (ly == 0 ? F_YLO : 0) | (ly >= ylim ? F_YHI : 0));
     hflags |= f << (5 * it);
   }
-  const bool last_piece_ok = ((fa + 4 * (NITw - 1)) * 64 + lane) < HALFw * 4;      // piece 22: lanes 0-31; 23: none
+  const bool last_piece_ok = ZST ? ((fa + 4 * (NITZw - 1)) * 64 + lane) < PLANEw * 4      // piece 11: lanes 0-15
+                                 : ((fa + 4 * (NITw - 1)) * 64 + lane) < HALFw * 4;      // piece 22: lanes 0-31; 23: none
 
   // ---- 4. operand and exchange addressing.  B operands: byte offset of (lane's tile, channel quarter) for the 8 slot residues ----
   // (rows dy = 2,3 sit one (y>>1) step further: their quarter swizzle differs in bit 0)
@@ -178,6 +187,9 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
   // (linear: piece * 1 KiB + lane * 16 within a half) just before the tile's last barrier.  (The vector-memory
   // path of a CU sustains only ~16 B/clk on this access pattern and blocks the issuing wave while its queue is
   // full, so halving the bytes shortens the non-MFMA phase of every tile.)
+  // ZST: the upper two planes of the previous tile are still in the lane's registers (hhi), so a slide is a register rename and
+  // no LDS read; halo_commit forms the four z frequencies F0 = d0 - d2, F1 = d1 + d2, F2 = d2 - d1, F3 = d1 - d3 of the lane's
+  // three items -- wino_compute's operations on the values it would have read -- and writes plane a at a * 11,520 B.
   u32x4 hlo[NITw], hhi[NITw];
   auto fetch_half = [&](u32x4 (&dst)[NITw], __amdgpu_buffer_rsrc_t rs, int base, unsigned sel) {
     // (opaque to the optimiser, or base + hrel[] of every branch is hoisted out of the tile loop into registers)
@@ -207,13 +219,32 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
     if (by == tiles_y - 1) sel |= F_YHI * F_ALL6;
     if (slide) {
 #pragma unroll
-      for (int it = 0; it < NITw; ++it) hlo[it] = *(const u32x4*)(buf + HALFBw + (fa + 4 * it) * 1024 + lane * 16);
+      for (int it = 0; it < NITw; ++it) {
+        if constexpr (ZST) hlo[it] = hhi[it];
+        else hlo[it] = *(const u32x4*)(buf + HALFBw + (fa + 4 * it) * 1024 + lane * 16);
+      }
     } else {
       fetch_half(hlo, rs, base, sel);
     }
     fetch_half(hhi, rs, base + 2 * H * W * 64, sel);
   };
   auto halo_commit = [&]() {
+    if constexpr (ZST) {
+#pragma unroll
+      for (int k = 0; k < NITZw; ++k) {
+        const f32x4 d0 = __builtin_bit_cast(f32x4, hlo[k]), d1 = __builtin_bit_cast(f32x4, hlo[NITZw + k]);
+        const f32x4 d2 = __builtin_bit_cast(f32x4, hhi[k]), d3 = __builtin_bit_cast(f32x4, hhi[NITZw + k]);
+        const f32x4 f0 = pk_sub(d0, d2), f1 = d1 + d2, f2 = pk_sub(d2, d1), f3 = pk_sub(d1, d3);
+        const int o = (fa + 4 * k) * 1024 + lane * 16;
+        if (k < NITZw - 1 || last_piece_ok) {
+          *(f32x4*)(buf + o) = f0;
+          *(f32x4*)(buf + PLANEBw + (o ^ 32)) = f1;
+          *(f32x4*)(buf + 2 * PLANEBw + o) = f2;
+          *(f32x4*)(buf + 3 * PLANEBw + (o ^ 32)) = f3;
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int it = 0; it < NITw; ++it) {
       unsigned char* dst = buf + (fa + 4 * it) * 1024 + lane * 16;
@@ -250,10 +281,10 @@ __device__ __forceinline__ void conv3d_c16_wino_body(
     TS(0);
     unsigned* const tsp = ((WINO_ABL & 16) && blockIdx.x == 11 && lane == 0) ? (unsigned*)norm_out + ((t - t_begin) * 4 + fa) * 16 : nullptr;
     switch (fa) {
-      case 0: wino_compute<0, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
-      case 1: wino_compute<1, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
-      case 2: wino_compute<2, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
-      default: wino_compute<3, SPLIT, FUSE != 0, PACK>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      case 0: wino_compute<0, SPLIT, FUSE != 0, PACK, ZST != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      case 1: wino_compute<1, SPLIT, FUSE != 0, PACK, ZST != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      case 2: wino_compute<2, SPLIT, FUSE != 0, PACK, ZST != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
+      default: wino_compute<3, SPLIT, FUSE != 0, PACK, ZST != 0>(buf, off, wt, whi, wlo, in_scale, px + fa * 8192, pw, tsp); break;
     }
     TS(1);
     lds_barrier();                                  // every wave is done reading the halo; all partials are in LDS
@@ -479,11 +510,36 @@ __global__ void __launch_bounds__(256, 2) conv3d_c16_wino_projfwd_form_kernel(
                                                  slope, eps, prev_y, prev_norm, prev_flags, nullptr, nullptr, pj);
 }
 
+// The fixed forms on the z-staged halo (ZST = 1, OPT = 1; kernels of their own, so that the ones above keep their names).
+template <int FORM, int OPT>
+__global__ void __launch_bounds__(256, 2) conv3d_c16_wino_zst_form_kernel(
+    const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
+    float* __restrict__ y, float* __restrict__ norm_out, int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z,
+    int ntiles, float he, unsigned flags, float slope, float eps, const float* __restrict__ prev_y,
+    const float* __restrict__ prev_norm, unsigned prev_flags, float* __restrict__ amax_out) {
+  conv3d_c16_wino_body<false, 0, true, FORM, OPT, 1>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags,
+                                                    slope, eps, prev_y, prev_norm, prev_flags, nullptr, amax_out);
+}
+
+template <int FORM, int OPT>
+__global__ void __launch_bounds__(256, 2) conv3d_c16_wino_projfwd_zst_form_kernel(
+    const float* __restrict__ x, const float* __restrict__ upack, const float* __restrict__ bias,
+    float* __restrict__ y, float* __restrict__ norm_out, int N, int D, int H, int W, int tiles_x, int tiles_y, int tiles_z,
+    int ntiles, float he, unsigned flags, float slope, float eps, const float* __restrict__ prev_y,
+    const float* __restrict__ prev_norm, unsigned prev_flags, WinoProj pj) {
+  conv3d_c16_wino_body<false, 1, true, FORM, OPT, 1>(x, upack, bias, y, norm_out, N, D, H, W, tiles_x, tiles_y, tiles_z, ntiles, he, flags,
+                                                    slope, eps, prev_y, prev_norm, prev_flags, nullptr, nullptr, pj);
+}
+
 // lf_set_tuning key 7: 1 = packed transforms next to the MFMAs (wino_rows_packed; default), 0 = the scalar form.  Bit-identical.
 int g_wino_pack = 1;
 // lf_set_tuning key 8: 1 = calls that match a fixed form run it, OPT = 1 (default), 0 = every call runs the generic kernel,
-// 2 = the fixed forms with OPT = 0.  Bit-identical.
+// 2 = the fixed forms with OPT = 0, 3 = the fixed forms, OPT = 1, all on the raw-plane halo (the staging before ZST),
+// 4 = all on the z-staged halo.  Bit-identical.  Under 1 a form runs z-staged where that measured faster (wino_zst_default).
 int g_wino_forms = 1;
+// index: WF_FWD_BLOCK, WF_DGRAD_PREV, WF_DGRAD_PLAIN, the forward block with the projection (profiles/wino_zstage_ab.json)
+constexpr bool wino_zst_default[4] = {true, false, false, true};
+bool wino_zst(int idx) { return g_wino_forms == 4 || (g_wino_forms == 1 && wino_zst_default[idx]); }
 
 // The fixed form a call may run, from ALL the arguments a form pins: a call that differs in any of them (add mode, amax_out,
 // LeakyReLU alone, flags without a bias, ...) is WF_GENERIC.
@@ -536,7 +592,7 @@ int lf_internal_wino_set_pack(int v) {
 }
 int lf_internal_wino_set_forms(int v) {
   const int prev = g_wino_forms;
-  if (v >= 0 && v <= 2) g_wino_forms = v;
+  if (v >= 0 && v <= 4) g_wino_forms = v;
   return prev;
 }
 
@@ -551,7 +607,10 @@ extern "C" int lf_conv3d_c16_wino(const float* x, const float* upack, const floa
 #define LF_WINO_FORM(F, O) \
   launch_wino<conv3d_c16_wino_form_kernel<F, O>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y, prev_norm, \
                                                  prev_flags, stream, amax_out)
-#define LF_WINO_OPTS(F) (g_wino_forms == 2 ? LF_WINO_FORM(F, 0) : LF_WINO_FORM(F, 1))
+#define LF_WINO_ZST(F) \
+  launch_wino<conv3d_c16_wino_zst_form_kernel<F, 1>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y, prev_norm, \
+                                                     prev_flags, stream, amax_out)
+#define LF_WINO_OPTS(F) (g_wino_forms == 2 ? LF_WINO_FORM(F, 0) : wino_zst(F - WF_FWD_BLOCK) ? LF_WINO_ZST(F) : LF_WINO_FORM(F, 1))
   switch (wino_form_of(bias, norm_out, flags, prev_y, prev_norm, prev_flags, amax_out)) {
     case WF_FWD_BLOCK: return LF_WINO_OPTS(WF_FWD_BLOCK);
     case WF_DGRAD_PREV: return LF_WINO_OPTS(WF_DGRAD_PREV);
@@ -559,6 +618,7 @@ extern "C" int lf_conv3d_c16_wino(const float* x, const float* upack, const floa
     default: break;
   }
 #undef LF_WINO_OPTS
+#undef LF_WINO_ZST
 #undef LF_WINO_FORM
   return g_wino_pack ? launch_wino<conv3d_c16_wino_kernel<true>>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, prev_y,
                                                                   prev_norm, prev_flags, stream, amax_out)
@@ -594,6 +654,9 @@ extern "C" int lf_conv3d_c16_wino_projfwd(const float* x, const float* upack, co
 #define LF_WINO_FORM(O) \
   launch_wino<conv3d_c16_wino_projfwd_form_kernel<WF_FWD_BLOCK, O>, true>(x, upack, bias, y, norm_out, N, D, H, W, he, flags, slope, eps, \
                                                                           nullptr, nullptr, 0u, stream, pj)
+    if (g_wino_forms != 2 && wino_zst(3))
+      return launch_wino<conv3d_c16_wino_projfwd_zst_form_kernel<WF_FWD_BLOCK, 1>, true>(x, upack, bias, y, norm_out, N, D, H, W, he, flags,
+                                                                                         slope, eps, nullptr, nullptr, 0u, stream, pj);
     return g_wino_forms == 2 ? LF_WINO_FORM(0) : LF_WINO_FORM(1);
 #undef LF_WINO_FORM
   }

@@ -82,7 +82,7 @@ __device__ __forceinline__ float lf_lrelu(float v, float slope) { return v > 0.f
 // A/B switches that live in other translation units (lf_set_tuning dispatches to them)
 int lf_internal_ring_bf16_set_wgs(int v);                         // conv_split.hip: workgroups per CU of lf_conv3d_c16_ring_bf16 (2 or 3)
 int lf_internal_wino_set_pack(int v);                            // conv_wino.hip: packed (1) / scalar (0) transforms next to the MFMAs
-int lf_internal_wino_set_forms(int v);                           // conv_wino.hip: fixed epilogue forms (1; 2 = without the register spending) / generic (0)
+int lf_internal_wino_set_forms(int v);                           // conv_wino.hip: fixed epilogue forms (1; 2 = without the register spending; 3 / 4 = raw-plane / z-staged halo) / generic (0)
 int lf_internal_fused_set_cfg(int v);                             // wino_fused.hip: workgroup shape of the fused GEMM, -1 = by shape
 int lf_internal_splat_set_variant(int v);                        // splat.hip: form of the deterministic splat, 1..4
 int lf_internal_splat_set_chunk_cap(int v);                      // splat.hip: samples per pass of the binned splat at most, 0 = by memory only

@@ -605,7 +605,7 @@ extern "C" int lf_set_tuning(int key, int value) {
   if (key == 6) return lf_internal_splat_set_chunk_cap(value);      // binned splat: samples per pass at most, 0 = by memory only
   if (key == 3) return lf_internal_fused_set_cfg(value);            // fused wide-conv GEMM: workgroup shape 0..3, -1 = by shape
   if (key == 7) return lf_internal_wino_set_pack(value);            // fp32 Winograd 16-channel kernels: 1 = packed transforms (default), 0 = scalar
-  if (key == 8) return lf_internal_wino_set_forms(value);           // same kernels: 1 = compile-time epilogue forms (default), 0 = generic, 2 = forms, freed registers unspent
+  if (key == 8) return lf_internal_wino_set_forms(value);           // same kernels: 1 = compile-time epilogue forms (default), 0 = generic, 2 = forms, freed registers unspent, 3 / 4 = forms on the raw-plane / z-staged halo
   if (key == 5) return lf_internal_ring_bf16_set_wgs(value);        // bf16 ring convolution: resident workgroups per CU
   if (key == 2) {
     const int prev = g_bwd_coef_variant;

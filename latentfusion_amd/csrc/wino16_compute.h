@@ -84,7 +84,9 @@ __device__ __forceinline__ void wino_rows_packed(f32x4 (&vx)[4][4], const float 
 // PACK (all-fp32 path only): the y input transform that feeds the B operands and the x / y output transforms on the MFMA
 // results as packed asm (rules R1 - R3 at pk_sub), same operations in the same order and association as the scalar
 // form, which stays selectable (lf_set_tuning key 7) for the bit-identity test and the A/B.
-template <int A, bool SPLIT, bool OFFX = false, bool PACK = false>
+// ZST (z-staged fixed forms): the halo buffer holds z-FREQUENCY planes (halo_commit combined them once per halo point), so
+// plane A is read as it is: one ds_read_b128 per value instead of two and no z combination here.
+template <int A, bool SPLIT, bool OFFX = false, bool PACK = false, bool ZST = false>
 __device__ __forceinline__ void wino_compute(const unsigned char* __restrict__ buf, const int (&off)[8][2],
                                               const float (&wt)[64], const f16x4 (&whi)[16], const f16x4 (&wlo)[16],
                                               float in_scale, unsigned char* __restrict__ pdst,
@@ -99,29 +101,43 @@ __device__ __forceinline__ void wino_compute(const unsigned char* __restrict__ b
     // the halo is read half a row (2 z planes x 2 x positions = 4 ds_read_b128) ahead of the half row being
     // transformed; the fences stop the scheduler from folding this back into load-wait-use pairs, which
     // exposes the full LDS latency sixteen times per group
-    f32x4 raw[2][4];
-    auto load_half = [&](int hh, f32x4 (&r)[4]) {
+    f32x4 raw[2][ZST ? 2 : 4];
+    auto load_half = [&](int hh, f32x4 (&r)[ZST ? 2 : 4]) {
       const int dy = hh >> 1;
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
         const int dx = (hh & 1) * 2 + e;
         const int ca = ((DZ0 * 10 + 4 * g + dy) * 18 + (dx & 1) * 9 + (dx >> 1));
-        const int cb = ((DZ1 * 10 + 4 * g + dy) * 18 + (dx & 1) * 9 + (dx >> 1));
-        if constexpr ((WINO_ABL & 64) != 0) {                  // ablation: ONE plane read per value, no z combination
-          r[2 * e] = *(const f32x4*)(buf + off[ca & 7][dy >> 1] + ca * 64);
-          r[2 * e + 1] = r[2 * e];
-        } else if constexpr (OFFX) {
-          int oa = off[ca & 7][0], ob = off[cb & 7][0];
-          if (dy >> 1) {
-            asm volatile("" : "+v"(oa), "+v"(ob));               // (opaque: or the xor-ed copies are hoisted back into registers)
-            oa ^= 16;
-            ob ^= 16;
+        if constexpr (ZST) {                                   // the frequency index takes the place of z in the slot
+          const int cf = ca + (A - DZ0) * 180;
+          if constexpr (OFFX) {
+            int oa = off[cf & 7][0];
+            if (dy >> 1) {
+              asm volatile("" : "+v"(oa));
+              oa ^= 16;
+            }
+            r[e] = *(const f32x4*)(buf + oa + cf * 64);
+          } else {
+            r[e] = *(const f32x4*)(buf + off[cf & 7][dy >> 1] + cf * 64);
           }
-          r[2 * e] = *(const f32x4*)(buf + oa + ca * 64);
-          r[2 * e + 1] = *(const f32x4*)(buf + ob + cb * 64);
         } else {
-          r[2 * e] = *(const f32x4*)(buf + off[ca & 7][dy >> 1] + ca * 64);
-          r[2 * e + 1] = *(const f32x4*)(buf + off[cb & 7][dy >> 1] + cb * 64);
+          const int cb = ((DZ1 * 10 + 4 * g + dy) * 18 + (dx & 1) * 9 + (dx >> 1));
+          if constexpr ((WINO_ABL & 64) != 0) {                  // ablation: ONE plane read per value, no z combination
+            r[2 * e] = *(const f32x4*)(buf + off[ca & 7][dy >> 1] + ca * 64);
+            r[2 * e + 1] = r[2 * e];
+          } else if constexpr (OFFX) {
+            int oa = off[ca & 7][0], ob = off[cb & 7][0];
+            if (dy >> 1) {
+              asm volatile("" : "+v"(oa), "+v"(ob));               // (opaque: or the xor-ed copies are hoisted back into registers)
+              oa ^= 16;
+              ob ^= 16;
+            }
+            r[2 * e] = *(const f32x4*)(buf + oa + ca * 64);
+            r[2 * e + 1] = *(const f32x4*)(buf + ob + cb * 64);
+          } else {
+            r[2 * e] = *(const f32x4*)(buf + off[ca & 7][dy >> 1] + ca * 64);
+            r[2 * e + 1] = *(const f32x4*)(buf + off[cb & 7][dy >> 1] + cb * 64);
+          }
         }
       }
     };
@@ -135,9 +151,13 @@ __device__ __forceinline__ void wino_compute(const unsigned char* __restrict__ b
       const int dy = hh >> 1;
 #pragma unroll
       for (int e = 0; e < 2; ++e) {
-        const f32x4 va = raw[hh & 1][2 * e], vb = raw[hh & 1][2 * e + 1];
-        if constexpr ((WINO_ABL & 64) != 0) d[(hh & 1) * 2 + e] = va;
-        else d[(hh & 1) * 2 + e] = (A == 1) ? (va + vb) : pk_sub(va, vb);
+        if constexpr (ZST) {
+          d[(hh & 1) * 2 + e] = raw[hh & 1][e];
+        } else {
+          const f32x4 va = raw[hh & 1][2 * e], vb = raw[hh & 1][2 * e + 1];
+          if constexpr ((WINO_ABL & 64) != 0) d[(hh & 1) * 2 + e] = va;
+          else d[(hh & 1) * 2 + e] = (A == 1) ? (va + vb) : pk_sub(va, vb);
+        }
       }
       if (hh & 1) {
         vx[dy][0] = pk_sub(d[0], d[2]);

@@ -55,6 +55,11 @@ constexpr int HALFBw = HALFw * 64;                              // 23,040 B
 constexpr int NSLOTw = (HALFw * 4 + 63) / 64;                   // 23 pieces of 1 KiB per half (the last one half full)
 constexpr int NITw = (NSLOTw + 3) / 4;                          // 6 pieces per wave and half
 constexpr int BUFw = 2 * HALFBw;                                // 46,080 B halo buffer
+// z-staged forms (ZST, conv_wino.hip section 6): the same buffer as four z-FREQUENCY planes of 180 voxel slots
+constexpr int PLANEw = HYw * HXw;                               // 180 voxels: one plane of the halo
+constexpr int PLANEBw = PLANEw * 64;                            // 11,520 B
+constexpr int NITZw = ((PLANEw * 4 + 63) / 64 + 3) / 4;         // 12 pieces of 1 KiB per plane (the last a quarter full): 3 per wave
+static_assert(4 * PLANEBw == BUFw && 2 * NITZw == NITw, "the staged forms reuse the halo buffer and the fetch registers");
 constexpr int PXw = 4 * 8192;                                   // 32,768 B partial-exchange region
 constexpr int LDSw = BUFw + PXw + 1024;                         // + 1 KiB DMA scratch = 79,872 B (two workgroups per CU)
 

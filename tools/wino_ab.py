@@ -12,8 +12,10 @@ forward with the factor projection riding on it (lf_conv3d_c16_wino_projfwd).  A
 too (the parent commit's against this one's), and `path@0` / `path@1` selects the scalar / packed transforms of that
 library through lf_set_tuning(7, .) before each of its calls; `path@8=0` / `path@8=1` (any `key=value`, comma-separated) the
 generic kernels / the compile-time epilogue forms.  The plain data gradient (no previous layer) is timed as well.
+One warm-up round is run and discarded.  `--json FILE` (first argument) also writes every round's time per variant and call, with median and min-to-max spread.
 Ablation variants are builds with -DWINO_ABL=bits; every bit is described at the top of csrc/wino16_math.h."""
 import ctypes
+import json
 import os
 import sys
 
@@ -23,6 +25,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from latentfusion_amd import ops  # noqa: E402
 from latentfusion_amd._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM  # noqa: E402
 
+JSON = None
+if sys.argv[1:2] == ['--json']:
+    JSON = sys.argv[2]
+    del sys.argv[1:3]
 P = ctypes.c_void_p
 S, N, ROUNDS = 128, 8, 7
 g = torch.Generator().manual_seed(0)
@@ -103,7 +109,7 @@ tf = [[] for _ in fs]
 tb = [[] for _ in fs]
 tp = [[] for _ in fs]
 tg = [[] for _ in fs]
-for r in range(ROUNDS):
+for r in range(ROUNDS + 1):
     for i, f in enumerate(fs):
         y, nrm, go, bw = outs[i]
         for which, acc in ((0, tf), (1, tb), (2, tg)):
@@ -127,7 +133,21 @@ for r in range(ROUNDS):
         e1.record()
         torch.cuda.synchronize()
         tp[i].append(e0.elapsed_time(e1) / 5)
+for acc in (tf, tb, tp, tg):                                  # round 0 is the warm-up (clocks still ramping): discarded
+    for i in range(len(fs)):
+        del acc[i][0]
 for i, p in enumerate(sys.argv[1:]):
     a, c, d, e = sorted(tf[i]), sorted(tb[i]), sorted(tp[i]), sorted(tg[i])
     print(f'{p}: fwd median {a[len(a) // 2]:.4f} ms (min {a[0]:.4f}), bwd+prev median {c[len(c) // 2]:.4f} ms (min {c[0]:.4f}), '
           f'bwd plain median {e[len(e) // 2]:.4f} ms (min {e[0]:.4f}), projfwd median {d[len(d) // 2]:.4f} ms (min {d[0]:.4f})')
+if JSON:
+    rec = {'shape': [N, 16, S, S, S], 'rounds': ROUNDS, 'launches_per_round': 5, 'unit': 'ms', 'variants': {}}
+    for i, p in enumerate(sys.argv[1:]):
+        rec['variants'][p] = {}
+        for name, acc in (('fwd', tf), ('dgrad_prev', tb), ('dgrad_plain', tg), ('projfwd', tp)):
+            v = sorted(acc[i])
+            rec['variants'][p][name] = {'median': round(v[len(v) // 2], 4), 'spread': round(v[-1] - v[0], 4),
+                                       'rounds': [round(t, 4) for t in acc[i]]}
+    with open(JSON, 'w') as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write('\n')
