@@ -25,14 +25,10 @@ import math
 import torch
 
 from . import _lib, ops
-from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_O2C, check
+from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_O2C
 
 NCOEF = 24
 NPAR = 10
-
-
-def _s():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class _CameraCoefs(torch.autograd.Function):
@@ -40,22 +36,20 @@ class _CameraCoefs(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, params, intr, cube, z_span, h, w):
-        L = _lib.lib()
         n = params.shape[0]
         coefs = torch.empty(n, NCOEF, device=params.device, dtype=torch.float32)
         jac = torch.empty(n, NCOEF, NPAR, device=params.device, dtype=torch.float32)
-        check(L.lf_camera_coefs(params.contiguous().data_ptr(), intr.contiguous().data_ptr(), cube, z_span, h, w,
-                                coefs.data_ptr(), jac.data_ptr(), n, _s()), 'lf_camera_coefs')
+        ops.launch('lf_camera_coefs', params.contiguous().data_ptr(), intr.contiguous().data_ptr(), cube, z_span, h, w,
+                   coefs.data_ptr(), jac.data_ptr(), n)
         ctx.save_for_backward(jac)
         return coefs
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         jac, = ctx.saved_tensors
         n = jac.shape[0]
         gp = torch.empty(n, NPAR, device=jac.device, dtype=torch.float32)
-        check(L.lf_camera_coefs_bwd(g.contiguous().data_ptr(), jac.data_ptr(), gp.data_ptr(), n, _s()), 'lf_camera_coefs_bwd')
+        ops.launch('lf_camera_coefs_bwd', g.contiguous().data_ptr(), jac.data_ptr(), gp.data_ptr(), n)
         return gp, None, None, None, None, None
 
 
@@ -101,9 +95,8 @@ def _pose_loss_fwd(lg, cf, tdepth, tmask, weights, H, W, mode='logits', tn=None,
     losses = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
     gsums = torch.empty(N, 8, device=lg.device, dtype=torch.float32)
     out = () if mode == 'masked' else (gsums.data_ptr(),)
-    check(getattr(_lib.lib(), name)(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), weights.data_ptr(),
-                                    sums.data_ptr(), losses.data_ptr(), *out, scratch.data_ptr(), scratch.numel() * 4,
-                                    N, *(tn or ()), h, w, H, W, _s()), name)
+    ops.launch(name, lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), weights.data_ptr(), sums.data_ptr(),
+               losses.data_ptr(), *out, scratch.data_ptr(), scratch.numel() * 4, N, *(tn or ()), h, w, H, W)
     return losses, gsums, scratch
 
 
@@ -111,9 +104,8 @@ def _pose_loss_bwd(lg, cf, tdepth, tmask, gsums, glogits, gcoefs, scratch, H, W,
     """THE launch of the loss backward: d/d(logits) and coefficient entries 18..23 (0..17 of gcoefs are not written)."""
     name = _pose_loss_entry('bwd', mode, tn)
     N, _, h, w = lg.shape
-    check(getattr(_lib.lib(), name)(lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), gsums.data_ptr(),
-                                    glogits.data_ptr(), gcoefs.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
-                                    N, *(tn or ()), h, w, H, W, _s()), name)
+    ops.launch(name, lg.data_ptr(), cf.data_ptr(), tdepth.data_ptr(), tmask.data_ptr(), gsums.data_ptr(), glogits.data_ptr(),
+               gcoefs.data_ptr(), scratch.data_ptr(), scratch.numel() * 4, N, *(tn or ()), h, w, H, W)
 
 
 class _PoseLoss(torch.autograd.Function):
@@ -621,18 +613,15 @@ class RenderLoopEngine:
     def _occlusion_fwd(self, zc, flags):
         """zc: output of the last camera block (n,16,S,S,S).  Returns (zs = zc * softmax_D(occlusion logits), saved); zs is None
         before a factor projection, which scales its operand itself (lf_conv1x1_fwd_scaled): the scaled volume is never written."""
-        L = _lib.lib()
-        o, s, dev = self.occ, _s(), self.dev
+        o, dev = self.occ, self.dev
         n, _, D, H, W = zc.shape
         P = H * W
         ta, t16 = ops.empty_cl(zc.shape, dev), torch.empty(n, 1, D, H, W, device=dev, dtype=torch.float32)
-        with ops._timed('occ_input_fwd'):
-            check(L.lf_occ_input_fwd(zc.data_ptr(), o['wi'].data_ptr(), o['bi'].data_ptr(), ta.data_ptr(), t16.data_ptr(), n, D, P,
-                                     ops.SLOPE, s), 'lf_occ_input_fwd')
+        ops.launch('lf_occ_input_fwd', zc.data_ptr(), o['wi'].data_ptr(), o['bi'].data_ptr(), ta.data_ptr(), t16.data_ptr(), n, D,
+                   P, ops.SLOPE, tag='occ_input_fwd')
         b2, he2, pa, _pat, w27 = o['first']
         pre = ops.empty_cl(zc.shape, dev)
-        with ops._timed('occ_conv17_fwd'):
-            check(L.lf_occ_conv17_fwd(t16.data_ptr(), w27.data_ptr(), pre.data_ptr(), n, D, H, W, s), 'lf_occ_conv17_fwd')
+        ops.launch('lf_occ_conv17_fwd', t16.data_ptr(), w27.data_ptr(), pre.data_ptr(), n, D, H, W, tag='occ_conv17_fwd')
         y, nrm = ops.conv3d_c16_wino(ta, pa, b2, he2, flags, prev=(pre, None, _lib.LF_EPI_ADD), out=pre)
         ys, ns = [y], [nrm]
         for (b, he, pk, _pkt) in o['rest']:
@@ -643,26 +632,23 @@ class RenderLoopEngine:
         wocc = torch.empty(n, 1, D, H, W, device=dev, dtype=torch.float32)
         if D <= 256:
             # (round 6) output block + softmax over the depth column in one pass over the last activation: no logits volume
-            with ops._timed('column_softmax_head'):
-                check(L.lf_column_softmax_head_fwd(ys[-1].data_ptr(), o['head_w16'].data_ptr(), hb.data_ptr() if hb is not None else None,
-                                                   hhe, wocc.data_ptr(), None, n, D, P, s), 'lf_column_softmax_head_fwd')
+            ops.launch('lf_column_softmax_head_fwd', ys[-1].data_ptr(), o['head_w16'].data_ptr(),
+                       hb.data_ptr() if hb is not None else None, hhe, wocc.data_ptr(), None, n, D, P, tag='column_softmax_head')
         else:
             logits = torch.empty(n, 1, D, H, W, device=dev, dtype=torch.float32)
             ops._conv1x1_raw(ys[-1], hpk, hb, n, D * P, 16, 1, D * P * 16, 0, 1, logits, hhe, 0)
-            with ops._timed('column_softmax'):
-                check(L.lf_column_softmax_fwd(logits.data_ptr(), wocc.data_ptr(), None, n, D, P, s), 'lf_column_softmax_fwd')
+            ops.launch('lf_column_softmax_fwd', logits.data_ptr(), wocc.data_ptr(), None, n, D, P, tag='column_softmax')
         if self.proj is not None:
             return None, (ta, t16, ys, ns, wocc)
         zs = ops.empty_cl(zc.shape, dev)
-        check(L.lf_column_scale_fwd(zc.data_ptr(), wocc.data_ptr(), zs.data_ptr(), n * D * P, 16, s), 'lf_column_scale_fwd')
+        ops.launch('lf_column_scale_fwd', zc.data_ptr(), wocc.data_ptr(), zs.data_ptr(), n * D * P, 16)
         return zs, (ta, t16, ys, ns, wocc)
 
     def _occlusion_bwd(self, g_zs, zc, saved, flags, prev, proj_bwd=None):
         """d/d(zs) -> d/d(zc): the scaling, the softmax, the output block, the four convolutions (each data-gradient launch folds
         in the LeakyReLU' / PixelNorm' of the layer it lands on) and the input block, plus the direct term of the scaling.
         prev = (zc, norm, flags) of the camera-block layer that produced zc: its epilogue backward is applied on the way out."""
-        L = _lib.lib()
-        o, s, dev = self.occ, _s(), self.dev
+        o, dev = self.occ, self.dev
         ta, t16, ys, ns, wocc = saved
         n, _, D, H, W = zc.shape
         P = H * W
@@ -671,23 +657,21 @@ class RenderLoopEngine:
         if proj_bwd is not None and D <= 256:
             # (round 6) the weights' gradient sum_c zc * g_zs, g_zs recomputed from the projection's 2-D gradient, and the softmax
             # backward over each pixel's depth column in one launch: one read of zc; neither g_zs nor gw exist as volumes
-            with ops._timed('occ_weight_grad_softmax_bwd'):
-                check(L.lf_occ_weight_grad_softmax_bwd(zc.data_ptr(), proj_bwd[0].data_ptr(), proj_bwd[1].data_ptr(), proj_bwd[2], wocc.data_ptr(),
-                                                       gl.data_ptr(), n, D, P, s), 'lf_occ_weight_grad_softmax_bwd')
+            ops.launch('lf_occ_weight_grad_softmax_bwd', zc.data_ptr(), proj_bwd[0].data_ptr(), proj_bwd[1].data_ptr(), proj_bwd[2],
+                       wocc.data_ptr(), gl.data_ptr(), n, D, P, tag='occ_weight_grad_softmax_bwd')
         else:
             gw = torch.empty_like(wocc)
             if proj_bwd is not None:
-                check(L.lf_occ_weight_grad(zc.data_ptr(), proj_bwd[0].data_ptr(), proj_bwd[1].data_ptr(), proj_bwd[2], gw.data_ptr(), n, D, P, s),
-                      'lf_occ_weight_grad')
+                ops.launch('lf_occ_weight_grad', zc.data_ptr(), proj_bwd[0].data_ptr(), proj_bwd[1].data_ptr(), proj_bwd[2],
+                           gw.data_ptr(), n, D, P)
             else:
-                check(L.lf_column_scale_bwd(g_zs.data_ptr(), zc.data_ptr(), wocc.data_ptr(), None, gw.data_ptr(), n * D * P, 16, s),
-                      'lf_column_scale_bwd')
-            check(L.lf_column_softmax_bwd(wocc.data_ptr(), gw.data_ptr(), None, gl.data_ptr(), n, D, P, s), 'lf_column_softmax_bwd')
+                ops.launch('lf_column_scale_bwd', g_zs.data_ptr(), zc.data_ptr(), wocc.data_ptr(), None, gw.data_ptr(), n * D * P,
+                           16)
+            ops.launch('lf_column_softmax_bwd', wocc.data_ptr(), gw.data_ptr(), None, gl.data_ptr(), n, D, P)
         hhe = o['head'][1]
         g = ops.empty_cl(zc.shape, dev)
-        with ops._timed('occ_head_bwd'):
-            check(L.lf_occ_head_bwd(gl.data_ptr(), o['head_w16'].data_ptr(), hhe, ys[-1].data_ptr(), ns[-1].data_ptr(), flags, ops.SLOPE,
-                                    g.data_ptr(), n * D * P, s), 'lf_occ_head_bwd')
+        ops.launch('lf_occ_head_bwd', gl.data_ptr(), o['head_w16'].data_ptr(), hhe, ys[-1].data_ptr(), ns[-1].data_ptr(), flags,
+                   ops.SLOPE, g.data_ptr(), n * D * P, tag='occ_head_bwd')
         for i in range(len(o['rest']) - 1, -1, -1):
             _b, he, _pk, pkt = o['rest'][i]
             g = ops.conv3d_c16_wino(g, pkt, None, he, 0, prev=(ys[i], ns[i], flags))[0]
@@ -699,21 +683,17 @@ class RenderLoopEngine:
         # persistent Winograd workgroups hold every CU, the side kernel took 1.33 ms instead of 0.38 and stretched its neighbour:
         # 63.4 against 64.4 it/s)
         gta = ops.conv3d_c16_wino(g, pat, None, he2, 0, prev=(ta, None, LF_EPI_LRELU))[0]
-        with ops._timed('occ_conv17_bwd'):
-            check(L.lf_occ_conv17_bwd(g.data_ptr(), t16.data_ptr(), w27.data_ptr(), gp16.data_ptr(), n, D, H, W, ops.SLOPE, s),
-                  'lf_occ_conv17_bwd')
+        ops.launch('lf_occ_conv17_bwd', g.data_ptr(), t16.data_ptr(), w27.data_ptr(), gp16.data_ptr(), n, D, H, W, ops.SLOPE,
+                   tag='occ_conv17_bwd')
         gz = ops.empty_cl(zc.shape, dev)
         if proj_bwd is not None:
             gp2d, ppack_t, phe = proj_bwd
-            with ops._timed('occ_input_bwd'):
-                check(L.lf_occ_input_bwd_proj(gta.data_ptr(), gp16.data_ptr(), o['wi'].data_ptr(), gp2d.data_ptr(), ppack_t.data_ptr(), phe,
-                                              wocc.data_ptr(), gz.data_ptr(), n, D, P, ops.SLOPE, zc.data_ptr(), prev[1].data_ptr(), prev[2], s),
-                      'lf_occ_input_bwd_proj')
+            ops.launch('lf_occ_input_bwd_proj', gta.data_ptr(), gp16.data_ptr(), o['wi'].data_ptr(), gp2d.data_ptr(),
+                       ppack_t.data_ptr(), phe, wocc.data_ptr(), gz.data_ptr(), n, D, P, ops.SLOPE, zc.data_ptr(),
+                       prev[1].data_ptr(), prev[2], tag='occ_input_bwd')
             return gz
-        with ops._timed('occ_input_bwd'):
-            check(L.lf_occ_input_bwd(gta.data_ptr(), None, gp16.data_ptr(), o['wi'].data_ptr(), g_zs.data_ptr(),
-                                     wocc.data_ptr(), gz.data_ptr(), n * D * P, ops.SLOPE, zc.data_ptr(), prev[1].data_ptr(), prev[2], s),
-                  'lf_occ_input_bwd')
+        ops.launch('lf_occ_input_bwd', gta.data_ptr(), None, gp16.data_ptr(), o['wi'].data_ptr(), g_zs.data_ptr(), wocc.data_ptr(),
+                   gz.data_ptr(), n * D * P, ops.SLOPE, zc.data_ptr(), prev[1].data_ptr(), prev[2], tag='occ_input_bwd')
         return gz
 
     # ---- one evaluation, stage by stage ----
@@ -789,13 +769,12 @@ class RenderLoopEngine:
 
     def _coefficients(self, params, intr, z_span, n):
         """(N,10) camera parameters -> coefficient blocks, their Jacobian, and the resampler's padded O2C block."""
-        L = _lib.lib()
         params = params.contiguous()
         intr = intr.contiguous()
         coefs = torch.empty(n, NCOEF, device=self.dev, dtype=torch.float32)
         jac = torch.empty(n, NCOEF, NPAR, device=self.dev, dtype=torch.float32)
-        check(L.lf_camera_coefs(params.data_ptr(), intr.data_ptr(), float(self.cube), z_span, self.crop,
-                                self.crop, coefs.data_ptr(), jac.data_ptr(), n, _s()), 'lf_camera_coefs')
+        ops.launch('lf_camera_coefs', params.data_ptr(), intr.data_ptr(), float(self.cube), z_span, self.crop, self.crop,
+                   coefs.data_ptr(), jac.data_ptr(), n)
         # O2C coefficient block padded to the resampler's stride (LF_MAP_COEFS = 20)
         # (the object->camera map reads 18 of the 20 floats of a block; the two pad floats are never read: no fill launch)
         cf20 = torch.empty(n, 20, device=self.dev, dtype=torch.float32)
@@ -803,12 +782,10 @@ class RenderLoopEngine:
         return coefs, jac, cf20
 
     def _resample(self, cf20, n):
-        L = _lib.lib()
         S = self.S
         x0 = ops.empty_cl((n, self.C, S, S, S), self.dev)
-        with ops._timed('resample_fwd'):
-            check(L.lf_resample3d_fwd(self.z.data_ptr(), 1, cf20.data_ptr(), LF_MAP_O2C, x0.data_ptr(), n, S, S, S, self.C, _s()),
-                  'lf_resample3d_fwd')
+        ops.launch('lf_resample3d_fwd', self.z.data_ptr(), 1, cf20.data_ptr(), LF_MAP_O2C, x0.data_ptr(), n, S, S, S, self.C,
+                   tag='resample_fwd')
         return x0
 
     def _blocks_fwd(self, x0, flags, proj_gemm):
@@ -851,7 +828,6 @@ class RenderLoopEngine:
     def _factor_fwd(self, act, rode, flags, need_grad, proj_gemm, n):
         """The plain factor projection: ridden along in the last block's launch, the row-major GEMM of a ranking call on wide
         blocks (self.proj_kernel: the library's, or lf_rows_gemm_epi with the epilogue in its store), or its own launch."""
-        L = _lib.lib()
         pw, pb, phe, ppack, _ppack_t = self.proj
         cout, S, Cl = pw.shape[0], self.S, self.Cl
         if rode:
@@ -869,7 +845,7 @@ class RenderLoopEngine:
                     rows = torch.mm(x2, self.proj_rows_t).mul_(phe)
                 torch.nn.functional.leaky_relu_(rows, ops.SLOPE)
                 pnorm = torch.empty(n * S * S, device=self.dev, dtype=torch.float32)
-                check(L.lf_pixelnorm_fwd(rows.data_ptr(), rows.data_ptr(), pnorm.data_ptr(), n * S * S, cout, ops.PN_EPS, _s()), 'lf_pixelnorm_fwd')
+                ops.launch('lf_pixelnorm_fwd', rows.data_ptr(), rows.data_ptr(), pnorm.data_ptr(), n * S * S, cout, ops.PN_EPS)
             zp = rows.view(n, S, S, cout).permute(0, 3, 1, 2)                # channels-last (n, cout, S, S)
         else:
             zp = ops.empty_cl((n, cout, S, S), self.dev)
@@ -879,7 +855,6 @@ class RenderLoopEngine:
         return _Tail(zp, pnorm, leaf, leaf, None)
 
     def _factor_bwd(self, tail, gp, g_leaf, acts, norms, flags, n):
-        L = _lib.lib()
         pw, _pb, phe, _ppack, ppack_t = self.proj
         cout, S, Cl, nconv = pw.shape[0], self.S, self.Cl, self.nconv
         gp = self._proj_pre_grad(tail, gp, g_leaf, flags)
@@ -891,11 +866,9 @@ class RenderLoopEngine:
         if self.plan.folds_prev:
             # every data-gradient kernel also applies the LeakyReLU'/PixelNorm' of the layer feeding it,
             # so no separate epilogue-backward pass touches the (N,16,S,S,S) volumes
-            with ops._timed('factor_project_bwd'):
-                check(L.lf_conv1x1_bwd_data(gp.data_ptr(), ppack_t.data_ptr(), g.data_ptr(), n, S * S, cout, S * Cl,
-                                            S * S * S * Cl, Cl, Cl, S * S * Cl, phe, acts[nconv].data_ptr(),
-                                            norms[nconv - 1].data_ptr(), flags, ops.SLOPE,
-                                            bounds[nconv].data_ptr() if bounds is not None else None, _s()), 'lf_conv1x1_bwd_data')
+            ops.launch('lf_conv1x1_bwd_data', gp.data_ptr(), ppack_t.data_ptr(), g.data_ptr(), n, S * S, cout, S * Cl,
+                       S * S * S * Cl, Cl, Cl, S * S * Cl, phe, acts[nconv].data_ptr(), norms[nconv - 1].data_ptr(), flags,
+                       ops.SLOPE, bounds[nconv].data_ptr() if bounds is not None else None, tag='factor_project_bwd')
         else:
             ops._conv1x1_raw(gp, ppack_t, None, n, S * S, cout, 1, S * S * cout, 0, S * Cl, g, phe, 0,
                              yaddr=(S * S * S * Cl, Cl, Cl, S * S * Cl))
@@ -993,16 +966,15 @@ class RenderLoopEngine:
         epilogue backward (a fused latent term joins before it, _proj_pre_grad)."""
         # each launch folds in the LeakyReLU' / PixelNorm' of the activation it lands on (whole records of 16 / 32 / 64 channels;
         # otherwise a separate pass); dacts[0] is the projected latent itself
-        L = _lib.lib()
         hw = self.heads[0]
         cin_h = hw.shape[1]
         hh, ww = dacts[-1].shape[-2:]
         g2 = ops.empty_cl((n, cin_h, hh, ww), self.dev)
         fuse_h = cin_h == 16
-        check(L.lf_conv1x1_bwd_data(glogits.data_ptr(), self.heads_pack[2].data_ptr(), g2.data_ptr(), n, hh * ww, hw.shape[0],
-                                    cin_h, hh * ww * cin_h, cin_h, cin_h if fuse_h else (1 << 30), 0, self.heads_pack[0],
-                                    dacts[-1].data_ptr() if fuse_h else None, dnorms[-1].data_ptr() if fuse_h else None,
-                                    flags if fuse_h else 0, ops.SLOPE, None, _s()), 'lf_conv1x1_bwd_data')
+        ops.launch('lf_conv1x1_bwd_data', glogits.data_ptr(), self.heads_pack[2].data_ptr(), g2.data_ptr(), n, hh * ww, hw.shape[0],
+                   cin_h, hh * ww * cin_h, cin_h, cin_h if fuse_h else (1 << 30), 0, self.heads_pack[0],
+                   dacts[-1].data_ptr() if fuse_h else None, dnorms[-1].data_ptr() if fuse_h else None, flags if fuse_h else 0,
+                   ops.SLOPE, None)
         if not fuse_h:
             g2 = ops._epilogue_bwd(g2, dacts[-1], dnorms[-1], flags)
         for i in range(len(self.dec) - 1, -1, -1):
@@ -1060,20 +1032,18 @@ class RenderLoopEngine:
         S = self.S
         nbytes = L.lf_resample3d_bwd_coef_scratch_bytes(n, S, S, S)
         scratch = torch.empty(nbytes // 4 + 1, device=self.dev, dtype=torch.float32)
-        with ops._timed('resample_bwd_coef'):
-            check(L.lf_resample3d_bwd_coef(g.data_ptr(), self.z.data_ptr(), 1, cf20.data_ptr(), gcoef18.data_ptr(),
-                                           scratch.data_ptr(), scratch.numel() * 4, n, S, S, S, self.C, _s()), 'lf_resample3d_bwd_coef')
+        ops.launch('lf_resample3d_bwd_coef', g.data_ptr(), self.z.data_ptr(), 1, cf20.data_ptr(), gcoef18.data_ptr(),
+                   scratch.data_ptr(), scratch.numel() * 4, n, S, S, S, self.C, tag='resample_bwd_coef')
 
     def _finish_backward(self, g, g_cf, cf20, jac, n, grad_scale, losses):
         """d/d(O2C output) -> coefficient gradient -> camera parameters (lf_resample3d_bwd_coef, lf_camera_coefs_bwd)."""
-        L = _lib.lib()
-        dev, s = self.dev, _s()
+        dev = self.dev
         gcoef18 = torch.empty(n, 18, device=dev, dtype=torch.float32)
         self._bwd_coef(g, cf20, gcoef18, n)
         gcoefs = g_cf.contiguous()
         gcoefs[:, :18] = gcoef18
         gparams = torch.empty(n, NPAR, device=dev, dtype=torch.float32)
-        check(L.lf_camera_coefs_bwd(gcoefs.data_ptr(), jac.data_ptr(), gparams.data_ptr(), n, s), 'lf_camera_coefs_bwd')
+        ops.launch('lf_camera_coefs_bwd', gcoefs.data_ptr(), jac.data_ptr(), gparams.data_ptr(), n)
         if grad_scale != 1.0:
             gparams *= grad_scale
         return losses, gparams

@@ -27,8 +27,7 @@ table lookup, csrc/resample_gather.inc); per row they are bit-identical to the o
 import torch
 
 from . import _lib, ops
-from ._lib import check
-from .engine import LF_MAP_O2C, RenderLoopEngine, _PoseLoss, _pose_loss_bwd, _pose_loss_fwd, _s
+from .engine import LF_MAP_O2C, RenderLoopEngine, _PoseLoss, _pose_loss_bwd, _pose_loss_fwd
 
 
 def distinct_volumes(z_objs):
@@ -206,13 +205,11 @@ class MultiTargetEngine(RenderLoopEngine):
     def _resample(self, cf20, n):
         if self.zs is None:
             return RenderLoopEngine._resample(self, cf20, n)
-        L = _lib.lib()
         S = self.S
         x0 = ops.empty_cl((n, self.C, S, S, S), self.dev)
         table = self._table(n)
-        with ops._timed('resample_fwd'):
-            check(L.lf_resample3d_fwd_indexed(self.zs.data_ptr(), self.zs.shape[0], table.data_ptr(), cf20.data_ptr(), LF_MAP_O2C,
-                                              x0.data_ptr(), n, S, S, S, self.C, _s()), 'lf_resample3d_fwd_indexed')
+        ops.launch('lf_resample3d_fwd_indexed', self.zs.data_ptr(), self.zs.shape[0], table.data_ptr(), cf20.data_ptr(), LF_MAP_O2C,
+                   x0.data_ptr(), n, S, S, S, self.C, tag='resample_fwd')
         return x0
 
     def _bwd_coef(self, g, cf20, gcoef18, n):
@@ -225,6 +222,5 @@ class MultiTargetEngine(RenderLoopEngine):
             name, vol = 'lf_resample3d_bwd_coef_indexed', (self.zs.data_ptr(), self.zs.shape[0], self._table(n).data_ptr())
         nbytes = getattr(L, name + '_scratch_bytes')(n, self._n, S, S, S)
         scratch = torch.empty(nbytes // 4 + 1, device=self.dev, dtype=torch.float32)
-        with ops._timed('resample_bwd_coef'):
-            check(getattr(L, name)(g.data_ptr(), *vol, cf20.data_ptr(), gcoef18.data_ptr(), scratch.data_ptr(), scratch.numel() * 4,
-                                   n, S, S, S, self.C, self._n, _s()), name)
+        ops.launch(name, g.data_ptr(), *vol, cf20.data_ptr(), gcoef18.data_ptr(), scratch.data_ptr(), scratch.numel() * 4, n, S, S,
+                   S, self.C, self._n, tag='resample_bwd_coef')

@@ -8,13 +8,13 @@ A/B reference paths, kept for tools/ and the tests that pin them -- nothing on a
 
 The second half holds RenderLoopEngineX, the engine with the measured-and-rejected variants.  Its kernel family for conv_mode
 'winograd_f16x3' joins the engine's camera-block plan through select_camera_blocks here, which the class names in `_select_blocks`."""
-import math  # noqa: F401
+import math
 
 import torch
 
 from . import _lib, ops
-from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_C2O, LF_MAP_COEFS, LF_MAP_O2C, check  # noqa: F401
-from .ops import (PN_EPS, SLOPE, _WINO_G, _ptr, _stream, _timed, empty_cl)  # noqa: F401
+from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_C2O, LF_MAP_COEFS, LF_MAP_O2C  # noqa: F401
+from .ops import (PN_EPS, SLOPE, _WINO_G, _norm_buf, _prev, _timed, empty_cl, launch)  # noqa: F401
 
 
 def pack_conv3d_c16_bf16(weight, transpose=False):
@@ -29,14 +29,10 @@ def pack_conv3d_c16_bf16(weight, transpose=False):
 
 def conv3d_c16_bf16(x, wpack, bias, he, flags, round_out):
     """Launch lf_conv3d_c16_bf16 on a channels-last (N,16,D,H,W) tensor."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     y = empty_cl((N, 16, D, H, W), x.device)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    with _timed('conv3d_c16_bf16'):
-        check(L.lf_conv3d_c16_bf16(_ptr(x), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y),
-                                   _ptr(norm) if norm is not None else None, N, D, H, W, he, flags, SLOPE, PN_EPS, round_out,
-                                   _stream()), 'lf_conv3d_c16_bf16')
+    norm = _norm_buf(flags, N * D * H * W, x.device)
+    launch('lf_conv3d_c16_bf16', x, wpack, bias, y, norm, N, D, H, W, he, flags, SLOPE, PN_EPS, round_out, tag='conv3d_c16_bf16')
     return y, norm
 
 
@@ -57,18 +53,12 @@ def pack_conv3d_c16_wino_split(weight, transpose=False):
 
 def conv3d_c16_wino_split(x, upack, bias, he, flags, prev=None, amax_in=None, amax_out=None):
     """Launch lf_conv3d_c16_wino_split on a channels-last (N,16,D,H,W) tensor."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     y = empty_cl((N, 16, D, H, W), x.device)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    py, pn, pf = (prev[0], prev[1], prev[2]) if prev is not None else (None, None, 0)
-    with _timed('conv3d_c16_wino_split'):
-        check(L.lf_conv3d_c16_wino_split(_ptr(x), _ptr(upack), _ptr(bias) if bias is not None else None, _ptr(y),
-                                         _ptr(norm) if norm is not None else None, N, D, H, W, he, flags, SLOPE, PN_EPS,
-                                         _ptr(py) if py is not None else None, _ptr(pn) if pn is not None else None, pf,
-                                         _ptr(amax_in) if amax_in is not None else None,
-                                         _ptr(amax_out) if amax_out is not None else None, _stream()),
-              'lf_conv3d_c16_wino_split')
+    norm = _norm_buf(flags, N * D * H * W, x.device)
+    py, pn, pf = _prev(prev)
+    launch('lf_conv3d_c16_wino_split', x, upack, bias, y, norm, N, D, H, W, he, flags, SLOPE, PN_EPS, py, pn, pf, amax_in, amax_out,
+           tag='conv3d_c16_wino_split')
     return y, norm
 
 
@@ -77,15 +67,11 @@ def conv3d_c16_wino_projbwd(gp, proj_wtA, proj_he, act, act_norm, act_flags, upa
     launch (the gradient volume between them is formed on chip).  gp: (N,16,H,W) channels-last gradient w.r.t. the
     projection's pre-activation; act / act_norm: the block's saved output; prev: (y, norm, flags) of the layer feeding the
     block.  Returns the (N,16,D,H,W) gradient w.r.t. that layer's pre-activation (or the block's input if prev is None)."""
-    L = _lib.lib()
     N, _, D, H, W = act.shape
     g = empty_cl((N, 16, D, H, W), act.device)
-    py, pn, pf = (prev[0], prev[1], prev[2]) if prev is not None else (None, None, 0)
-    with _timed('conv3d_c16_wino_projbwd'):
-        check(L.lf_conv3d_c16_wino_projbwd(_ptr(gp), _ptr(proj_wtA), proj_he, _ptr(act),
-                                           _ptr(act_norm) if act_norm is not None else None, act_flags, _ptr(upack_t), _ptr(g),
-                                           N, D, H, W, he, SLOPE, _ptr(py) if py is not None else None,
-                                           _ptr(pn) if pn is not None else None, pf, _stream()), 'lf_conv3d_c16_wino_projbwd')
+    py, pn, pf = _prev(prev)
+    launch('lf_conv3d_c16_wino_projbwd', gp, proj_wtA, proj_he, act, act_norm, act_flags, upack_t, g, N, D, H, W, he, SLOPE, py, pn,
+           pf, tag='conv3d_c16_wino_projbwd')
     return g
 
 
@@ -104,53 +90,24 @@ def pack_conv3d_wino_gemm(weight, transpose=False):
 
 
 def conv3d_wino_gemm(x, U, bias, he, flags):
-    """Wide 3-D conv as Winograd F(2x2x2,3x3x3): input transform (HIP) -> 64 batched fp32 GEMMs (rocBLAS via
+    """Wide 2-D / 3-D conv as Winograd F(2x2(x2),3x3(x3)): input transform (HIP) -> 16 / 64 batched fp32 GEMMs (rocBLAS via
     torch.bmm) -> output transform with the fused epilogue (HIP).  Returns (y, norm or None).  (A/B reference of the
     fused path: ops.WIDE_CONV_MODE = 'bmm'.)"""
-    L = _lib.lib()
-    if x.dim() == 4:
-        return _conv2d_wino_gemm(x, U, bias, he, flags)
-    N, cin, D, H, W = x.shape
+    dims = x.dim() - 2
+    N, cin, sp = x.shape[0], x.shape[1], tuple(x.shape[2:])
     cout = U.shape[2]
-    T = L.lf_wino3d_tiles(N, D, H, W)
-    V = torch.empty(64, T, cin, device=x.device, dtype=torch.float32)
-    with _timed('wino3d_input'):
-        check(L.lf_wino3d_input_transform(_ptr(x), _ptr(V), N, D, H, W, cin, _stream()), 'lf_wino3d_input_transform')
-    with _timed('wino3d_gemm'):
+    T = getattr(_lib.lib(), f'lf_wino{dims}d_tiles')(N, *sp)
+    V = torch.empty(4 ** dims, T, cin, device=x.device, dtype=torch.float32)
+    launch(f'lf_wino{dims}d_input_transform', x, V, N, *sp, cin, tag=f'wino{dims}d_input')
+    with _timed(f'wino{dims}d_gemm'):
         M = torch.bmm(V, U)
     del V
-    y = empty_cl((N, cout, D, H, W), x.device)
-    pn = bool(flags & LF_EPI_PIXELNORM)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if pn else None
-    with _timed('wino3d_output'):
-        check(L.lf_wino3d_output_transform(_ptr(M), _ptr(bias) if bias is not None else None, _ptr(y),
-                                           _ptr(norm) if norm is not None else None, N, D, H, W, cout, he, flags, SLOPE,
-                                           PN_EPS, _stream()), 'lf_wino3d_output_transform')
-    if pn and cout > 256:
-        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * D * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
-    return y, norm
-
-
-def _conv2d_wino_gemm(x, U, bias, he, flags):
-    L = _lib.lib()
-    N, cin, H, W = x.shape
-    cout = U.shape[2]
-    T = L.lf_wino2d_tiles(N, H, W)
-    V = torch.empty(16, T, cin, device=x.device, dtype=torch.float32)
-    with _timed('wino2d_input'):
-        check(L.lf_wino2d_input_transform(_ptr(x), _ptr(V), N, H, W, cin, _stream()), 'lf_wino2d_input_transform')
-    with _timed('wino2d_gemm'):
-        M = torch.bmm(V, U)
-    del V
-    y = empty_cl((N, cout, H, W), x.device)
-    pn = bool(flags & LF_EPI_PIXELNORM)
-    norm = torch.empty(N * H * W, device=x.device, dtype=torch.float32) if pn else None
-    with _timed('wino2d_output'):
-        check(L.lf_wino2d_output_transform(_ptr(M), _ptr(bias) if bias is not None else None, _ptr(y),
-                                           _ptr(norm) if norm is not None else None, N, H, W, cout, he, flags, SLOPE, PN_EPS,
-                                           _stream()), 'lf_wino2d_output_transform')
-    if pn and cout > 256:
-        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+    y = empty_cl((N, cout) + sp, x.device)
+    rows = N * math.prod(sp)
+    norm = _norm_buf(flags, rows, x.device)
+    launch(f'lf_wino{dims}d_output_transform', M, bias, y, norm, N, *sp, cout, he, flags, SLOPE, PN_EPS, tag=f'wino{dims}d_output')
+    if norm is not None and cout > 256:
+        launch('lf_pixelnorm_fwd', y, y, norm, rows, cout, PN_EPS)
     return y, norm
 
 

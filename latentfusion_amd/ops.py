@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_C2O, LF_MAP_COEFS, LF_MAP_O2C, check
+from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_C2O, LF_MAP_COEFS, LF_MAP_O2C
 
 SLOPE = 0.2
 PN_EPS = 1e-8
@@ -65,12 +65,11 @@ class autocast:
 
 def round_bf16(t):
     """bf16(t) in an fp32 container of the same layout (lf_round_bf16)."""
-    L = _lib.lib()
     _req(t, 'tensor')
     src = t if (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last)
                 or (t.dim() == 5 and t.is_contiguous(memory_format=torch.channels_last_3d))) else t.contiguous()
     out = torch.empty_like(src, memory_format=torch.preserve_format)
-    check(L.lf_round_bf16(_ptr(src), _ptr(out), src.numel(), _stream()), 'lf_round_bf16')
+    launch('lf_round_bf16', src, out, src.numel())
     return out
 
 
@@ -159,6 +158,51 @@ def _ptr(t, scratch=False):
     if _lib.BYTE_LOG is not None:
         _lib.note_bytes(t, scratch)
     return t.data_ptr()
+
+
+_Tensor = torch.Tensor
+_LAUNCH_PLAN = {}          # entry point -> (arity with the stream, positions of its c_void_p arguments)
+
+
+def launch(name, *args, tag=None, detail=''):
+    """THE call of a library entry point `int lf_x(..., void* stream)` on the current stream: `args` are its C arguments
+    without the stream.  At a void* position a tensor goes as its data_ptr() and is counted in the byte accounting as _ptr
+    counts it (once per argument); None is NULL; anything else goes as it is, so an int there is an uncounted pointer (scratch
+    buffers, pointer arithmetic).  A wrong argument count is a TypeError (ctypes would take surplus arguments silently), a
+    non-zero return code an LFHipError naming the entry point.  tag: run inside _timed(tag, detail)."""
+    plan = _LAUNCH_PLAN.get(name)
+    if plan is None:
+        res, argtypes = _lib.SIGNATURES.get(name) or _lib.EXPERIMENTAL_SIGNATURES[name]
+        assert res is _lib.c_int and argtypes[-1] is _lib.P, f'{name} is not a launch: int lf_x(..., void* stream)'
+        plan = _LAUNCH_PLAN[name] = (len(argtypes), tuple(i for i, t in enumerate(argtypes[:-1]) if t is _lib.P))
+    if len(args) + 1 != plan[0]:
+        raise TypeError(f'{name} takes {plan[0] - 1} arguments before the stream, got {len(args)}')
+    a = list(args)
+    for i in plan[1]:
+        t = a[i]
+        if t is not None and isinstance(t, _Tensor):
+            a[i] = t.data_ptr()
+    if _lib.BYTE_LOG is not None:                                 # (one branch per launch, not per pointer)
+        for i in plan[1]:
+            if isinstance(args[i], _Tensor):
+                _lib.note_bytes(args[i])
+    fn = getattr(_lib.lib(), name)
+    if tag is None or KERNEL_TIMER is None:                       # (no timer: not even the _timed object)
+        rc = fn(*a, _stream())
+    else:
+        with _timed(tag, detail):
+            rc = fn(*a, _stream())
+    _lib.check(rc, name)
+
+
+def _prev(prev):
+    """(y, norm, flags) of the layer whose epilogue backward a launch folds in -> its prev_y, prev_norm, prev_flags arguments."""
+    return (prev[0], prev[1], prev[2]) if prev is not None else (None, None, 0)
+
+
+def _norm_buf(flags, rows, device):
+    """The per-row norms a PixelNorm epilogue saves for its backward (None without one)."""
+    return torch.empty(rows, device=device, dtype=torch.float32) if flags & LF_EPI_PIXELNORM else None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -281,17 +325,12 @@ def pack_conv3d_c16_split(weight, transpose=False):
 
 def conv3d_c16_split(x, wsplit, bias, he, flags, prev=None, amax_in=None, amax_out=None, want_norm=True):
     """Launch lf_conv3d_c16_split on a channels-last (N,16,D,H,W) tensor."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     y = empty_cl((N, 16, D, H, W), x.device)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    py, pn, pf = (prev[0], prev[1], prev[2]) if prev is not None else (None, None, 0)
-    with _timed('conv3d_c16_split'):
-        check(L.lf_conv3d_c16_split(_ptr(x), _ptr(wsplit), _ptr(bias) if bias is not None else None, _ptr(y),
-                                    _ptr(norm) if norm is not None else None, N, D, H, W, he, flags, SLOPE, PN_EPS,
-                                    _ptr(py) if py is not None else None, _ptr(pn) if pn is not None else None, pf,
-                                    _ptr(amax_in) if amax_in is not None else None,
-                                    _ptr(amax_out) if amax_out is not None else None, _stream()), 'lf_conv3d_c16_split')
+    norm = _norm_buf(flags, N * D * H * W, x.device)
+    py, pn, pf = _prev(prev)
+    launch('lf_conv3d_c16_split', x, wsplit, bias, y, norm, N, D, H, W, he, flags, SLOPE, PN_EPS, py, pn, pf, amax_in, amax_out,
+           tag='conv3d_c16_split')
     return y, norm
 
 
@@ -308,14 +347,11 @@ def pack_conv3d_c16_ring_bf16(weight, transpose=False):
 
 def conv3d_c16_ring_bf16(x, wpack, bias, he, flags, round_out, addend=None):
     """Launch lf_conv3d_c16_ring_bf16 on a channels-last (N,16,D,H,W) tensor (un-rounded input: the kernel rounds)."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     y = empty_cl((N, 16, D, H, W), x.device)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    with _timed('conv3d_c16_ring_bf16', f"{'add' if addend is not None else 'fwd'}:{N}:io0"):
-        check(L.lf_conv3d_c16_ring_bf16(_ptr(x), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y),
-                                        _ptr(norm) if norm is not None else None, N, D, H, W, he, flags, SLOPE, PN_EPS,
-                                        _ptr(addend) if addend is not None else None, round_out, _stream()), 'lf_conv3d_c16_ring_bf16')
+    norm = _norm_buf(flags, N * D * H * W, x.device)
+    launch('lf_conv3d_c16_ring_bf16', x, wpack, bias, y, norm, N, D, H, W, he, flags, SLOPE, PN_EPS, addend, round_out,
+           tag='conv3d_c16_ring_bf16', detail=f"{'add' if addend is not None else 'fwd'}:{N}:io0")
     return y, norm
 
 
@@ -328,17 +364,13 @@ def conv3d_c16_ring_bf16_io(x, wpack, bias, he, flags, round_out, addend=None, o
     """lf_conv3d_c16_ring_bf16_io: the bf16 ring convolution on volumes stored as fp32 OR bf16 channels-last records (the
     dtype of `x` / `addend` / `out` says which).  `out`: write into this (N,16,D,H,W) channels-last tensor (e.g. a slice of a
     gradient block) instead of a new one.  Returns (y, norm)."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     y = out if out is not None else empty_cl16((N, 16, D, H, W), x.device, out_bf16)
     io = ((_lib.LF_IO_IN_BF16 if x.dtype == torch.bfloat16 else 0) | (_lib.LF_IO_OUT_BF16 if y.dtype == torch.bfloat16 else 0)
           | (_lib.LF_IO_ADDEND_BF16 if (addend is not None and addend.dtype == torch.bfloat16) else 0))
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    with _timed('conv3d_c16_ring_bf16', f"{'add' if addend is not None else 'fwd'}:{N}:io{io}"):
-        check(L.lf_conv3d_c16_ring_bf16_io(_ptr(x), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y),
-                                           _ptr(norm) if norm is not None else None, N, D, H, W, he, flags, SLOPE, PN_EPS,
-                                           _ptr(addend) if addend is not None else None, round_out, io, _stream()),
-              'lf_conv3d_c16_ring_bf16_io')
+    norm = _norm_buf(flags, N * D * H * W, x.device)
+    launch('lf_conv3d_c16_ring_bf16_io', x, wpack, bias, y, norm, N, D, H, W, he, flags, SLOPE, PN_EPS, addend, round_out, io,
+           tag='conv3d_c16_ring_bf16', detail=f"{'add' if addend is not None else 'fwd'}:{N}:io{io}")
     return y, norm
 
 
@@ -361,16 +393,12 @@ def pack_conv3d_c16_wino(weight, transpose=False):
 
 def conv3d_c16_wino(x, upack, bias, he, flags, prev=None, amax_out=None, out=None):
     """Launch lf_conv3d_c16_wino on a channels-last (N,16,D,H,W) tensor (`out`: write into this tensor)."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     y = out if out is not None else empty_cl((N, 16, D, H, W), x.device)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    py, pn, pf = (prev[0], prev[1], prev[2]) if prev is not None else (None, None, 0)
-    with _timed('conv3d_c16_wino'):
-        check(L.lf_conv3d_c16_wino(_ptr(x), _ptr(upack), _ptr(bias) if bias is not None else None, _ptr(y),
-                                   _ptr(norm) if norm is not None else None, N, D, H, W, he, flags, SLOPE, PN_EPS,
-                                   _ptr(py) if py is not None else None, _ptr(pn) if pn is not None else None, pf,
-                                   _ptr(amax_out) if amax_out is not None else None, _stream()), 'lf_conv3d_c16_wino')
+    norm = _norm_buf(flags, N * D * H * W, x.device)
+    py, pn, pf = _prev(prev)
+    launch('lf_conv3d_c16_wino', x, upack, bias, y, norm, N, D, H, W, he, flags, SLOPE, PN_EPS, py, pn, pf, amax_out,
+           tag='conv3d_c16_wino')
     return y, norm
 
 
@@ -393,18 +421,13 @@ def pack_wino_proj(wp_dmajor, transpose=False):
 def conv3d_c16_wino_projfwd(x, upack, bias, he, flags, proj_wA, proj_bias, proj_he, proj_flags):
     """lf_conv3d_c16_wino_projfwd: the last camera block's convolution AND the factor projection behind it in one launch.
     Returns (y, norm, zp (N,16,H,W) channels-last, pnorm)."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     y = empty_cl((N, 16, D, H, W), x.device)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
+    norm = _norm_buf(flags, N * D * H * W, x.device)
     zp = empty_cl((N, 16, H, W), x.device)
-    pnorm = torch.empty(N * H * W, device=x.device, dtype=torch.float32) if (proj_flags & LF_EPI_PIXELNORM) else None
-    with _timed('conv3d_c16_wino_projfwd'):
-        check(L.lf_conv3d_c16_wino_projfwd(_ptr(x), _ptr(upack), _ptr(bias) if bias is not None else None, _ptr(y),
-                                           _ptr(norm) if norm is not None else None, N, D, H, W, he, flags, SLOPE, PN_EPS,
-                                           _ptr(proj_wA), _ptr(proj_bias) if proj_bias is not None else None, _ptr(zp),
-                                           _ptr(pnorm) if pnorm is not None else None, proj_he, proj_flags, _stream()),
-              'lf_conv3d_c16_wino_projfwd')
+    pnorm = _norm_buf(proj_flags, N * H * W, x.device)
+    launch('lf_conv3d_c16_wino_projfwd', x, upack, bias, y, norm, N, D, H, W, he, flags, SLOPE, PN_EPS, proj_wA, proj_bias, zp,
+           pnorm, proj_he, proj_flags, tag='conv3d_c16_wino_projfwd')
     return y, norm, zp, pnorm
 
 
@@ -437,32 +460,28 @@ def pack_conv_wino_fused(weight, transpose=False):
     return out.contiguous()
 
 
-def _wino_conv_fused(x, cout, flags, depth_inner, v_shape, v_dtype, transform, scratch_bytes, gemm):
+def _wino_conv_fused(x, cout, flags, depth_inner, v_shape, v_dtype, transform, nscr, gemm):
     """The launch sequence of the fused wide convolutions, written once: V, input transform, y (or the depth-inner y), scratch,
     GEMM, PixelNorm as a pass over the (small) output.  transform = (tag, f(V)) and gemm = (tag, f(V, y, scratch pointer or
-    None, scratch bytes, GEMM flags)) make their library call, each under _timed(tag); scratch_bytes() is the GEMM's query.
-    Returns (y, norm or None)."""
-    L = _lib.lib()
+    None, GEMM flags)); each f returns the (entry point, arguments...) of its launch, which runs under _timed(tag); nscr: the
+    GEMM's scratch bytes (its own query).  Returns (y, norm or None)."""
     N, sp = x.shape[0], tuple(x.shape[2:])
     V = torch.empty(v_shape, device=x.device, dtype=v_dtype)
-    with _timed(transform[0]):
-        transform[1](V)
+    launch(*transform[1](V), tag=transform[0])
     if depth_inner:
         assert len(sp) == 3
         y = torch.empty((N, sp[1], sp[2], sp[0], cout), device=x.device, dtype=torch.float32)
     else:
         y = empty_cl((N, cout) + sp, x.device)
-    nscr = scratch_bytes()
     scr = torch.empty(nscr // 4, device=x.device, dtype=torch.float32) if nscr else None
-    with _timed(gemm[0]):
-        gemm[1](V, y, _ptr(scr, True) if scr is not None else None, nscr,
-                (flags & LF_EPI_LRELU) | (_lib.LF_OUT_DEPTH_INNER if depth_inner else 0))
+    launch(*gemm[1](V, y, scr.data_ptr() if scr is not None else None,
+                    (flags & LF_EPI_LRELU) | (_lib.LF_OUT_DEPTH_INNER if depth_inner else 0)), tag=gemm[0])
     del V
     norm = None
     if flags & LF_EPI_PIXELNORM:
         rows = N * math.prod(sp)
         norm = torch.empty(rows, device=x.device, dtype=torch.float32)
-        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), rows, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+        launch('lf_pixelnorm_fwd', y, y, norm, rows, cout, PN_EPS)
     return y, norm
 
 
@@ -484,28 +503,21 @@ def conv_wino_fused(x, U2, cout, bias, he, flags, depth_inner=False, part_n=None
             raise ValueError(f'part_n = {part_n} does not divide the {N} rows')
     if dims == 3:
         T = L.lf_wino3d_tiles(N, D, H, W)
-        transform = ('wino3d_input', lambda V: check(L.lf_wino3d_input_transform(_ptr(x), _ptr(V), N, D, H, W, cin, _stream()),
-                                                     'lf_wino3d_input_transform'))
+        transform = ('wino3d_input', lambda V: ('lf_wino3d_input_transform', x, V, N, D, H, W, cin))
     else:
         T = L.lf_wino2d_tiles(N, H, W)
-        transform = ('wino2d_input', lambda V: check(L.lf_wino2d_input_transform(_ptr(x), _ptr(V), N, H, W, cin, _stream()),
-                                                     'lf_wino2d_input_transform'))
+        transform = ('wino2d_input', lambda V: ('lf_wino2d_input_transform', x, V, N, H, W, cin))
+    if part_n is None:                                        # the scratch follows the query of the entry point that is called
+        name, part = 'lf_wino_fused_gemm', ()
+        nscr = L.lf_wino_fused_scratch_bytes(dims, N, D, H, W, cout)
+    else:
+        name, part = 'lf_wino_fused_gemm_part', (part_n,)
+        nscr = L.lf_wino_fused_scratch_bytes_part(dims, N, D, H, W, cout, part_n)
 
-    def gemm(V, y, scr, nscr, gflags):
-        b = _ptr(bias) if bias is not None else None
-        if part_n is None:
-            check(L.lf_wino_fused_gemm(_ptr(V), _ptr(U2), b, _ptr(y), scr, nscr, dims, N, D, H, W, cin, cout, he, gflags, SLOPE,
-                                       _stream()), 'lf_wino_fused_gemm')
-        else:
-            check(L.lf_wino_fused_gemm_part(_ptr(V), _ptr(U2), b, _ptr(y), scr, nscr, dims, N, D, H, W, cin, cout, he, gflags,
-                                            SLOPE, part_n, _stream()), 'lf_wino_fused_gemm_part')
-
-    def scratch_bytes():                                      # the scratch follows the query of the entry point that is called
-        if part_n is None:
-            return L.lf_wino_fused_scratch_bytes(dims, N, D, H, W, cout)
-        return L.lf_wino_fused_scratch_bytes_part(dims, N, D, H, W, cout, part_n)
-    return _wino_conv_fused(x, cout, flags, depth_inner, (16 if dims == 2 else 64, T, cin), torch.float32, transform,
-                            scratch_bytes, (f'wino{dims}d_fused', gemm))
+    def gemm(V, y, scr, gflags):
+        return (name, V, U2, bias, y, scr, nscr, dims, N, D, H, W, cin, cout, he, gflags, SLOPE) + part
+    return _wino_conv_fused(x, cout, flags, depth_inner, (16 if dims == 2 else 64, T, cin), torch.float32, transform, nscr,
+                            (f'wino{dims}d_fused', gemm))
 
 
 def wide_conv(x, weight, bias, he, flags, transpose=False, depth_inner=False, part_n=None):
@@ -589,18 +601,12 @@ def wide_conv_f16x3(x, weight, bias, he, flags, transpose=False, depth_inner=Fal
     if amax_in is None:
         amax_in = amax_buffer(x.detach().abs().amax(), x.device)
     T = L.lf_wino3d_tiles(N, D, H, W)
-
-    def transform(V):
-        check(L.lf_wino3d_input_transform_f16x3(_ptr(x), _ptr(amax_in), _ptr(V), N, D, H, W, cin, _stream()),
-              'lf_wino3d_input_transform_f16x3')
-
-    def gemm(V, y, scr, nscr, gflags):
-        check(L.lf_wino_fused_f16x3_gemm(_ptr(V), _ptr(U2), eU, _ptr(amax_in), _ptr(bias) if bias is not None else None, _ptr(y),
-                                         _ptr(amax_out) if amax_out is not None else None, scr, nscr, N, D, H, W, cin, cout, he,
-                                         gflags, SLOPE, _stream()), 'lf_wino_fused_f16x3_gemm')
-    return _wino_conv_fused(x, cout, flags, depth_inner, (64, T, L.lf_wino_f16x3_cin_padded(cin) * 2), torch.float16,
-                            ('wino3d_input_f16x3', transform), lambda: L.lf_wino_fused_f16x3_scratch_bytes(N, D, H, W, cout),
-                            ('wino3d_fused_f16x3', gemm))
+    nscr = L.lf_wino_fused_f16x3_scratch_bytes(N, D, H, W, cout)
+    return _wino_conv_fused(
+        x, cout, flags, depth_inner, (64, T, L.lf_wino_f16x3_cin_padded(cin) * 2), torch.float16,
+        ('wino3d_input_f16x3', lambda V: ('lf_wino3d_input_transform_f16x3', x, amax_in, V, N, D, H, W, cin)), nscr,
+        ('wino3d_fused_f16x3', lambda V, y, scr, gflags: ('lf_wino_fused_f16x3_gemm', V, U2, eU, amax_in, bias, y, amax_out, scr, nscr,
+                                                          N, D, H, W, cin, cout, he, gflags, SLOPE)))
 
 
 def _wide_conv2d_f16x3(x, weight, bias, he, flags, transpose=False):
@@ -610,16 +616,12 @@ def _wide_conv2d_f16x3(x, weight, bias, he, flags, transpose=False):
     N, cin, H, W = x.shape
     T = L.lf_wino2d_tiles(N, H, W)
     eV = torch.empty(T, device=x.device, dtype=torch.int32)
-
-    def transform(V):
-        check(L.lf_wino2d_input_transform_f16x3(_ptr(x), _ptr(V), _ptr(eV), N, H, W, cin, _stream()), 'lf_wino2d_input_transform_f16x3')
-
-    def gemm(V, y, scr, nscr, gflags):
-        check(L.lf_wino_fused2d_f16x3_gemm(_ptr(V), _ptr(eV), _ptr(U2), eU, _ptr(bias) if bias is not None else None, _ptr(y), scr,
-                                           nscr, N, H, W, cin, cout, he, gflags, SLOPE, _stream()), 'lf_wino_fused2d_f16x3_gemm')
-    return _wino_conv_fused(x, cout, flags, False, (16, T, L.lf_wino_f16x3_cin_padded(cin) * 2), torch.float16,
-                            ('wino2d_input_f16x3', transform), lambda: L.lf_wino_fused2d_f16x3_scratch_bytes(N, H, W, cout),
-                            ('wino2d_fused_f16x3', gemm))
+    nscr = L.lf_wino_fused2d_f16x3_scratch_bytes(N, H, W, cout)
+    return _wino_conv_fused(
+        x, cout, flags, False, (16, T, L.lf_wino_f16x3_cin_padded(cin) * 2), torch.float16,
+        ('wino2d_input_f16x3', lambda V: ('lf_wino2d_input_transform_f16x3', x, V, eV, N, H, W, cin)), nscr,
+        ('wino2d_fused_f16x3', lambda V, y, scr, gflags: ('lf_wino_fused2d_f16x3_gemm', V, eV, U2, eU, bias, y, scr, nscr, N, H, W,
+                                                          cin, cout, he, gflags, SLOPE)))
 
 
 # Scope of the split-precision 2-D decoder (RenderLoopEngine conv_mode='f16x3'): inside `with ops.wide2d_f16x3():` the wide 2-D
@@ -673,11 +675,9 @@ def _wide_part_n(N):
 
 def epilogue_bwd_amax(gy, y, norm, flags, amax_out):
     """_epilogue_bwd (LeakyReLU' / PixelNorm' of a layer) that also publishes max|gp| into amax_out (lf_epilogue_bwd_amax)."""
-    L = _lib.lib()
     rows = gy.numel() // gy.shape[1]
     gp = torch.empty_like(gy, memory_format=torch.preserve_format)
-    check(L.lf_epilogue_bwd_amax(_ptr(gy), _ptr(y), _ptr(norm) if norm is not None else None, _ptr(gp), rows, gy.shape[1], flags,
-                                 SLOPE, _ptr(amax_out), _stream()), 'lf_epilogue_bwd_amax')
+    launch('lf_epilogue_bwd_amax', gy, y, norm, gp, rows, gy.shape[1], flags, SLOPE, amax_out)
     return gp
 
 
@@ -696,7 +696,6 @@ def he_constant(weight):
 # 3-D resampling
 # ---------------------------------------------------------------------------------------------
 def _resample_fwd(vol, coef, kind):
-    L = _lib.lib()
     n = coef.shape[0]
     vol_n = 1 if (vol.shape[0] == 1 or vol.stride(0) == 0) else vol.shape[0]
     if vol_n not in (1, n):
@@ -706,8 +705,7 @@ def _resample_fwd(vol, coef, kind):
     out = empty_cl((n, C, D, H, W), v.device)
     cf = torch.zeros(n, LF_MAP_COEFS, device=v.device, dtype=torch.float32)
     cf[:, :coef.shape[1]] = coef
-    check(L.lf_resample3d_fwd(_ptr(v), vol_n, _ptr(cf), kind, _ptr(out), n, D, H, W, C, _stream()),
-          'lf_resample3d_fwd')
+    launch('lf_resample3d_fwd', v, vol_n, cf, kind, out, n, D, H, W, C)
     return out, v, cf, vol_n
 
 
@@ -735,19 +733,16 @@ class _Resample(torch.autograd.Function):
             gcoef = torch.empty(n, 18, device=g.device, dtype=torch.float32)
             nbytes = L.lf_resample3d_bwd_coef_scratch_bytes(n, D, H, W)
             scratch = torch.empty(max(nbytes, 4) // 4 + 1, device=g.device, dtype=torch.float32)
-            check(L.lf_resample3d_bwd_coef(_ptr(g), _ptr(v), ctx.vol_n, _ptr(cf), _ptr(gcoef), _ptr(scratch, True),
-                                           scratch.numel() * 4, n, D, H, W, C, _stream()), 'lf_resample3d_bwd_coef')
+            launch('lf_resample3d_bwd_coef', g, v, ctx.vol_n, cf, gcoef, scratch.data_ptr(), scratch.numel() * 4, n, D, H, W, C)
         if ctx.needs_input_grad[0]:
             if DETERMINISTIC_SPLAT:
                 gv = empty_cl((ctx.vol_n, C, D, H, W), g.device)
                 nb = L.lf_resample3d_bwd_vol_det_scratch_bytes(ctx.vol_n, D, H, W, C)
                 scr = torch.empty(nb // 8 + 1, device=g.device, dtype=torch.int64)
-                check(L.lf_resample3d_bwd_vol_det(_ptr(g), _ptr(cf), ctx.kind, _ptr(gv), ctx.vol_n, _ptr(scr, True), scr.numel() * 8,
-                                                  n, D, H, W, C, _stream()), 'lf_resample3d_bwd_vol_det')
+                launch('lf_resample3d_bwd_vol_det', g, cf, ctx.kind, gv, ctx.vol_n, scr.data_ptr(), scr.numel() * 8, n, D, H, W, C)
             else:
                 gv = empty_cl((ctx.vol_n, C, D, H, W), g.device).zero_()
-                check(L.lf_resample3d_bwd_vol(_ptr(g), _ptr(cf), ctx.kind, _ptr(gv), ctx.vol_n, n, D, H, W, C, _stream()),
-                      'lf_resample3d_bwd_vol')
+                launch('lf_resample3d_bwd_vol', g, cf, ctx.kind, gv, ctx.vol_n, n, D, H, W, C)
             if gv.shape[0] == ctx.vol_shape[0]:
                 gvol = gv
             else:
@@ -798,15 +793,13 @@ def resample_fwd_indexed(vols, table, coef, kind=LF_MAP_O2C):
     """lf_resample3d_fwd_indexed: vols (K,C,D,H,W) channels-last, table (N,) from volume_table, coef (N,<=20) -> (N,C,D,H,W);
     row i is the resample of vols[table[i]] under coef[i].  Forward only (the pose loop's coefficient gradient is
     resample_bwd_coef_indexed)."""
-    L = _lib.lib()
     n = coef.shape[0]
     _indexed_args(vols, table, n)
     K, C, D, H, W = vols.shape
     out = empty_cl((n, C, D, H, W), vols.device)
     cf = torch.zeros(n, LF_MAP_COEFS, device=vols.device, dtype=torch.float32)
     cf[:, :coef.shape[1]] = coef
-    check(L.lf_resample3d_fwd_indexed(_ptr(vols), K, _ptr(table), _ptr(cf), kind, _ptr(out), n, D, H, W, C, _stream()),
-          'lf_resample3d_fwd_indexed')
+    launch('lf_resample3d_fwd_indexed', vols, K, table, cf, kind, out, n, D, H, W, C)
     return out
 
 
@@ -826,9 +819,8 @@ def resample_bwd_coef_indexed(gout, vols, table, coef, part_n):
     gcoef = torch.empty(n, 18, device=g.device, dtype=torch.float32)
     nbytes = L.lf_resample3d_bwd_coef_indexed_scratch_bytes(n, part_n, D, H, W)
     scratch = torch.empty(nbytes // 4 + 1, device=g.device, dtype=torch.float32)
-    check(L.lf_resample3d_bwd_coef_indexed(_ptr(g), _ptr(vols), vols.shape[0], _ptr(table), _ptr(cf), _ptr(gcoef),
-                                           _ptr(scratch, True), scratch.numel() * 4, n, D, H, W, C, part_n, _stream()),
-          'lf_resample3d_bwd_coef_indexed')
+    launch('lf_resample3d_bwd_coef_indexed', g, vols, vols.shape[0], table, cf, gcoef, scratch.data_ptr(), scratch.numel() * 4, n,
+           D, H, W, C, part_n)
     return gcoef
 
 
@@ -836,7 +828,6 @@ def resample_bwd_coef_indexed(gout, vols, table, coef, part_n):
 # convolutions with fused epilogue
 # ---------------------------------------------------------------------------------------------
 def _conv3x3_raw(x, wpack, bias, cout, he, flags, want_norm):
-    L = _lib.lib()
     dims = x.dim() - 2
     if dims == 3:
         N, cin, D, H, W = x.shape
@@ -846,40 +837,33 @@ def _conv3x3_raw(x, wpack, bias, cout, he, flags, want_norm):
     fuse_pn = bool(flags & LF_EPI_PIXELNORM) and cout <= 64
     kflags = flags if fuse_pn else (flags & ~LF_EPI_PIXELNORM)
     y = empty_cl((N, cout) + tuple(x.shape[2:]), x.device)
-    norm = torch.empty(N * D * H * W, device=x.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    with _timed(f'conv3x3_{dims}d_{cin}x{cout}'):
-        check(L.lf_conv3x3_fwd(_ptr(x), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y),
-                               _ptr(norm) if (norm is not None and fuse_pn) else None,
-                               dims, N, D, H, W, cin, cout, he, kflags, SLOPE, PN_EPS, _stream()), 'lf_conv3x3_fwd')
+    norm = _norm_buf(flags, N * D * H * W, x.device)
+    launch('lf_conv3x3_fwd', x, wpack, bias, y, norm if fuse_pn else None, dims, N, D, H, W, cin, cout,
+           he, kflags, SLOPE, PN_EPS, tag=f'conv3x3_{dims}d_{cin}x{cout}')
     if (flags & LF_EPI_PIXELNORM) and not fuse_pn:
-        check(L.lf_pixelnorm_fwd(_ptr(y), _ptr(y), _ptr(norm), N * D * H * W, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+        launch('lf_pixelnorm_fwd', y, y, norm, N * D * H * W, cout, PN_EPS)
     return y, norm
 
 
 def conv3x3_bwd_data(gy, wpack_t, cin, he, prev=None):
     """gx = conv^T(gy) * he; prev = (y_prev, norm_prev, flags_prev) folds the producing layer's
     epilogue backward into the store (16-channel records only)."""
-    L = _lib.lib()
     dims = gy.dim() - 2
     N, cout = gy.shape[0], gy.shape[1]
     D, H, W = (gy.shape[2:] if dims == 3 else (1,) + tuple(gy.shape[2:]))
     gx = empty_cl((N, cin) + tuple(gy.shape[2:]), gy.device)
-    py, pn, pf = (prev[0], prev[1], prev[2]) if prev is not None else (None, None, 0)
-    with _timed(f'conv3x3_{dims}d_{cout}x{cin}'):
-        check(L.lf_conv3x3_bwd_data(_ptr(gy), _ptr(wpack_t), _ptr(gx), dims, N, D, H, W, cout, cin, he,
-                                    _ptr(py) if py is not None else None, _ptr(pn) if pn is not None else None, pf,
-                                    SLOPE, _stream()), 'lf_conv3x3_bwd_data')
+    py, pn, pf = _prev(prev)
+    launch('lf_conv3x3_bwd_data', gy, wpack_t, gx, dims, N, D, H, W, cout, cin, he, py, pn, pf, SLOPE,
+           tag=f'conv3x3_{dims}d_{cout}x{cin}')
     return gx
 
 
 def _epilogue_bwd(gy, y, norm, flags):
-    L = _lib.lib()
     if flags == 0:
         return gy
     rows = gy.numel() // gy.shape[1]
     gp = torch.empty_like(gy, memory_format=torch.preserve_format)
-    check(L.lf_epilogue_bwd(_ptr(gy), _ptr(y), _ptr(norm) if norm is not None else None, _ptr(gp), rows,
-                            gy.shape[1], flags, SLOPE, _stream()), 'lf_epilogue_bwd')
+    launch('lf_epilogue_bwd', gy, y, norm, gp, rows, gy.shape[1], flags, SLOPE)
     return gp
 
 
@@ -913,10 +897,8 @@ def latent_cosine_fwd(zp, zt, losses=None, w_latent=0.0):
     sums = torch.empty(N, 4, device=zp.device, dtype=torch.float32)
     nbytes = L.lf_latent_cosine_scratch_bytes(N, P, C)
     scratch = torch.empty(nbytes // 4 + 4, device=zp.device, dtype=torch.float32)
-    with _timed('latent_cosine_fwd', f'{N}x{P}x{C}'):
-        check(L.lf_latent_cosine_fwd(_ptr(zp), _ptr(zt), zt.shape[0], sn, sp, sc, _ptr(sums),
-                                     _ptr(losses) if losses is not None else None, w_latent, _ptr(scratch, True),
-                                     scratch.numel() * 4, N, P, C, _stream()), 'lf_latent_cosine_fwd')
+    launch('lf_latent_cosine_fwd', zp, zt, zt.shape[0], sn, sp, sc, sums, losses, w_latent, scratch.data_ptr(), scratch.numel() * 4,
+           N, P, C, tag='latent_cosine_fwd', detail=f'{N}x{P}x{C}')
     return sums
 
 
@@ -924,7 +906,6 @@ def latent_cosine_bwd_epi(g_in, zp, norm, zt, sums, gscale, flags, out=None):
     """gp = Epi'(g_in + gscale * d(dist)/d(zp); zp, norm, flags) (lf_latent_cosine_bwd_epi): the latent term's gradient joins the
     decoder's gradient g_in (None: the addend alone) at the projected latent and the projection's LeakyReLU' / PixelNorm' is
     applied in the same pass.  out: None = a new tensor, or g_in itself for the in-place form."""
-    L = _lib.lib()
     N, P, C, zt, (sn, sp, sc) = _latent_args(zp, zt)
     _req(sums, 'sums')
     if tuple(sums.shape) != (N, 4) or not sums.is_contiguous():
@@ -939,10 +920,8 @@ def latent_cosine_bwd_epi(g_in, zp, norm, zt, sums, gscale, flags, out=None):
         if norm.numel() != N * P or not norm.is_contiguous():
             raise ValueError('norm must hold N*h*w contiguous values')
     gp = out if out is not None else torch.empty_like(zp, memory_format=torch.preserve_format)
-    with _timed('latent_cosine_bwd_epi', f'{N}x{P}x{C}'):
-        check(L.lf_latent_cosine_bwd_epi(_ptr(g_in) if g_in is not None else None, _ptr(zp), _ptr(norm) if norm is not None else None,
-                                         _ptr(zt), zt.shape[0], sn, sp, sc, _ptr(sums), gscale, _ptr(gp), N, P, C, flags, SLOPE,
-                                         _stream()), 'lf_latent_cosine_bwd_epi')
+    launch('lf_latent_cosine_bwd_epi', g_in, zp, norm, zt, zt.shape[0], sn, sp, sc, sums, gscale, gp, N, P, C, flags, SLOPE,
+           tag='latent_cosine_bwd_epi', detail=f'{N}x{P}x{C}')
     return gp
 
 
@@ -1001,11 +980,8 @@ def nn_dist(x1, x2, T1=None, T2=None, want=('dist',)):
     mean = torch.empty(B, device=dev, dtype=torch.float32) if 'mean' in want else None
     nbytes = L.lf_nn_dist_scratch_bytes(B, M, Q)
     scratch = torch.empty(nbytes // 4 + 4, device=dev, dtype=torch.float32)
-    with _timed('nn_dist', f'{B}x{M}x{Q}'):
-        check(L.lf_nn_dist(_ptr(x1), s1, _ptr(T1) if T1 is not None else None, _ptr(x2), s2, _ptr(T2) if T2 is not None else None,
-                           _ptr(dist) if dist is not None else None, _ptr(idx) if idx is not None else None,
-                           _ptr(mean) if mean is not None else None, _ptr(scratch, True), scratch.numel() * 4, B, M, Q,
-                           _stream()), 'lf_nn_dist')
+    launch('lf_nn_dist', x1, s1, T1, x2, s2, T2, dist, idx, mean, scratch.data_ptr(), scratch.numel() * 4, B, M, Q, tag='nn_dist',
+           detail=f'{B}x{M}x{Q}')
     out = {'dist': dist, 'idx': idx, 'mean': mean}
     return {k: (out[k] if batched else out[k][0]) for k in want}
 
@@ -1031,9 +1007,8 @@ def points_pair_dist(points, A, B):
     mean = torch.empty(R, device=points.device, dtype=torch.float32)
     nbytes = L.lf_points_pair_dist_scratch_bytes(R, P)
     scratch = torch.empty(nbytes // 4 + 4, device=points.device, dtype=torch.float32)
-    with _timed('points_pair_dist', f'{R}x{P}x{rows}'):
-        check(L.lf_points_pair_dist(_ptr(points), sr, _ptr(A), _ptr(B), rows, _ptr(mean), _ptr(scratch, True), scratch.numel() * 4,
-                                    R, P, _stream()), 'lf_points_pair_dist')
+    launch('lf_points_pair_dist', points, sr, A, B, rows, mean, scratch.data_ptr(), scratch.numel() * 4, R, P,
+           tag='points_pair_dist', detail=f'{R}x{P}x{rows}')
     return mean
 
 
@@ -1096,11 +1071,8 @@ def depth_init(depth, mask, intrinsic=None, m=3.0, erode_radius=0):
     counts = torch.empty(B, 8, device=dev, dtype=torch.int32)
     nbytes = L.lf_depth_init_scratch_bytes(B, H, W)
     scratch = torch.empty(nbytes // 4 + 4, device=dev, dtype=torch.float32)
-    with _timed('depth_init', f'{B}x{H}x{W}'):
-        check(L.lf_depth_init(_ptr(d3), _ptr(k3), int(u8), _ptr(intr) if intr is not None else None,
-                              intr.shape[0] if intr is not None else 1, float(m), erode_radius,
-                              _ptr(trans) if trans is not None else None, _ptr(stats), _ptr(counts), _ptr(scratch, True),
-                              scratch.numel() * 4, B, H, W, _stream()), 'lf_depth_init')
+    launch('lf_depth_init', d3, k3, int(u8), intr, intr.shape[0] if intr is not None else 1, float(m), erode_radius, trans, stats,
+           counts, scratch.data_ptr(), scratch.numel() * 4, B, H, W, tag='depth_init', detail=f'{B}x{H}x{W}')
     out = {'stats': stats, 'counts': counts}
     if trans is not None:
         out['trans'] = trans
@@ -1160,7 +1132,6 @@ def observation_prepare(color, depth, mask, boxes, target_size, zn=None, zf=None
             raise ValueError(f'{name} must be float32 shaped ({B},), got {z.dtype} {tuple(z.shape)}')
     if isinstance(stack, (list, dict, set)) or stack not in OBS_STACKS:
         raise ValueError(f'stack {stack!r}: one of {OBS_STACKS}')
-    L = _lib.lib()
     d3 = _aligned4(d3)
     u8 = k3.dtype != torch.float32
     k3 = _aligned4(k3.view(torch.uint8) if k3.dtype == torch.bool else k3)
@@ -1174,12 +1145,8 @@ def observation_prepare(color, depth, mask, boxes, target_size, zn=None, zf=None
     planes = C + 1 + int(with_depth)
     stacked = torch.empty(B, planes, T, T, device=dev, dtype=torch.float32) if stack is not None else None
     stages = (_lib.LF_OBS_PREPARE if prepare else 0) | (_lib.LF_OBS_NORMALIZE if normalize else 0)
-    with _timed('obs_prepare', f'{B}x{C}x{H}x{W}->{T}'):
-        check(L.lf_obs_prepare(_ptr(color) if color is not None else None, _ptr(d3), _ptr(k3), int(u8), _ptr(boxes),
-                               _ptr(zn) if zn is not None else None, _ptr(zf) if zf is not None else None,
-                               _ptr(color_out) if color_out is not None else None, _ptr(depth_out), _ptr(mask_out),
-                               _ptr(stacked) if stacked is not None else None, planes * T * T, int(with_depth), B, C, H, W, T,
-                               stages, _stream()), 'lf_obs_prepare')
+    launch('lf_obs_prepare', color, d3, k3, int(u8), boxes, zn, zf, color_out, depth_out, mask_out, stacked, planes * T * T,
+           int(with_depth), B, C, H, W, T, stages, tag='obs_prepare', detail=f'{B}x{C}x{H}x{W}->{T}')
     out = {'color': color_out, 'depth': depth_out, 'mask': mask_out}
     if stacked is not None:
         out['stack'] = stacked
@@ -1243,10 +1210,6 @@ def _recon_beta(beta_param):
     return float(beta_param), float(beta_param), float(losses._log_beta(float(beta_param), float(beta_param)))
 
 
-def _opt_ptr(t):
-    return _ptr(t) if t is not None else None
-
-
 def recon_losses_fwd(x, y, base, k, mask_logits=None, mask_target=None, beta_param=None):
     """lf_recon_loss_fwd on prepared tensors (fp32, contiguous): -> {'terms': (4,) = (recon, mask_recon, mask_beta, 0), and with
     x: 'thresh': (B,), 'sel': (B,2) int32 = (n_gt, n_tie), 'img_sum': (B,)}.  Three launches, nothing synchronises."""
@@ -1263,28 +1226,22 @@ def recon_losses_fwd(x, y, base, k, mask_logits=None, mask_target=None, beta_par
         out['img_sum'] = torch.empty(B, device=dev, dtype=torch.float32)
     nbytes = L.lf_recon_loss_scratch_bytes(B, C, H, W, Mn)
     scratch = torch.empty(nbytes // 8 + 1, device=dev, dtype=torch.float64)
-    with _timed('recon_loss_fwd', f'{B}x{C}x{H}x{W} k={k} Mn={Mn}'):
-        check(L.lf_recon_loss_fwd(_opt_ptr(x), _opt_ptr(y), RECON_BASES.index(base) if x is not None else 0,
-                                  k if x is not None else 0, _opt_ptr(mask_logits), _opt_ptr(mask_target), a, b, lb,
-                                  _opt_ptr(out.get('thresh')), _opt_ptr(out.get('sel')), _opt_ptr(out.get('img_sum')),
-                                  _ptr(out['terms']), _ptr(scratch, True), scratch.numel() * 8, B, C, H, W, Mn, _stream()),
-              'lf_recon_loss_fwd')
+    launch('lf_recon_loss_fwd', x, y, RECON_BASES.index(base) if x is not None else 0, k if x is not None else 0, mask_logits,
+           mask_target, a, b, lb, out.get('thresh'), out.get('sel'), out.get('img_sum'), out['terms'], scratch.data_ptr(),
+           scratch.numel() * 8, B, C, H, W, Mn, tag='recon_loss_fwd', detail=f'{B}x{C}x{H}x{W} k={k} Mn={Mn}')
     return out
 
 
 def recon_losses_bwd(g_terms, x, y, base, k, thresh, sel, mask_logits=None, mask_target=None, beta_param=None):
     """lf_recon_loss_bwd: g_terms (>= 3,) fp32 ON THE DEVICE -> (gx or None, gmlogit or None).  One launch."""
-    L = _lib.lib()
     B, C, H, W = x.shape if x is not None else (0, 0, 0, 0)
     Mn = mask_logits.numel() if mask_logits is not None else 0
     a, b, lb = _recon_beta(beta_param if mask_logits is not None else None)
     gx = torch.empty_like(x) if x is not None else None
     gz = torch.empty_like(mask_logits) if mask_logits is not None else None
-    with _timed('recon_loss_bwd', f'{B}x{C}x{H}x{W} k={k} Mn={Mn}'):
-        check(L.lf_recon_loss_bwd(_ptr(g_terms), _opt_ptr(x), _opt_ptr(y), RECON_BASES.index(base) if x is not None else 0,
-                                  k if x is not None else 0, _opt_ptr(thresh), _opt_ptr(sel), _opt_ptr(mask_logits),
-                                  _opt_ptr(mask_target), a, b, lb, _opt_ptr(gx), _opt_ptr(gz), B, C, H, W, Mn, _stream()),
-              'lf_recon_loss_bwd')
+    launch('lf_recon_loss_bwd', g_terms, x, y, RECON_BASES.index(base) if x is not None else 0, k if x is not None else 0, thresh,
+           sel, mask_logits, mask_target, a, b, lb, gx, gz, B, C, H, W, Mn, tag='recon_loss_bwd',
+           detail=f'{B}x{C}x{H}x{W} k={k} Mn={Mn}')
     return gx, gz
 
 
@@ -1414,24 +1371,20 @@ def _conv1x1_raw(x_ptr_tensor, wpack, bias, N, P, cin, ksl, xbs, xss, cout, y2d,
     """y2d: output buffer; yaddr = (batch_stride, row_stride, slice_channels, slice_stride) or None
     for plain [N*P][cout] rows.  xscale: a factor per (sample, slice, pixel) applied to the operand (lf_conv1x1_fwd_scaled).
     Returns norm or None."""
-    L = _lib.lib()
     ybs, yrs, ysc, yss = yaddr if yaddr is not None else (P * cout, cout, 1 << 30, 0)
     fuse_pn = bool(flags & LF_EPI_PIXELNORM) and cout <= 128
     kflags = flags if fuse_pn else (flags & ~LF_EPI_PIXELNORM)
-    norm = torch.empty(N * P, device=y2d.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
+    norm = _norm_buf(flags, N * P, y2d.device)
     if xscale is not None:
         assert xscale.numel() == N * ksl * P and xscale.dtype == torch.float32 and xscale.is_contiguous()
-        check(L.lf_conv1x1_fwd_scaled(_ptr(x_ptr_tensor), _ptr(xscale), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y2d),
-                                      _ptr(norm) if (norm is not None and fuse_pn) else None,
-                                      N, P, cin, ksl, xbs, xss, cout, ybs, yrs, ysc, yss, he, kflags, SLOPE, PN_EPS, _stream()),
-              'lf_conv1x1_fwd_scaled')
+        launch('lf_conv1x1_fwd_scaled', x_ptr_tensor, xscale, wpack, bias, y2d,
+               norm if fuse_pn else None, N, P, cin, ksl, xbs, xss, cout, ybs, yrs, ysc, yss, he,
+               kflags, SLOPE, PN_EPS)
     else:
-        check(L.lf_conv1x1_fwd(_ptr(x_ptr_tensor), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y2d),
-                               _ptr(norm) if (norm is not None and fuse_pn) else None,
-                               N, P, cin, ksl, xbs, xss, cout, ybs, yrs, ysc, yss, he, kflags, SLOPE, PN_EPS, _stream()),
-              'lf_conv1x1_fwd')
+        launch('lf_conv1x1_fwd', x_ptr_tensor, wpack, bias, y2d, norm if fuse_pn else None, N, P, cin,
+               ksl, xbs, xss, cout, ybs, yrs, ysc, yss, he, kflags, SLOPE, PN_EPS)
     if (flags & LF_EPI_PIXELNORM) and not fuse_pn:
-        check(L.lf_pixelnorm_fwd(_ptr(y2d), _ptr(y2d), _ptr(norm), N * P, cout, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+        launch('lf_pixelnorm_fwd', y2d, y2d, norm, N * P, cout, PN_EPS)
     return norm
 
 
@@ -1452,11 +1405,8 @@ def rows_gemm_epilogue(x2, wpack, bias, he, cout, flags=LF_EPI_LRELU | LF_EPI_PI
         if bias.numel() != cout:
             raise ValueError('bias must hold Cout values')
     y = torch.empty(M, cout, device=x2.device, dtype=torch.float32)
-    norm = torch.empty(M, device=x2.device, dtype=torch.float32) if (flags & LF_EPI_PIXELNORM) else None
-    with _timed(tag, f'{M}x{K}x{cout}'):
-        check(L.lf_rows_gemm_epi(_ptr(x2), _ptr(wpack), _ptr(bias) if bias is not None else None, _ptr(y),
-                                 _ptr(norm) if norm is not None else None, M, K, cout, he, flags, SLOPE, PN_EPS, _stream()),
-              'lf_rows_gemm_epi')
+    norm = _norm_buf(flags, M, x2.device)
+    launch('lf_rows_gemm_epi', x2, wpack, bias, y, norm, M, K, cout, he, flags, SLOPE, PN_EPS, tag=tag, detail=f'{M}x{K}x{cout}')
     return y, norm
 
 
@@ -1525,7 +1475,6 @@ class _FactorProject(torch.autograd.Function):
                         and x.shape[2] in (16, 32, 64, 128) and (x.shape[3] * x.shape[4]) % 16 == 0 and x.is_cuda)
         if ctx.mfma:
             # round 6 (csrc/lift_mfma.hip): the bf16 volume read as it lies, one MFMA per depth; no fp32 copy of the volume
-            L = _lib.lib()
             _req(weight, 'weight')
             x = cl(x)
             N, C, D, H, W = x.shape
@@ -1533,9 +1482,7 @@ class _FactorProject(torch.autograd.Function):
             wtab = _pk(weight, 'p16f', lambda w: w.reshape(16, 16, D).permute(2, 0, 1).contiguous().to(torch.bfloat16))
             y = empty_cl((N, 16, H, W), x.device)
             norm = torch.empty(N * H * W, device=x.device, dtype=torch.float32)
-            with _timed('proj16_fwd'):
-                check(L.lf_proj16_fwd(_ptr(x), _ptr(wtab), _ptr(bias) if bias is not None else None, _ptr(y), _ptr(norm), N * H * W, H * W,
-                                      D, he, SLOPE, PN_EPS, _stream()), 'lf_proj16_fwd')
+            launch('lf_proj16_fwd', x, wtab, bias, y, norm, N * H * W, H * W, D, he, SLOPE, PN_EPS, tag='proj16_fwd')
             ctx.flags, ctx.he, ctx.xshape = LF_EPI_LRELU | LF_EPI_PIXELNORM, he, x.shape
             ctx.save_for_backward(y, norm, weight, x)
             return y
@@ -1572,9 +1519,8 @@ class _FactorProject(torch.autograd.Function):
             gwt = torch.empty(16, 16 * D, device=gp.device, dtype=torch.float32)
             nb = L.lf_proj16_bwd_scratch_bytes(D)
             scr = torch.empty(nb // 4 + 4, device=gp.device, dtype=torch.float32)
-            with _timed('proj16_bwd'):
-                check(L.lf_proj16_bwd(_ptr(gp), _ptr(x_saved), _ptr(wtab_t), _ptr(gx), _ptr(gwt), _ptr(scr, True), scr.numel() * 4,
-                                      N * H * W, H * W, D, ctx.he, _stream()), 'lf_proj16_bwd')
+            launch('lf_proj16_bwd', gp, x_saved, wtab_t, gx, gwt, scr.data_ptr(), scr.numel() * 4, N * H * W, H * W, D, ctx.he,
+                   tag='proj16_bwd')
             with autocast(True):
                 if ctx.needs_input_grad[2]:
                     gb = _T().bias_grad(gp.permute(0, 2, 3, 1).reshape(N * H * W, cout), 0)
@@ -1615,7 +1561,7 @@ LIFT_FUSED = True          # A/B switch of the fused training-path lift (_LiftFu
 
 
 def _lift_permute(src, V, P, c0, S, fold, out):
-    check(_lib.lib().lf_lift_permute(_ptr(src), _ptr(out), V, P, c0, S, 1 if fold else 0, _stream()), 'lf_lift_permute')
+    launch('lf_lift_permute', src, out, V, P, c0, S, 1 if fold else 0)
     return out
 
 
@@ -1628,7 +1574,6 @@ def lift(x, weight, bias, out_size):
     PixelNorm over ALL C0*S channels, viewed as (V,C0,S,H,W).  The fused unfold below is the inference path;
     when a gradient is wanted the same result is composed from the differentiable pointwise conv and a
     layout copy."""
-    L = _lib.lib()
     _req(x, 'x')
     x = cl(x)
     V, cin, H, W = x.shape
@@ -1651,10 +1596,10 @@ def lift(x, weight, bias, out_size):
         norm = torch.empty(V * P, device=x.device, dtype=torch.float32)
         # norm only: normalisation itself is folded into the unfold pass below
         tmp2 = torch.empty_like(tmp)
-        check(L.lf_pixelnorm_fwd(_ptr(tmp), _ptr(tmp2), _ptr(norm), V * P, cs, PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+        launch('lf_pixelnorm_fwd', tmp, tmp2, norm, V * P, cs, PN_EPS)
         tmp = tmp2
     out = empty_cl((V, c0, out_size, H, W), x.device)
-    check(L.lf_lift_unfold(_ptr(tmp), None, _ptr(out), V, P, c0, out_size, _stream()), 'lf_lift_unfold')
+    launch('lf_lift_unfold', tmp, None, out, V, P, c0, out_size)
     return out
 
 
@@ -1666,22 +1611,19 @@ class _ColumnSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        L = _lib.lib()
         x = cl(_req(_f32(x), 'x'))
         N, C, D, H, W = x.shape
         y = empty_cl((N, C, H, W), x.device)
-        with _timed('column_sum'):
-            check(L.lf_column_reduce_sum_fwd(_ptr(x), _ptr(y), N, D, H * W, C, _stream()), 'lf_column_reduce_sum_fwd')
+        launch('lf_column_reduce_sum_fwd', x, y, N, D, H * W, C, tag='column_sum')
         ctx.xshape = tuple(x.shape)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        L = _lib.lib()
         N, C, D, H, W = ctx.xshape
         g = cl(gy)
         gx = empty_cl(ctx.xshape, g.device)
-        check(L.lf_column_reduce_sum_bwd(_ptr(g), _ptr(gx), N, D, H * W, C, _stream()), 'lf_column_reduce_sum_bwd')
+        launch('lf_column_reduce_sum_bwd', g, gx, N, D, H * W, C)
         return gx
 
 
@@ -1695,22 +1637,19 @@ class _ColumnSoftmax(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, logits):
-        L = _lib.lib()
         lg = _req(logits, 'logits').contiguous()
         N, one, D, H, W = lg.shape
         if one != 1:
             raise ValueError('column_softmax expects single-channel logits')
         w = torch.empty_like(lg)
         zd = torch.empty(N, 1, H, W, device=lg.device, dtype=torch.float32)
-        with _timed('column_softmax'):
-            check(L.lf_column_softmax_fwd(_ptr(lg), _ptr(w), _ptr(zd), N, D, H * W, _stream()), 'lf_column_softmax_fwd')
+        launch('lf_column_softmax_fwd', lg, w, zd, N, D, H * W, tag='column_softmax')
         ctx.save_for_backward(w)
         ctx.set_materialize_grads(False)
         return w, zd
 
     @staticmethod
     def backward(ctx, gw, gzd):
-        L = _lib.lib()
         w, = ctx.saved_tensors
         N, _, D, H, W = w.shape
         if gw is None and gzd is None:
@@ -1718,8 +1657,7 @@ class _ColumnSoftmax(torch.autograd.Function):
         gw = gw.contiguous() if gw is not None else None
         gzd = gzd.contiguous() if gzd is not None else None
         gl = torch.empty_like(w)
-        check(L.lf_column_softmax_bwd(_ptr(w), _ptr(gw) if gw is not None else None, _ptr(gzd) if gzd is not None else None,
-                                      _ptr(gl), N, D, H * W, _stream()), 'lf_column_softmax_bwd')
+        launch('lf_column_softmax_bwd', w, gw, gzd, gl, N, D, H * W)
         return gl
 
 
@@ -1732,20 +1670,18 @@ class _ColumnScale(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, w):
-        L = _lib.lib()
         z = cl(_req(_f32(z), 'z'))
         w = _req(w, 'w').contiguous()
         N, C, D, H, W = z.shape
         if tuple(w.shape) != (N, 1, D, H, W) or C % 4:
             raise ValueError('column_scale: w must be (N,1,D,H,W) and C a multiple of 4')
         out = empty_cl(z.shape, z.device)
-        check(L.lf_column_scale_fwd(_ptr(z), _ptr(w), _ptr(out), N * D * H * W, C, _stream()), 'lf_column_scale_fwd')
+        launch('lf_column_scale_fwd', z, w, out, N * D * H * W, C)
         ctx.save_for_backward(z, w)
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        L = _lib.lib()
         z, w = ctx.saved_tensors
         N, C, D, H, W = z.shape
         g = cl(gout)
@@ -1753,8 +1689,7 @@ class _ColumnScale(torch.autograd.Function):
         gw = torch.empty_like(w) if ctx.needs_input_grad[1] else None
         if gz is None and gw is None:
             return None, None
-        check(L.lf_column_scale_bwd(_ptr(g), _ptr(z), _ptr(w), _ptr(gz) if gz is not None else None,
-                                    _ptr(gw) if gw is not None else None, N * D * H * W, C, _stream()), 'lf_column_scale_bwd')
+        launch('lf_column_scale_bwd', g, z, w, gz, gw, N * D * H * W, C)
         return gz, gw
 
 
@@ -1781,7 +1716,6 @@ class _FuseViews(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, kind):
-        L = _lib.lib()
         z = _f32(z)
         _req(z, 'z')
         B, V = z.shape[0], z.shape[1]
@@ -1792,8 +1726,7 @@ class _FuseViews(torch.autograd.Function):
         idx = torch.empty(B, n, device=z.device, dtype=torch.int32) if need_idx else None
         with _timed('fuse_views'):
             for b in range(B):
-                check(L.lf_fuse_views_fwd(_ptr(zz[b * V]), _ptr(out[b]), _ptr(idx[b]) if idx is not None else None, kind, V, n, n,
-                                          _stream()), 'lf_fuse_views_fwd')
+                launch('lf_fuse_views_fwd', zz[b * V], out[b], idx[b] if idx is not None else None, kind, V, n, n)
         ctx.meta = (kind, B, V, n, tuple(zz.shape), tuple(z.shape))
         if idx is not None:
             ctx.save_for_backward(idx)
@@ -1801,7 +1734,6 @@ class _FuseViews(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         kind, B, V, n, zshape, orig = ctx.meta
         idx = ctx.saved_tensors[0] if ctx.saved_tensors else None
         g = g.squeeze(1)
@@ -1810,8 +1742,7 @@ class _FuseViews(torch.autograd.Function):
                          memory_format=(torch.channels_last_3d if len(zshape) == 5 else torch.channels_last if len(zshape) == 4
                                         else torch.contiguous_format))
         for b in range(B):
-            check(L.lf_fuse_views_bwd(_ptr(g[b]), _ptr(idx[b]) if idx is not None else None, _ptr(gz[b * V]), kind, V, n, n,
-                                      _stream()), 'lf_fuse_views_bwd')
+            launch('lf_fuse_views_bwd', g[b], idx[b] if idx is not None else None, gz[b * V], kind, V, n, n)
         return gz.view(orig), None
 
 
@@ -1827,7 +1758,6 @@ class _FuseBlend(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, logits):
-        L = _lib.lib()
         z = _f32(z)
         _req(z, 'z'), _req(logits, 'logits')
         B, V, C = z.shape[:3]
@@ -1840,8 +1770,7 @@ class _FuseBlend(torch.autograd.Function):
         out = torch.empty_like(zz[:B])
         with _timed('fuse_blend'):
             for b in range(B):
-                check(L.lf_fuse_blend_fwd(_ptr(zz[b * V]), _ptr(lg[b * V]), _ptr(w[b * V]), _ptr(out[b]), V, rows, C, rows * C, rows,
-                                          _stream()), 'lf_fuse_blend_fwd')
+                launch('lf_fuse_blend_fwd', zz[b * V], lg[b * V], w[b * V], out[b], V, rows, C, rows * C, rows)
         ctx.save_for_backward(zz, w)
         ctx.meta = (B, V, C, rows, tuple(z.shape), tuple(logits.shape))
         ctx.mark_non_differentiable(w)
@@ -1849,7 +1778,6 @@ class _FuseBlend(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g, _gw):
-        L = _lib.lib()
         zz, w = ctx.saved_tensors
         B, V, C, rows, zshape, lshape = ctx.meta
         g = cl(g.squeeze(1))
@@ -1858,9 +1786,8 @@ class _FuseBlend(torch.autograd.Function):
         if gz is None and gl is None:
             return None, None
         for b in range(B):
-            check(L.lf_fuse_blend_bwd(_ptr(g[b]), _ptr(zz[b * V]), _ptr(w[b * V]), _ptr(gz[b * V]) if gz is not None else None,
-                                      _ptr(gl[b * V]) if gl is not None else None, V, rows, C, rows * C, rows, _stream()),
-                  'lf_fuse_blend_bwd')
+            launch('lf_fuse_blend_bwd', g[b], zz[b * V], w[b * V], gz[b * V] if gz is not None else None,
+                   gl[b * V] if gl is not None else None, V, rows, C, rows * C, rows)
         return (gz.view(zshape) if gz is not None else None), (gl.view(lshape) if gl is not None else None)
 
 
@@ -1874,7 +1801,6 @@ def fuse_blend(z, logits):
 class _GridSample2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, grid, bilinear, border):
-        L = _lib.lib()
         _req(img, 'image')
         img, grid = img.float().contiguous(), grid.float().contiguous()
         N, C, H, W = img.shape
@@ -1882,15 +1808,13 @@ class _GridSample2d(torch.autograd.Function):
         if grid.shape[0] != N or grid.shape[3] != 2:
             raise ValueError('grid must be (N, Ho, Wo, 2)')
         out = torch.empty(N, C, Ho, Wo, device=img.device, dtype=torch.float32)
-        check(L.lf_grid_sample2d_fwd(_ptr(img), _ptr(grid), _ptr(out), N, C, H, W, Ho, Wo, int(bilinear), int(border), _stream()),
-              'lf_grid_sample2d_fwd')
+        launch('lf_grid_sample2d_fwd', img, grid, out, N, C, H, W, Ho, Wo, int(bilinear), int(border))
         ctx.save_for_backward(img, grid)
         ctx.mode = (int(bilinear), int(border))
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        L = _lib.lib()
         img, grid = ctx.saved_tensors
         N, C, H, W = img.shape
         Ho, Wo = grid.shape[1], grid.shape[2]
@@ -1898,9 +1822,8 @@ class _GridSample2d(torch.autograd.Function):
         ggrid = torch.empty_like(grid) if ctx.needs_input_grad[1] else None
         if gimg is None and ggrid is None:
             return None, None, None, None
-        check(L.lf_grid_sample2d_bwd(_ptr(img), _ptr(grid), _ptr(gout.float().contiguous()),
-                                     _ptr(gimg) if gimg is not None else None, _ptr(ggrid) if ggrid is not None else None,
-                                     N, C, H, W, Ho, Wo, ctx.mode[0], ctx.mode[1], _stream()), 'lf_grid_sample2d_bwd')
+        launch('lf_grid_sample2d_bwd', img, grid, gout.float().contiguous(), gimg, ggrid, N, C, H, W, Ho, Wo, ctx.mode[0],
+               ctx.mode[1])
         return gimg, ggrid, None, None
 
 
@@ -2006,7 +1929,6 @@ def _ibr_shapes(image_in, depth_in, depth_out, mask_out, rec):
 
 
 def _ibr_fwd(image_in, depth_in, depth_out, mask_out, rec, out):
-    L = _lib.lib()
     for t, name in ((image_in, 'image_in'), (depth_in, 'depth_in'), (depth_out, 'depth_out'), (rec.flat, 'records')):
         _req(t, name)
     B, Vo, Vi, C, H, W = _ibr_shapes(image_in, depth_in, depth_out, mask_out, rec)
@@ -2021,9 +1943,8 @@ def _ibr_fwd(image_in, depth_in, depth_out, mask_out, rec, out):
         rows = out.view(B, Vo, Vi, C + 2, H, W)
         image_re, depth_re = rows[:, :, :, :C], rows[:, :, :, C:C + 1]
         strides = ((C + 2) * H * W, (C + 2) * H * W)
-    check(L.lf_ibr_reproject_fwd(_ptr(image_in), _ptr(depth_in), _ptr(depth_out), _ptr(mask_out) if mask_out is not None else None,
-                                 rec.pair.data_ptr(), rec.view_in.data_ptr(), rec.view_out.data_ptr(), _ptr(image_re),
-                                 _ptr(depth_re), B, Vo, Vi, C, H, W, strides[0], strides[1], _stream()), 'lf_ibr_reproject_fwd')
+    launch('lf_ibr_reproject_fwd', image_in, depth_in, depth_out, mask_out, rec.pair.data_ptr(), rec.view_in.data_ptr(),
+           rec.view_out.data_ptr(), image_re, depth_re, B, Vo, Vi, C, H, W, strides[0], strides[1])
     return (image_in, depth_in, depth_out, mask_out), (image_re, depth_re)
 
 
@@ -2037,7 +1958,6 @@ class _IbrReproject(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_image, g_depth):
-        L = _lib.lib()
         image_in, depth_in, depth_out, mask_out = ctx.saved_tensors
         rec = ctx.rec
         B, Vo, Vi, C, H, W = _ibr_shapes(image_in, depth_in, depth_out, mask_out, rec)
@@ -2049,10 +1969,8 @@ class _IbrReproject(torch.autograd.Function):
         gi = torch.zeros_like(image_in) if need[0] else None
         gdi = torch.zeros_like(depth_in) if need[1] else None
         gdo = torch.empty_like(depth_out) if need[2] else None
-        opt = lambda t: _ptr(t) if t is not None else None                                   # noqa: E731
-        check(L.lf_ibr_reproject_bwd(_ptr(image_in), _ptr(depth_in), _ptr(depth_out), opt(mask_out), rec.pair.data_ptr(),
-                                     rec.view_in.data_ptr(), rec.view_out.data_ptr(), opt(g_image), opt(g_depth), opt(gi), opt(gdi),
-                                     opt(gdo), B, Vo, Vi, C, H, W, _stream()), 'lf_ibr_reproject_bwd')
+        launch('lf_ibr_reproject_bwd', image_in, depth_in, depth_out, mask_out, rec.pair.data_ptr(), rec.view_in.data_ptr(),
+               rec.view_out.data_ptr(), g_image, g_depth, gi, gdi, gdo, B, Vo, Vi, C, H, W)
         return gi, gdi, gdo, None, None
 
 
@@ -2086,13 +2004,12 @@ def ibr_reproject(image_in, depth_in, depth_out, records, mask_out=None, out=Non
 class _PixelNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
-        L = _lib.lib()
         _req(x, 'x')
         x = cl(x)
         rows = x.numel() // x.shape[1]
         y = torch.empty_like(x, memory_format=torch.preserve_format)
         norm = torch.empty(rows, device=x.device, dtype=torch.float32)
-        check(L.lf_pixelnorm_fwd(_ptr(x), _ptr(y), _ptr(norm), rows, x.shape[1], PN_EPS, _stream()), 'lf_pixelnorm_fwd')
+        launch('lf_pixelnorm_fwd', x, y, norm, rows, x.shape[1], PN_EPS)
         ctx.save_for_backward(y, norm)
         return y
 
@@ -2109,7 +2026,6 @@ def pixelnorm(x):
 class _Resize(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, linear, up):
-        L = _lib.lib()
         _req(x, 'x')
         x = cl(x)
         dims = x.dim() - 2
@@ -2117,17 +2033,16 @@ class _Resize(torch.autograd.Function):
         D, H, W = (x.shape[2:] if dims == 3 else (1,) + tuple(x.shape[2:]))
         out_sp = tuple((s * 2 if up else s // 2) for s in x.shape[2:])
         y = empty_cl((N, C) + out_sp, x.device)
-        check(L.lf_resize_fwd(_ptr(x), _ptr(y), dims, N, D, H, W, C, linear, up, _stream()), 'lf_resize_fwd')
+        launch('lf_resize_fwd', x, y, dims, N, D, H, W, C, linear, up)
         ctx.meta = (dims, N, C, D, H, W, linear, up, tuple(x.shape))
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        L = _lib.lib()
         dims, N, C, D, H, W, linear, up, xshape = ctx.meta
         g = cl(gy)
         gx = empty_cl(xshape, g.device)
-        check(L.lf_resize_bwd(_ptr(g), _ptr(gx), dims, N, D, H, W, C, linear, up, _stream()), 'lf_resize_bwd')
+        launch('lf_resize_bwd', g, gx, dims, N, D, H, W, C, linear, up)
         return gx, None, None
 
 

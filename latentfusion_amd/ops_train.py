@@ -9,8 +9,8 @@ import math  # noqa: F401
 import torch
 
 from . import _lib, ops
-from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_C2O, LF_MAP_COEFS, LF_MAP_O2C, check  # noqa: F401
-from .ops import (PN_EPS, SLOPE, _ac_in, _cached, _conv1x1_raw, _dense_views, _f32, _lift_permute, _pk, _ptr, _req, _stream, _timed, _wsrc, autocast, cl, conv3d_c16_ring_bf16, conv3d_c16_ring_bf16_io, conv3d_c16_wino, empty_cl, empty_cl16, he_constant, pack_conv1x1, pack_conv3d_c16_ring_bf16, pack_conv3d_c16_wino, round_bf16, storage_bf16)  # noqa: F401
+from ._lib import LF_EPI_LRELU, LF_EPI_PIXELNORM, LF_MAP_C2O, LF_MAP_COEFS, LF_MAP_O2C  # noqa: F401
+from .ops import (PN_EPS, SLOPE, _ac_in, _cached, _conv1x1_raw, _dense_views, _f32, _lift_permute, _pk, _req, _timed, _wsrc, launch, autocast, cl, conv3d_c16_ring_bf16, conv3d_c16_ring_bf16_io, conv3d_c16_wino, empty_cl, empty_cl16, he_constant, pack_conv1x1, pack_conv3d_c16_ring_bf16, pack_conv3d_c16_wino, round_bf16, storage_bf16)  # noqa: F401
 
 
 # Weight-gradient launches of the training step on a second HIP stream (round 5).  The 16 -> 16 kernels of the step are bound by
@@ -95,7 +95,6 @@ class _ResampleAC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vol, coef, kind):
-        L = _lib.lib()
         n = coef.shape[0]
         vol_n = 1 if (vol.shape[0] == 1 or vol.stride(0) == 0) else vol.shape[0]
         if vol_n not in (1, n):
@@ -106,8 +105,7 @@ class _ResampleAC(torch.autograd.Function):
         cf = torch.zeros(n, LF_MAP_COEFS, device=v.device, dtype=torch.float32)
         cf[:, :coef.shape[1]] = coef.detach().float()
         io = (1 if v.dtype == torch.bfloat16 else 0) | 2
-        with _timed('resample_fwd', f'{kind}:{n}:io{io}'):
-            check(L.lf_resample3d_fwd_io(_ptr(v), vol_n, _ptr(cf), kind, _ptr(out), n, D, H, W, io, _stream()), 'lf_resample3d_fwd_io')
+        launch('lf_resample3d_fwd_io', v, vol_n, cf, kind, out, n, D, H, W, io, tag='resample_fwd', detail=f'{kind}:{n}:io{io}')
         ctx.save_for_backward(cf)
         ctx.meta = (kind, vol_n, tuple(vol.shape), vol.dtype)
         return out
@@ -127,9 +125,8 @@ class _ResampleAC(torch.autograd.Function):
         nb = L.lf_resample3d_bwd_vol_det_io_scratch_bytes(vol_n, n, D, H, W)
         scr = torch.empty(nb // 8 + 1, device=g.device, dtype=torch.int64)
         io = (1 if g.dtype == torch.bfloat16 else 0) | (2 if gv.dtype == torch.bfloat16 else 0)
-        with _timed('resample_bwd_vol', f'{kind}:{n}:io{io}'):
-            check(L.lf_resample3d_bwd_vol_det_io(_ptr(g), _ptr(cf), kind, _ptr(gv), vol_n, _ptr(scr, True), scr.numel() * 8, n, D, H, W, io,
-                                                 _stream()), 'lf_resample3d_bwd_vol_det_io')
+        launch('lf_resample3d_bwd_vol_det_io', g, cf, kind, gv, vol_n, scr.data_ptr(), scr.numel() * 8, n, D, H, W, io,
+               tag='resample_bwd_vol', detail=f'{kind}:{n}:io{io}')
         if gv.shape[0] == vshape[0]:
             return gv, None, None
         gvol = torch.zeros(vshape, device=g.device, dtype=gv.dtype)     # expanded (stride-0) input: see _Resample.backward
@@ -188,8 +185,7 @@ class _Wgrad:
 
     def _launch(self, entry, x, gp, out, dims, cin, he, *io):
         N = gp.shape[0] if self.dims else 1
-        check(getattr(_lib.lib(), entry)(_ptr(x) if x is not None else None, _ptr(gp), _ptr(out), _ptr(self.scratch, True),
-                                         self.scratch.numel() * 4, dims, N, *self.sp, cin, self.cout, he, *io, _stream()), entry)
+        launch(entry, x, gp, out, self.scratch.data_ptr(), self.scratch.numel() * 4, dims, N, *self.sp, cin, self.cout, he, *io)
 
     def __call__(self, x, gp, out):
         """out [taps][cout][cin] = he * sum_v gp[v] x[v + tap] on the current stream.  The bf16 entry takes either operand in fp32
@@ -269,10 +265,8 @@ def epilogue_bwd_c16(gy, y, norm, flags, want_bias, out_bf16=True):
     nb = L.lf_epilogue_bwd_c16_scratch_bytes(rows) if want_bias else 0
     scr = torch.empty(nb // 4 + 1, device=gy.device, dtype=torch.float32) if want_bias else None
     io = (1 if gy.dtype == torch.bfloat16 else 0) | (2 if (y is not None and y.dtype == torch.bfloat16) else 0) | (4 if out_bf16 else 0)
-    with _timed('epilogue_bwd_c16', f'{rows}:io{io}'):
-        check(L.lf_epilogue_bwd_c16(_ptr(gy), _ptr(y) if y is not None else None, _ptr(norm) if norm is not None else None, _ptr(gp),
-                                    _ptr(gb) if gb is not None else None, _ptr(scr, True) if scr is not None else None,
-                                    scr.numel() * 4 if scr is not None else 0, rows, flags, SLOPE, io, _stream()), 'lf_epilogue_bwd_c16')
+    launch('lf_epilogue_bwd_c16', gy, y, norm, gp, gb, scr.data_ptr() if scr is not None else None,
+           scr.numel() * 4 if scr is not None else 0, rows, flags, SLOPE, io, tag='epilogue_bwd_c16', detail=f'{rows}:io{io}')
     return gp, gb
 
 
@@ -342,14 +336,12 @@ class _Conv16AC(torch.autograd.Function):
         ctx.pw = bool(one and PW16 and flags in (0, LF_EPI_LRELU))
         if ctx.pw:
             # (round 6) a pointwise layer is one MFMA per 16 voxels, streamed: same products, same roundings as the ring kernel
-            L = _lib.lib()
             wq = _pk(weight, 'p1f', lambda t: t.detach().reshape(16, 16).to(torch.bfloat16).contiguous())
             y = empty_cl16(tuple(x.shape), x.device, True)
             norm = None
             b_ = bias.detach() if bias is not None else None
-            with _timed('pw16_fwd', f'{x.shape[0]}:{x.dtype == torch.bfloat16}'):
-                check(L.lf_pw16_fwd(_ptr(x), 1 if x.dtype == torch.bfloat16 else 0, _ptr(wq), _ptr(b_) if b_ is not None else None, he, flags,
-                                    SLOPE, _ptr(y), x.numel() // 16, _stream()), 'lf_pw16_fwd')
+            launch('lf_pw16_fwd', x, 1 if x.dtype == torch.bfloat16 else 0, wq, b_, he, flags, SLOPE, y, x.numel() // 16,
+                   tag='pw16_fwd', detail=f'{x.shape[0]}:{x.dtype == torch.bfloat16}')
         elif RING_BLOCK_FWD and flags == (LF_EPI_LRELU | LF_EPI_PIXELNORM) and x.shape[2] * x.shape[3] * x.shape[4] * 64 < 2 ** 31:
             # the same arithmetic on the one-group ring kernel with its epilogue at compile time (LF_RING_EX_BLOCK): bit-identical
             pack = _pk(weight, 'a3f', lambda t: pack_conv3d_c16_ring_bf16(w3(t)))
@@ -423,9 +415,9 @@ class _Conv16AC(torch.autograd.Function):
                     gb = torch.empty(16, device=gp.device, dtype=torch.float32)
                     nb = L.lf_pw16_bwd_scratch_bytes(rows)
                     scr = torch.empty(nb // 4 + 4, device=gp.device, dtype=torch.float32)
-                with _timed('pw16_bwd', f'{gp.shape[0]}:{out16}'):
-                    check(L.lf_pw16_bwd(_ptr(gp), _ptr(wtq), ctx.he, _ptr(gx), 1 if out16 else 0, _ptr(gb) if need_gb else None,
-                                        _ptr(scr, True) if need_gb else None, scr.numel() * 4 if need_gb else 0, rows, _stream()), 'lf_pw16_bwd')
+                launch('lf_pw16_bwd', gp, wtq, ctx.he, gx, 1 if out16 else 0, gb if need_gb else None,
+                       scr.data_ptr() if need_gb else None, scr.numel() * 4 if need_gb else 0, rows, tag='pw16_bwd',
+                       detail=f'{gp.shape[0]}:{out16}')
             elif ctx.needs_input_grad[0]:
                 pack_t = _pk(w, 'a3b', lambda t: pack_conv3d_c16_ring_bf16(w3(t), transpose=True))
                 if ctx.link is not None and gp.dtype == torch.bfloat16 and _chain_take(ctx.link[1]) is None:
@@ -547,7 +539,6 @@ def ring_multi(x, wpacks, he, outs, extra=0, e0=None, e1=None, o2=None, addend_p
     ring-kernel weight packs.  wpacks: the packs back to back ((ngroups,14,16,32) bf16); outs: per group (y, addend or None, round)
     -- y / addend fp32 or bf16 channels-last volumes (their dtypes select the storage flags), round: bf16(bf16(conv) * he) instead
     of fma(conv, he, addend).  extra / e0 / e1 / o2: the fused element-wise stage (LF_RING_EX_*, include/lf_hip.h)."""
-    L = _lib.lib()
     N, _, D, H, W = x.shape
     ng = len(outs)
     assert wpacks.dtype == torch.bfloat16 and wpacks.numel() == ng * 14 * 512 and wpacks.is_contiguous()
@@ -555,15 +546,12 @@ def ring_multi(x, wpacks, he, outs, extra=0, e0=None, e1=None, o2=None, addend_p
     for y, add, rnd in outs:
         fl = ((_lib.LF_RING_OUT_BF16 if y.dtype == torch.bfloat16 else 0) | (_lib.LF_RING_ROUND if rnd else 0)
               | (_lib.LF_RING_ADD_BF16 if (add is not None and add.dtype == torch.bfloat16) else 0))
-        args += [_ptr(y), _ptr(add) if add is not None else None, fl]
+        args += [y, add, fl]
     if ng == 1:
         args += [None, None, 0]
     fl0 = args[2] | (8 if outs[0][1] is not None else 0)           # group 0's epilogue form, as the kernel template sees it
-    with _timed('conv3d_c16_ring_multi', f'{ng}:{extra}:{N}:{fl0}:{x.element_size()}'):
-        check(L.lf_conv3d_c16_ring_multi(_ptr(x), int(x.dtype == torch.bfloat16), _ptr(wpacks), ng, *args, extra,
-                                         _ptr(e0) if e0 is not None else None, _ptr(e1) if e1 is not None else None,
-                                         _ptr(o2) if o2 is not None else None, N, D, H, W, he, int(bool(addend_per_sample)), _stream()),
-              'lf_conv3d_c16_ring_multi')
+    launch('lf_conv3d_c16_ring_multi', x, int(x.dtype == torch.bfloat16), wpacks, ng, *args, extra, e0, e1, o2, N, D, H, W, he,
+           int(bool(addend_per_sample)), tag='conv3d_c16_ring_multi', detail=f'{ng}:{extra}:{N}:{fl0}:{x.element_size()}')
 
 
 class _GruGates(torch.autograd.Function):
@@ -572,23 +560,20 @@ class _GruGates(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, upre, rpre, h):
-        L = _lib.lib()
         upre, rpre, h = cl(upre), cl(rpre), cl(h)
         u, rh = torch.empty_like(h), torch.empty_like(h)
         C = h.shape[1]
         nvox = h.numel() // C
-        check(L.lf_gru_stage_a(_ptr(upre), _ptr(rpre), C, _ptr(h), _ptr(u), _ptr(rh), nvox, C, C, 0, _stream()), 'lf_gru_stage_a')
+        launch('lf_gru_stage_a', upre, rpre, C, h, u, rh, nvox, C, C, 0)
         ctx.save_for_backward(u, rpre, h)
         return u, rh
 
     @staticmethod
     def backward(ctx, gu, grh):
-        L = _lib.lib()
         u, rpre, h = ctx.saved_tensors
         gu, grh = cl(gu), cl(grh)
         gupre, grpre, gh = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
-        check(L.lf_gru_stage_a_bwd(_ptr(gu), _ptr(grh), _ptr(u), _ptr(rpre), _ptr(h), _ptr(gupre), _ptr(grpre), _ptr(gh),
-                                   h.numel(), _stream()), 'lf_gru_stage_a_bwd')
+        launch('lf_gru_stage_a_bwd', gu, grh, u, rpre, h, gupre, grpre, gh, h.numel())
         return gupre, grpre, gh
 
 
@@ -597,22 +582,19 @@ class _GruBlend(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, u, cand):
-        L = _lib.lib()
         h, u, cand = cl(h), cl(u), cl(cand)
         out = torch.empty_like(h)
         C = h.shape[1]
-        check(L.lf_gru_stage_b(_ptr(h), _ptr(u), _ptr(cand), _ptr(out), None, h.numel() // C, C, C, 0, _stream()), 'lf_gru_stage_b')
+        launch('lf_gru_stage_b', h, u, cand, out, None, h.numel() // C, C, C, 0)
         ctx.save_for_backward(h, u, cand)
         return out
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         h, u, cand = ctx.saved_tensors
         g = cl(g)
         gh, gu, gc = torch.empty_like(h), torch.empty_like(h), torch.empty_like(h)
-        check(L.lf_gru_stage_b_bwd(_ptr(g), _ptr(h), _ptr(u), _ptr(cand), _ptr(gh), _ptr(gu), _ptr(gc), h.numel(), _stream()),
-              'lf_gru_stage_b_bwd')
+        launch('lf_gru_stage_b_bwd', g, h, u, cand, gh, gu, gc, h.numel())
         return gh, gu, gc
 
 
@@ -622,20 +604,18 @@ class _LstmCell(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cc, c_cur):
-        L = _lib.lib()
         cc, c_cur = cl(_req(cc, 'cc')), cl(_req(c_cur, 'c'))
         Ch = c_cur.shape[1]
         if cc.shape[1] != 4 * Ch:
             raise ValueError('lstm_cell: cc must hold 4 x hidden channels')
         h, cn = torch.empty_like(c_cur), torch.empty_like(c_cur)
-        check(L.lf_lstm_cell_fwd(_ptr(cc), _ptr(c_cur), _ptr(h), _ptr(cn), c_cur.numel() // Ch, Ch, _stream()), 'lf_lstm_cell_fwd')
+        launch('lf_lstm_cell_fwd', cc, c_cur, h, cn, c_cur.numel() // Ch, Ch)
         ctx.save_for_backward(cc, c_cur)
         ctx.set_materialize_grads(False)
         return h, cn
 
     @staticmethod
     def backward(ctx, gh, gcn):
-        L = _lib.lib()
         cc, c_cur = ctx.saved_tensors
         if gh is None and gcn is None:
             return None, None
@@ -643,8 +623,7 @@ class _LstmCell(torch.autograd.Function):
         gh = cl(gh) if gh is not None else None
         gcn = cl(gcn) if gcn is not None else None
         gcc, gc = torch.empty_like(cc), torch.empty_like(c_cur)
-        check(L.lf_lstm_cell_bwd(_ptr(cc), _ptr(c_cur), _ptr(gh) if gh is not None else None, _ptr(gcn) if gcn is not None else None,
-                                 _ptr(gcc), _ptr(gc), c_cur.numel() // Ch, Ch, _stream()), 'lf_lstm_cell_bwd')
+        launch('lf_lstm_cell_bwd', cc, c_cur, gh, gcn, gcc, gc, c_cur.numel() // Ch, Ch)
         return gcc, gc
 
 
@@ -714,7 +693,6 @@ class _GruFuse(torch.autograd.Function):
 
         conv = functools.partial(_gru_conv, ac, he)
         n = zz[0].numel()
-        s = _stream()
         base = [conv(c16, pk[k][1][0], bias=(b.detach() if b is not None else None)) for k, (_, b) in enumerate(gates)]
         ctx.ring = bool(GRU_RING and ac and V >= 2 and D * H * W * 64 < 2 ** 31)
         if ctx.ring:
@@ -747,7 +725,6 @@ class _GruFuse(torch.autograd.Function):
             ring_multi(zz[1:], wz[1], he, [(CA, base[2], False)], addend_per_sample=False)
             out = empty_cl(HS[0:1].shape, zz.device)
             whu, whr = pk[0][2][0].reshape(1, 14, 16, 32), pk[1][2][0].reshape(1, 14, 16, 32)
-            L = _lib.lib()
             for i in range(1, V):
                 h, j = HS[i - 1:i], slice(i - 1, i)
                 hx = H16[j] if H16 is not None else h            # the staged operand
@@ -757,10 +734,9 @@ class _GruFuse(torch.autograd.Function):
                     ring_multi(hx, whu, he, [(UP[j], UP[j], False)])
                     ring_multi(hx, whr, he, [(RP[j], RP[j], False)], extra=_lib.LF_RING_EX_RH, e0=h if H16 is not None else None, o2=RH[j])
                 hn = HS[i:i + 1] if i < V - 1 else out
-                with _timed('conv3d_c16_ring_multi', '1:2:1:11:2'):
-                    check(L.lf_conv3d_c16_ring_blend(_ptr(RH[j]), _ptr(wh[1]), _ptr(CA[j]), _ptr(CA[j]), _ptr(h), _ptr(UP[j]), _ptr(hn),
-                                                     _ptr(H16[i:i + 1]) if (H16 is not None and i < V - 1) else None, 1, D, H, W, he, _stream()),
-                          'lf_conv3d_c16_ring_blend')
+                launch('lf_conv3d_c16_ring_blend', RH[j], wh[1], CA[j], CA[j], h, UP[j], hn,
+                       H16[i:i + 1] if (H16 is not None and i < V - 1) else None, 1, D, H, W, he, tag='conv3d_c16_ring_multi',
+                       detail='1:2:1:11:2')
             ctx.ac, ctx.T16, ctx.he, ctx.pk = ac, T16, he, pk
             ctx.blocks = [UP, RP, CA, RH, HS, H16]
             ctx.zshape = tuple(z.shape)
@@ -777,12 +753,12 @@ class _GruFuse(torch.autograd.Function):
                 del xk
             upre, rpre = pre
             rh = empty_cl16(h.shape, h.device, T16)
-            check(L.lf_gru_train_stage_a(_ptr(rpre), _ptr(h), _ptr(rh), n, int(T16), s), 'lf_gru_train_stage_a')
+            launch('lf_gru_train_stage_a', rpre, h, rh, n, int(T16))
             xo = conv(zi, pk[2][0][0], addend=base[2], out16=T16)
             cand = conv(rh, pk[2][2][0], addend=xo, out16=T16)
             del xo
             hn = empty_cl(h.shape, h.device)
-            check(L.lf_gru_train_stage_b(_ptr(h), _ptr(upre), _ptr(cand), _ptr(hn), n, int(T16), s), 'lf_gru_train_stage_b')
+            launch('lf_gru_train_stage_b', h, upre, cand, hn, n, int(T16))
             saved.append((upre, rpre, rh, cand))
             hs.append(hn)
         ctx.ac, ctx.T16, ctx.he, ctx.pk = ac, T16, he, pk
@@ -796,12 +772,10 @@ class _GruFuse(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         zz, c16, wu, wr, wo = ctx.saved_tensors
         V = zz.shape[0]
         ac, T16, he, pk = ctx.ac, ctx.T16, ctx.he, ctx.pk
         dev = zz.device
-        s = _stream()
         n = zz[0].numel()
         shape1 = (1,) + tuple(zz.shape[1:])
         D, H, W = zz.shape[2:]
@@ -845,12 +819,10 @@ class _GruFuse(torch.autograd.Function):
             upre, rpre, rh, cand = steps[i - 1]
             h = (ctx.h0 if ctx.h0 is not None else zz[0:1]) if i == 1 else hs[i - 2]
             zi = zz[i:i + 1]
-            check(L.lf_gru_train_stage_b_bwd(_ptr(g), _ptr(h), _ptr(upre), _ptr(cand), _ptr(gh1), _ptr(gupre), _ptr(gc),
-                                             _ptr(acc[0]) if need_w else None, _ptr(acc[2]) if need_w else None, n, int(T16), s),
-                  'lf_gru_train_stage_b_bwd')
+            launch('lf_gru_train_stage_b_bwd', g, h, upre, cand, gh1, gupre, gc, acc[0],
+                   acc[2], n, int(T16))
             conv(gc, pk[2][2][1], out=grh, rnd=1)
-            check(L.lf_gru_train_stage_a_bwd(_ptr(grh), _ptr(rpre), _ptr(h), _ptr(gh1), _ptr(grpre), _ptr(gh12),
-                                             _ptr(acc[1]) if need_w else None, n, int(T16), s), 'lf_gru_train_stage_a_bwd')
+            launch('lf_gru_train_stage_a_bwd', grh, rpre, h, gh1, grpre, gh12, acc[1], n, int(T16))
             if side is not None:
                 ready = torch.cuda.Event()
                 ready.record(main)                                # the three gate gradients of this step are complete
@@ -896,7 +868,6 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
     (was: two stage kernels + six convolutions + six weight-gradient launches).  The weight gradients run afterwards over the
     STORED gate gradients as multi-volume launches, in chunks of GRU_WGRAD_CHUNK steps on the side stream beside the chain;
     the sums over the steps that the bias / coordinate-channel gradients need come from lf_sum_views_bf16 over the same blocks."""
-    L = _lib.lib()
     if ctx.blocks is None:
         raise RuntimeError('the fused GRU recurrence overwrites its activations during backward: a second backward through '
                            'the same graph is not supported')
@@ -909,7 +880,6 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
     D, H, W = zz.shape[2:]
     shape1 = (1,) + tuple(zz.shape[1:])
     n = zz[0].numel()
-    s = _stream()
     # transposed packs: [o: towards r h | towards x], [u: towards x | towards h], [r: towards x | towards h]
     tp = tuple(torch.stack(p) for p in ((pk[2][2][1], pk[2][0][1]), (pk[0][0][1], pk[0][2][1]), (pk[1][0][1], pk[1][2][1])))
     gz = empty_cl16((V, 16, D, H, W), dev, True)
@@ -938,7 +908,7 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
         for k, (gp, xh) in enumerate(((UP, HX), (RP, HX), (CA, RH))):
             for q, x in enumerate((zz[lo:hi], xh[j])):
                 wg(x, gp[j], gwb[ci, k, q])
-            check(L.lf_sum_views_bf16(_ptr(gp[j]), _ptr(acc[k]), n, nv, int(ci > 0), _stream()), 'lf_sum_views_bf16')
+            launch('lf_sum_views_bf16', gp[j], acc[k], n, nv, int(ci > 0))
 
     def on_side(fn, *a):
         if side is not None:
@@ -956,8 +926,7 @@ def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
             j = slice(i - 1, i)
             h = HS[j]
             gnext = gbuf[i & 1]
-            check(L.lf_gru_train_stage_b_bwd(_ptr(g), _ptr(h), _ptr(UP[j]), _ptr(CA[j]), _ptr(gh1), _ptr(UP[j]), _ptr(CA[j]),
-                                             None, None, n, 1, s), 'lf_gru_train_stage_b_bwd')
+            launch('lf_gru_train_stage_b_bwd', g, h, UP[j], CA[j], gh1, UP[j], CA[j], None, None, n, 1)
             if two:
                 ring_multi(CA[j], tp[0], he, [(RP[j], RP[j], True), (gz[i:i + 1], None, True)], extra=_lib.LF_RING_EX_ABWD,
                            e0=h, e1=gh1, o2=gh12)
@@ -1047,7 +1016,6 @@ class _LiftFused(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, S):
-        L = _lib.lib()
         _req(x, 'x'), _req(weight, 'weight')
         ctx.ac = ops.AUTOCAST is not None
         x = _ac_in(cl(x))
@@ -1063,9 +1031,7 @@ class _LiftFused(torch.autograd.Function):
             btab = bias.detach().reshape(16, S).t().contiguous() if bias is not None else None
             vol = empty_cl16((V, c0, S, H, W), x.device, True)
             norm = torch.empty(V * P, device=x.device, dtype=torch.float32)
-            with _timed('lift16_fwd'):
-                check(L.lf_lift16_fwd(_ptr(x), _ptr(wtab), _ptr(btab) if btab is not None else None, _ptr(vol), _ptr(norm), V * P, P, S,
-                                      he, SLOPE, PN_EPS, _stream()), 'lf_lift16_fwd')
+            launch('lf_lift16_fwd', x, wtab, btab, vol, norm, V * P, P, S, he, SLOPE, PN_EPS, tag='lift16_fwd')
             ctx.dims, ctx.he = (V, cin, H, W, c0, S), he
             ctx.save_for_backward(vol, norm, weight, x)
             return vol
@@ -1075,8 +1041,7 @@ class _LiftFused(torch.autograd.Function):
         out16 = storage_bf16() and c0 == 16
         vol = empty_cl16((V, c0, S, H, W), x.device, out16)
         norm = torch.empty(V * P, device=x.device, dtype=torch.float32)
-        with _timed('lift_norm_unfold'):
-            check(L.lf_lift_norm_unfold(_ptr(tmp), _ptr(vol), _ptr(norm), V, P, c0, S, PN_EPS, int(out16), _stream()), 'lf_lift_norm_unfold')
+        launch('lf_lift_norm_unfold', tmp, vol, norm, V, P, c0, S, PN_EPS, int(out16), tag='lift_norm_unfold')
         del tmp
         ctx.dims, ctx.he = (V, cin, H, W, c0, S), he
         ctx.save_for_backward(vol, norm, weight, x)
@@ -1096,15 +1061,13 @@ class _LiftFused(torch.autograd.Function):
             gb = torch.empty(cs, device=g.device, dtype=torch.float32)
             nb = L.lf_lift16_bwd_scratch_bytes(S)
             scr = torch.empty(nb // 4 + 4, device=g.device, dtype=torch.float32)
-            with _timed('lift16_bwd'):
-                check(L.lf_lift16_bwd(_ptr(g), _ptr(vol), _ptr(norm), _ptr(x), _ptr(wtab_t), _ptr(gx), _ptr(gw), _ptr(gb), _ptr(scr, True),
-                                      scr.numel() * 4, V * P, P, S, ctx.he, SLOPE, 1, _stream()), 'lf_lift16_bwd')
+            launch('lf_lift16_bwd', g, vol, norm, x, wtab_t, gx, gw, gb, scr.data_ptr(), scr.numel() * 4, V * P, P, S, ctx.he,
+                   SLOPE, 1, tag='lift16_bwd')
             return (gx if ctx.needs_input_grad[0] else None, _ac_in(gw.reshape(w.shape)) if ctx.needs_input_grad[1] else None,
                     gb if ctx.needs_input_grad[2] else None, None)
         gp = torch.empty(V * P, cs, device=g.device, dtype=torch.float32)
         io = (1 if g.dtype == torch.bfloat16 else 0) | (2 if vol.dtype == torch.bfloat16 else 0)
-        with _timed('lift_bwd'):
-            check(L.lf_lift_bwd(_ptr(g), _ptr(vol), _ptr(norm), _ptr(gp), V, P, c0, S, SLOPE, int(ctx.ac), io, _stream()), 'lf_lift_bwd')
+        launch('lf_lift_bwd', g, vol, norm, gp, V, P, c0, S, SLOPE, int(ctx.ac), io, tag='lift_bwd')
         gx = gw = gb = None
         with autocast(ctx.ac):
             if ctx.needs_input_grad[0]:

@@ -466,8 +466,7 @@ class BatchedOptimizer:
 
     def _step_hip_adam(self, lr_rows):
         """lf_adam_step: one launch per parameter tensor (same arithmetic as the torch branch below)."""
-        from .. import _lib
-        L = _lib.lib()
+        from .. import ops
         b1, b2, eps = 0.9, 0.999, 1e-8
         bc1, bc2 = 1 - b1 ** self.t, 1 - b2 ** self.t
         dev = self.params[0].device
@@ -479,14 +478,12 @@ class BatchedOptimizer:
         host.copy_(torch.tensor([[l / bc1 for l in lr_rows], list(lr_rows)], dtype=torch.float32))
         both = host.to(dev, non_blocking=True)
         wd = 1e-2 if self.name == 'adamw' else 0.0
-        stream = torch.cuda.current_stream().cuda_stream
         for p, m, v in zip(self.params, self.m, self.v):
             if p.grad is None:
                 continue
             g = p.grad.contiguous()
-            _lib.check(L.lf_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), both[0].data_ptr(),
-                                      both[1].data_ptr(), math.sqrt(bc2), b1, b2, eps, wd, p.shape[0], p.shape[1], stream),
-                       'lf_adam_step')
+            ops.launch('lf_adam_step', p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), both[0].data_ptr(),
+                       both[1].data_ptr(), math.sqrt(bc2), b1, b2, eps, wd, p.shape[0], p.shape[1])
 
     def step(self, lr_rows):
         self.t += 1

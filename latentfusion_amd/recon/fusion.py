@@ -246,13 +246,11 @@ class GRUFuser(_ArgsFuser):
         Other widths: one channels-last record [z_i | coords | state] per voxel feeds a merged update+reset
         convolution and the out convolution; the gate arithmetic writes the state slots in place."""
         from .. import _lib, ops
-        L = _lib.lib()
         cell = self.gru
         V, C = z_obj.shape[1], z_obj.shape[2]
         D, H, W = z_obj.shape[3:]
         dev = z_obj.device
         nvox = D * H * W
-        s = torch.cuda.current_stream().cuda_stream
         gates = (cell.update_gate, cell.reset_gate, cell.out_gate)
         coords = utils.get_normalized_voxel_coords(z_obj[:, 0])
         if C == 16 and nvox * 64 < 2 ** 31:
@@ -285,13 +283,12 @@ class GRUFuser(_ArgsFuser):
                 for k in (0, 1):
                     xk = ops.conv3d_c16_wino(zi, packs(gates[k])[0], None, he, 0, prev=(base[k],) + add[1:])[0]
                     pre.append(ops.conv3d_c16_wino(h, packs(gates[k])[2], None, he, 0, prev=(xk,) + add[1:])[0])
-                _lib.check(L.lf_gru_stage_a(pre[0].data_ptr(), pre[1].data_ptr(), C, h.data_ptr(), u.data_ptr(), rh.data_ptr(),
-                                            nvox, C, C, 0, s), 'lf_gru_stage_a')
+                ops.launch('lf_gru_stage_a', pre[0].data_ptr(), pre[1].data_ptr(), C, h.data_ptr(), u.data_ptr(), rh.data_ptr(),
+                           nvox, C, C, 0)
                 xo = ops.conv3d_c16_wino(zi, packs(gates[2])[0], None, he, 0, prev=(base[2],) + add[1:])[0]
                 cand = ops.conv3d_c16_wino(rh, packs(gates[2])[2], None, he, 0, prev=(xo,) + add[1:])[0]
                 h_new = torch.empty_like(h)
-                _lib.check(L.lf_gru_stage_b(h.data_ptr(), u.data_ptr(), cand.data_ptr(), h_new.data_ptr(), None, nvox, C, C, 0, s),
-                           'lf_gru_stage_b')
+                ops.launch('lf_gru_stage_b', h.data_ptr(), u.data_ptr(), cand.data_ptr(), h_new.data_ptr(), None, nvox, C, C, 0)
                 h = h_new
             return h.unsqueeze(1)
         rec = ops.empty_cl((1, 2 * C + 3, D, H, W), dev)
@@ -306,12 +303,12 @@ class GRUFuser(_ArgsFuser):
         for i in range(1, V):
             rec[:, :C] = z_obj[:, i]
             ur = ops.conv3x3(rec, w_ur, b_ur, lrelu=False, pixelnorm=False)
-            _lib.check(L.lf_gru_stage_a(ur.data_ptr(), ur.data_ptr() + 4 * C, 2 * C, h.data_ptr(), u.data_ptr(), rec.data_ptr(),
-                                        nvox, C, 2 * C + 3, C + 3, s), 'lf_gru_stage_a')
+            ops.launch('lf_gru_stage_a', ur.data_ptr(), ur.data_ptr() + 4 * C, 2 * C, h.data_ptr(), u.data_ptr(), rec.data_ptr(),
+                       nvox, C, 2 * C + 3, C + 3)
             cand = ops.conv3x3(rec, w_o, b_o.detach() if b_o is not None else None, lrelu=False, pixelnorm=False)
             h_new = torch.empty_like(h)
-            _lib.check(L.lf_gru_stage_b(h.data_ptr(), u.data_ptr(), cand.data_ptr(), h_new.data_ptr(),
-                                        rec.data_ptr() if i + 1 < V else None, nvox, C, 2 * C + 3, C + 3, s), 'lf_gru_stage_b')
+            ops.launch('lf_gru_stage_b', h.data_ptr(), u.data_ptr(), cand.data_ptr(), h_new.data_ptr(),
+                       rec.data_ptr() if i + 1 < V else None, nvox, C, 2 * C + 3, C + 3)
             h = h_new
         return h.unsqueeze(1)
 

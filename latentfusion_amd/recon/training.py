@@ -71,13 +71,11 @@ class FlatAdam:
         bc1, bc2 = 1.0 - b1 ** self.t, 1.0 - b2 ** self.t
         dev = self.flat.data.device
         rows = torch.tensor([self.lr / bc1, self.lr], dtype=torch.float32, device=dev)
-        L = _lib.lib()
         n = self.flat.data.numel()
         if n >= 2 ** 31:
             raise ValueError('flat parameter buffer too large for one launch')
-        _lib.check(L.lf_adam_step(self.flat.data.data_ptr(), self.flat.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
-                                  rows[0:1].data_ptr(), rows[1:2].data_ptr(), math.sqrt(bc2), b1, b2, self.eps,
-                                  self.weight_decay, 1, n, torch.cuda.current_stream().cuda_stream), 'lf_adam_step')
+        ops.launch('lf_adam_step', self.flat.data.data_ptr(), self.flat.grad.data_ptr(), self.m.data_ptr(), self.v.data_ptr(),
+                   rows[0:1].data_ptr(), rows[1:2].data_ptr(), math.sqrt(bc2), b1, b2, self.eps, self.weight_decay, 1, n)
         ops.invalidate_weight_packs()                     # the kernel wrote the weights behind torch's back
 
 
