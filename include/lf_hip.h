@@ -829,6 +829,77 @@ int lf_depth_init(const float* depth, const void* mask, int mask_u8, const float
                   float* trans, float* stats, int* counts, void* scratch, size_t scratch_bytes, int B, int H, int W,
                   void* stream);
 
+/* ---- evaluation point clouds from depth maps (csrc/depth_points.hip) ------------------------------------------------------------
+ * Observation.pointcloud (reference observation.py:292-316 over pointcloud.py:57-79 project_pointcloud / compute_point_mask):
+ * back-projection of the viewport lattice, segmentation by re-projection into the mask, ordered compaction.
+ *   depth [B][H][W] fp32; mask [B][H][W], fp32 (mask_u8 = 0) or bytes (mask_u8 = 1), foreground iff != 0, NULL allowed with
+ *   segment = 0; color [B][3][H][W] fp32 or NULL (colors is then NULL too); cams [B][LF_DEPTH_CAM_FLOATS], one record per view,
+ *   formed by the caller in fp64 from the camera and rounded once:
+ *     [0] vx, [1] vy (viewport xmin, ymin), [2] vw, [3] vh (viewport width, height), [4] fu, [5] fv, [6] u0, [7] v0,
+ *     [8..19] cam_to_obj, [20..31] obj_to_image, both 3x4 row-major.
+ *   points [cap][3], colors [cap][3] or NULL, index [cap] int32 or NULL, counts [B] int32; cap = B * H * W.
+ * Per pixel (b, y, x) with z = depth[b][y][x], every step ONE correctly rounded fp32 operation in this order:
+ *   1. u = fmaf(vw, x / (W - 1), vx), and u = vx for W = 1; v = fmaf(vh, y / (H - 1), vy), v = vy for H = 1.
+ *   2. px = ((u - u0) / fu) * z, py = ((v - v0) / fv) * z, pz = z: a subtraction, a division, a multiplication.
+ *   3. to_object = 1: (px, py, pz) <- rows of cam_to_obj, each fmaf(t0, px, fmaf(t1, py, fmaf(t2, pz, t3))); to_object = 0 keeps
+ *      the camera-frame point.
+ *   4. segment = 1: (h0, h1, h2) = rows of obj_to_image applied to the point of step 3 by the same chain -- whatever to_object
+ *      is, as the reference does -- and u' = h0 / h2, v' = h1 / h2.  The pixel is kept iff z != 0, both quotients are finite,
+ *      trunc(u') in [0, frame_w), trunc(v') in [0, frame_h) and mask[b][trunc(v')][trunc(u')] != 0 (trunc: toward zero, so
+ *      -1 < u' < 0 reads column 0, as .long() does).
+ * ZERO DEPTH: a pixel whose depth is exactly 0 is never kept under segment.  This is the one departure from the reference,
+ * where such a pixel back-projects to the camera centre and its re-projection is 0/0 in exact arithmetic: rounding noise in
+ * fp32 (finite garbage of a few pixels), so the reference keeps or drops it by accident.
+ * Output: the kept pixels' points in the order of their source index b * H * W + y * W + x (view-major, then row-major), packed
+ * from row 0; index[row] = that source index, colors[row] = color[b][0..2][y][x]; counts[b] = kept pixels of view b.  Rows from
+ * sum(counts) on are not written.  segment = 0: every pixel is written at its own index, counts[b] = H * W, one launch.
+ * Compaction without atomics: launch 1 writes the kept count of every chunk of 1024 consecutive pixels of a view into scratch;
+ * launch 2 adds up the counts of the chunks before its own in a fixed order, ranks its kept pixels by a wave ballot and writes
+ * the rows.  points, colors, index and counts are bit-identical from run to run, and a view's rows depend on that view alone
+ * (the other views only shift them).
+ * Domain: B, H, W >= 1, B * H * W < 2^31, mask_u8, to_object, segment in {0, 1}, color and colors both given or both NULL,
+ * required pointers (depth, cams, points, counts; mask with segment) not NULL, and with segment (frame_h, frame_w) == (H, W) --
+ * the reference indexes the H x W mask with frame pixels and raises IndexError otherwise (else LF_EINVAL); every pointer
+ * 4-byte aligned (LF_EALIGN); with segment, fewer than lf_depth_points_scratch_bytes(B, H, W) bytes of scratch is LF_ENOSPC (the
+ * query returns 0 outside the domain).  Nothing is launched or written in any of these cases. */
+#define LF_DEPTH_CAM_FLOATS 32
+size_t lf_depth_points_scratch_bytes(int B, int H, int W);
+int lf_depth_points(const float* depth, const void* mask, int mask_u8, const float* color, const float* cams, float* points,
+                    float* colors, int* index, int* counts, void* scratch, size_t scratch_bytes, int B, int H, int W, int frame_w,
+                    int frame_h, int to_object, int segment, void* stream);
+
+/* ---- farthest-point sampling (csrc/fps.hip) -------------------------------------------------------------------------------------
+ * Greedy farthest-point sampling of B clouds (reference three/utils.py:4-49 farthest_points with F.pairwise_distance, as
+ * tools/dataset/moped_eval_pointclouds.py and the BOP / RealSense readers call it).  x: packed xyz fp32 rows [B][N][3], x_sb the
+ * batch stride in floats, 0 shares one cloud (as lf_nn_dist).  centers [B][K] int32, owner [B][N] int32, nearest [B][N] fp32;
+ * each may be NULL, not all three.
+ * Arithmetic, every operation one correctly rounded fp32 operation, never contracted:
+ *   d^2(i, c) = (dx * dx + dy * dy) + dz * dz, dx = x_i - x_c (direct differences, as lf_nn_dist; NOT F.pairwise_distance,
+ *   which adds 1e-6 to every coordinate difference: the two agree except at near-ties).
+ *   min_i starts at 1e14f (the reference's 1e7, squared) and is held on d^2.
+ *   pick k = the SMALLEST index among the maxima of min before update k (so pick 0 is row 0); centers[b][k] = pick k.
+ *   update k: owner[i] = k whenever d^2(i, pick k) <= min_i (the last centre that attains the minimum wins, as
+ *   clusters[distances == new_distances] = i does), then min_i = min(min_i, d^2).
+ *   nearest[i] = sqrt(min_i) after the K updates, one correctly rounded root.
+ * The maximum is exact and ties go to the smallest index, so no reduction order shows: the two forms give the same bits.
+ *   form 1, resident: one workgroup per cloud, the coordinates and running minima in LDS (16 bytes per point) for all K picks of
+ *     ONE launch, one workgroup barrier per pick.  N <= LF_FPS_RESIDENT_MAX = (160 KiB - 256 bytes of reduction slots) / 16;
+ *     above that form 1 is LF_EINVAL.  No scratch.
+ *   form 2, streamed: any N.  One launch per pick over ceil(N / 1024) workgroups per cloud; each first reduces the previous
+ *     launch's per-workgroup partial maxima from scratch in a fixed order (so all derive the same pick), updates its slice of
+ *     the running minima (in scratch) and writes its own partial.  K launches, and one more that takes the roots when nearest
+ *     is asked for, queued back to back.
+ *   form 0: resident iff N <= LF_FPS_RESIDENT_MAX -- by N alone, so a cloud's result and path do not depend on B.
+ * No kernel waits for another workgroup.  NaN / infinite coordinates and differences beyond 1e7 are outside the contract: no
+ * fault, result unspecified.
+ * Domain: B >= 1, 1 <= K <= N, B * N < 2^31, x_sb >= 0, form in {0, 1, 2} (else LF_EINVAL); every pointer 4-byte aligned
+ * (LF_EALIGN); the streamed form with fewer than lf_farthest_points_scratch_bytes(B, N, K, form) bytes of scratch is LF_ENOSPC
+ * (the query returns 0 for the resident form and outside the domain).  Nothing is launched or written in any of these cases. */
+#define LF_FPS_RESIDENT_MAX 10224
+size_t lf_farthest_points_scratch_bytes(int B, int N, int K, int form);
+int lf_farthest_points(const float* x, long x_sb, int* centers, int* owner, float* nearest, void* scratch, size_t scratch_bytes,
+                       int B, int N, int K, int form, void* stream);
+
 /* ---- training losses (csrc/train_loss.hip) --------------------------------------------------------------------------------------
  * The loss tail of the generator's training step in three launches forward and one backward, no device-to-host copy, no float
  * atomics (reference losses.py:33-57 HardPixelLoss, losses.py:94-99 beta_prior_loss, train_reconstruct.py:491-521 the terms).

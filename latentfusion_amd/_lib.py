@@ -24,7 +24,9 @@ LF_MAP_COEFS = 20
 LF_FUSE_MEAN, LF_FUSE_MAX, LF_FUSE_ABSMAX, LF_FUSE_MEDIAN = 0, 1, 2, 3
 LF_IBR_PAIR_FLOATS, LF_IBR_PAIR_SPLIT, LF_IBR_VIEW_FLOATS, LF_IBR_VIEW_SPLIT = 32, 16, 16, 8   # camera records of lf_ibr_reproject_*
 LF_OBS_PREPARE, LF_OBS_NORMALIZE = 1, 2   # stages of lf_obs_prepare
-LF_AMAX_FLOATS = 2048          # floats of a max-abs side-channel buffer (include/lf_hip.h)
+LF_DEPTH_CAM_FLOATS = 32      # camera record of lf_depth_points
+LF_FPS_RESIDENT_MAX = 10224   # largest cloud of lf_farthest_points' resident form
+LF_AMAX_FLOATS = 2048         # floats of a max-abs side-channel buffer (include/lf_hip.h)
 
 P = c_void_p
 # name -> (restype, argtypes); mirrors include/lf_hip.h one to one (the product ABI)
@@ -152,6 +154,10 @@ SIGNATURES = {
     'lf_points_pair_dist': (c_int, [P, c_long, P, P, c_int, P, P, c_size_t, c_int, c_int, P]),
     'lf_depth_init_scratch_bytes': (c_size_t, [c_int, c_int, c_int]),
     'lf_depth_init': (c_int, [P, P, c_int, P, c_int, c_float, c_int, P, P, P, P, c_size_t, c_int, c_int, c_int, P]),
+    'lf_depth_points_scratch_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'lf_depth_points': (c_int, [P, P, c_int, P, P, P, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'lf_farthest_points_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int]),
+    'lf_farthest_points': (c_int, [P, c_long, P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, P]),
     'lf_recon_loss_scratch_bytes': (c_size_t, [c_int, c_int, c_int, c_int, c_long]),
     'lf_recon_loss_fwd': (c_int, [P, P, c_int, c_int, P, P, c_float, c_float, c_float, P, P, P, P, P, c_size_t, c_int, c_int,
                                   c_int, c_int, c_long, P]),

@@ -19,7 +19,8 @@ def gan_denormalize(t):
 
 KERNELS = ('composed', 'fused')
 KERNEL = 'composed'        # what Observation.zoom runs when kernel is None: 'composed' (Camera.zoom per map: the reference's host loop
-#                            over the frames around lf_grid_sample2d_fwd) or 'fused' (one ops.observation_prepare call, device tensors only)
+#                            over the frames around lf_grid_sample2d_fwd) or 'fused' (one ops.observation_prepare call, device tensors only);
+#                            Observation.pointcloud and pointcloud.eval_points resolve through it too ('fused': ops.depth_points)
 
 
 def _resolve_kernel(kernel):
@@ -202,6 +203,39 @@ class Observation:
         _resolve_kernel(zoom_kernel)
         return self.zoom(target_dist, target_size, camera=self.estimate_camera(kernel=kernel, erode_radius=erode_radius),
                          kernel=zoom_kernel)
+
+    def pointcloud(self, frame='object', return_colors=False, segment=True, kernel=None):
+        """The views' depth maps as one cloud (reference :292-316): the viewport lattice back-projected by
+        Camera.depth_object_coords (frame='object') or depth_camera_coords (anything else), (n,3), view-major then row-major
+        [, the colours of the same pixels, (n,3)].  segment=True keeps the points that pointcloud.compute_point_mask keeps:
+        re-projected with camera.obj_to_image WHATEVER the frame, inside camera.width x camera.height, on a set pixel of the
+        mask (read at the truncated pixel).  kernel: None (the module's KERNEL) | 'composed' | 'fused' (one ops.depth_points
+        call, device tensors only; its one device-to-host copy is the point count, where the composed path's boolean indexing
+        has one too; a pixel of depth exactly 0 is never kept there -- include/lf_hip.h says why)."""
+        if _resolve_kernel(kernel) == 'fused':
+            return self._pointcloud_fused(frame, return_colors, segment)
+        from .pointcloud import compute_point_mask
+        lattice = self.camera.depth_object_coords if frame == 'object' else self.camera.depth_camera_coords
+        points = torch.stack(lattice(self.depth), dim=-1).reshape(len(self), -1, 3)
+        keep = compute_point_mask(self.camera, self.mask, points) if segment else None
+        points = points[keep] if segment else points.reshape(-1, 3)
+        if not return_colors:
+            return points
+        colors = self.color.permute(0, 2, 3, 1).reshape(len(self), -1, 3)
+        return points, (colors[keep] if segment else colors.reshape(-1, 3))
+
+    def _pointcloud_fused(self, frame, return_colors, segment):
+        from . import ops
+        tensors = [t for t in (self.color if return_colors else None, self.depth, self.mask) if t is not None]
+        if not all(t.is_cuda for t in tensors):
+            if not torch.cuda.is_available():
+                raise RuntimeError("kernel 'fused' needs a GPU: the point-cloud HIP kernel has no CPU form (use kernel='composed')")
+            raise ValueError("kernel='fused' needs device tensors (move the observation with .to(device); the composed path "
+                             "serves host tensors)")
+        out = ops.depth_points(self.depth, self.mask if segment else None, self.camera, color=self.color if return_colors else None,
+                               frame='object' if frame == 'object' else 'camera', segment=bool(segment))
+        n = int(out['counts'].sum())                                 # the one device-to-host copy
+        return (out['points'][:n], out['colors'][:n]) if return_colors else out['points'][:n]
 
     def uncrop(self, camera=None):
         camera = self.camera if camera is None else camera

@@ -1079,6 +1079,140 @@ def depth_init(depth, mask, intrinsic=None, m=3.0, erode_radius=0):
     return out
 
 
+def pack_depth_cameras(camera):
+    """Host packing of the camera records of `depth_points` (layout: include/lf_hip.h), one per view: viewport origin and
+    extent, fu, fv, u0, v0, the 3x4 cam_to_obj and the 3x4 obj_to_image.  Everything is formed in fp64 from the Camera's state,
+    view by view (a record does not depend on its batch mates), and rounded once to fp32, as pack_ibr_cameras does.  A camera on
+    the device is read back for this (four small tensors); pack once and pass the records where that copy matters.
+    -> (B, LF_DEPTH_CAM_FLOATS) float32 on the camera's device."""
+    c = camera._map(lambda t: t.detach().to('cpu', torch.float64))
+    n = len(c)
+    rot, t = c.rotation_matrix[:, :3, :3], c.translation
+    ext = torch.zeros(n, 4, 4, dtype=torch.float64)
+    ext[:, :3, :3], ext[:, :3, 3], ext[:, 3, 3] = rot, t, 1.0                                   # obj_to_cam
+    rec = torch.zeros(n, _lib.LF_DEPTH_CAM_FLOATS, dtype=torch.float64)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = c.viewport[:, 0], c.viewport[:, 1], c.viewport_width, c.viewport_height
+    rec[:, 4], rec[:, 5], rec[:, 6], rec[:, 7] = c.fu, c.fv, c.u0, c.v0
+    inv = torch.cat((rot.transpose(1, 2), -sum(rot[:, k, :] * t[:, k, None] for k in range(3))[:, :, None]), dim=2)
+    rec[:, 8:20] = inv.reshape(n, 12)                                                           # cam_to_obj
+    rec[:, 20:32] = _mm4(c.intrinsic, ext).reshape(n, 12)                                       # obj_to_image
+    return rec.to(torch.float32).to(camera.device)
+
+
+DEPTH_FRAMES = ('object', 'camera')
+
+
+def depth_points(depth, mask, camera, color=None, frame='object', segment=True, want_index=False):
+    """Back-projection of B depth maps to points, segmentation by re-projection into the mask and ordered compaction in one
+    call (lf_depth_points; Observation.pointcloud).  depth (B,1,H,W) or (B,H,W) float32; mask the same shape, float32, bool or
+    uint8 (foreground iff != 0), None allowed without segment; camera: a Camera of B views or the records of
+    pack_depth_cameras; color: None or (B,3,H,W) float32; frame: 'object' | 'camera' (the points' frame; the segmentation
+    re-projects them with obj_to_image either way, as the reference does).  A pixel of depth exactly 0 is never kept under
+    segment (the one departure from the reference, where its re-projection is rounding noise).
+    -> {'points': (B*H*W, 3), 'counts': (B,) int32, 'colors': (B*H*W, 3) with color, 'index': (B*H*W,) int32 with want_index}:
+    the kept points packed from row 0 in view-major, row-major order, sum(counts) rows valid, the rest unwritten.  Nothing here
+    synchronises; the caller reads counts when it needs the total."""
+    from .modules.geometry import Camera
+    if frame not in DEPTH_FRAMES:
+        raise ValueError(f'frame must be one of {DEPTH_FRAMES}, got {frame!r}')
+    if not isinstance(segment, bool) or not isinstance(want_index, bool):
+        raise ValueError('segment and want_index must be bool')
+    d3 = _frames_arg(depth, 'depth', (torch.float32,))
+    B, H, W = d3.shape
+    k3 = None
+    if mask is not None:
+        k3 = _frames_arg(mask, 'mask', (torch.float32, torch.bool, torch.uint8))
+        if tuple(k3.shape) != tuple(d3.shape):
+            raise ValueError(f'depth and mask differ in shape: {tuple(depth.shape)} and {tuple(mask.shape)}')
+        if k3.device != d3.device:
+            raise ValueError('depth and mask must be on one device')
+    elif segment:
+        raise ValueError('segment=True needs a mask')
+    if B * H * W >= 2 ** 31:
+        raise ValueError(f'{B} x {H} x {W} pixels: at most 2^31 - 1 per call')
+    if color is not None:
+        if not isinstance(color, torch.Tensor) or not color.is_cuda or color.device != d3.device:
+            raise ValueError('color must be a device tensor on the device of depth')
+        if color.dtype != torch.float32 or tuple(color.shape) != (B, 3, H, W):
+            raise ValueError(f'color must be float32 and shaped ({B}, 3, {H}, {W}), got {color.dtype} {tuple(color.shape)}')
+    if isinstance(camera, Camera):
+        if len(camera) != B:
+            raise ValueError(f'camera holds {len(camera)} views, depth {B}')
+        frame_w, frame_h = int(camera.width), int(camera.height)
+        if segment and (frame_h, frame_w) != (H, W):
+            raise ValueError(f'segment=True indexes the {H} x {W} mask with pixels of the {frame_h} x {frame_w} frame: the two '
+                             f'must be equal')
+        cams = pack_depth_cameras(camera).to(d3.device)
+    else:
+        cams = _points_arg(camera, 'camera', (B, _lib.LF_DEPTH_CAM_FLOATS), (2,))
+        if cams.device != d3.device:
+            raise ValueError('the camera records must be on the device of depth')
+        frame_w, frame_h = W, H
+    L = _lib.lib()
+    dev = d3.device
+    d3 = _aligned4(d3)
+    u8 = k3 is not None and k3.dtype != torch.float32
+    if k3 is not None:
+        k3 = _aligned4(k3.view(torch.uint8) if k3.dtype == torch.bool else k3)
+    cap = B * H * W
+    points = torch.empty(cap, 3, device=dev, dtype=torch.float32)
+    colors = torch.empty(cap, 3, device=dev, dtype=torch.float32) if color is not None else None
+    index = torch.empty(cap, device=dev, dtype=torch.int32) if want_index else None
+    counts = torch.empty(B, device=dev, dtype=torch.int32)
+    nbytes = L.lf_depth_points_scratch_bytes(B, H, W)
+    scratch = torch.empty(nbytes // 4 + 4, device=dev, dtype=torch.int32)
+    launch('lf_depth_points', d3, k3, int(u8), color.contiguous() if color is not None else None, cams.contiguous(), points, colors,
+           index, counts, scratch.data_ptr(), scratch.numel() * 4, B, H, W, frame_w, frame_h, int(frame == 'object'), int(segment),
+           tag='depth_points', detail=f'{B}x{H}x{W}')
+    out = {'points': points, 'counts': counts}
+    if colors is not None:
+        out['colors'] = colors
+    if index is not None:
+        out['index'] = index
+    return out
+
+
+FPS_FORMS = {'auto': 0, 'resident': 1, 'streamed': 2}
+
+
+def farthest_points(points, k, want=('centers',), form='auto'):
+    """Greedy farthest-point sampling of one cloud (N,3) or B clouds (B,N,3), device float32 (lf_farthest_points): pick 0 is
+    row 0, pick j the smallest index among the rows farthest from picks 0..j-1, distances from direct coordinate differences in
+    fp32 (not F.pairwise_distance's, which adds 1e-6 to every difference: the picks agree except at near-ties).  want: any of
+    'centers' (B,k) int32, 'owner' (B,N) int32 -- the LAST pick that attains a row's minimum distance -- and 'nearest' (B,N),
+    that distance; -> a dict of them (without the batch dimension for an (N,3) cloud).  form: 'auto' (by N alone) | 'resident'
+    (one workgroup per cloud, one launch; N <= LF_FPS_RESIDENT_MAX) | 'streamed' (one launch per pick): the same bits."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ('centers', 'owner', 'nearest') for w in want):
+        raise ValueError("want must name some of 'centers', 'owner', 'nearest'")
+    if form not in FPS_FORMS:
+        raise ValueError(f'form must be one of {tuple(FPS_FORMS)}, got {form!r}')
+    _points_arg(points, 'points', (3,), (2, 3))
+    batched = points.dim() == 3
+    B, N = (points.shape[0], points.shape[1]) if batched else (1, points.shape[0])
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= N:
+        raise ValueError(f'k must be an integer in 1..{N}, got {k!r}')
+    if form == 'resident' and N > _lib.LF_FPS_RESIDENT_MAX:
+        raise ValueError(f"form='resident' takes at most {_lib.LF_FPS_RESIDENT_MAX} points per cloud, got {N}")
+    if B * N >= 2 ** 31:
+        raise ValueError(f'{B} x {N} points: at most 2^31 - 1 per call')
+    if batched and B > 1 and points.stride(0) == 0:               # an expanded cloud stays one cloud (batch stride 0)
+        x, stride = points[0].contiguous(), 0
+    else:
+        x, stride = points.contiguous(), N * 3
+    L = _lib.lib()
+    dev = x.device
+    centers = torch.empty(B, k, device=dev, dtype=torch.int32) if 'centers' in want else None
+    owner = torch.empty(B, N, device=dev, dtype=torch.int32) if 'owner' in want else None
+    nearest = torch.empty(B, N, device=dev, dtype=torch.float32) if 'nearest' in want else None
+    nbytes = L.lf_farthest_points_scratch_bytes(B, N, k, FPS_FORMS[form])
+    scratch = torch.empty(nbytes // 4 + 4, device=dev, dtype=torch.float32)
+    launch('lf_farthest_points', x, stride, centers, owner, nearest, scratch.data_ptr(), scratch.numel() * 4, B, N, k,
+           FPS_FORMS[form], tag='farthest_points', detail=f'{B}x{N}x{k}')
+    out = {'centers': centers, 'owner': owner, 'nearest': nearest}
+    return {w: (out[w] if batched else out[w][0]) for w in want}
+
+
 OBS_STACKS = (None, 'color_mask', 'color_depth_mask')
 
 
