@@ -122,7 +122,9 @@ def __getattr__(name):
     """`ops.<name>` for the operators that live in ops_train.py (training step: weight gradients, bf16-storage layers, the
     fused ConvGRU recurrence / lift) and experimental.py (A/B and superseded kernels, include/lf_hip_experimental.h)."""
     import importlib
-    for mod in ('ops_train', 'experimental'):
+    if name.startswith('__'):                                 # (the import system probing `__path__`: not an operator, and the modules
+        raise AttributeError(name)                            # below import names from this one while they load)
+    for mod in ('ops_train', 'gru_train', 'experimental'):
         m = importlib.import_module('.' + mod, __package__)
         if name in m.__dict__:
             return m.__dict__[name]

@@ -1,9 +1,8 @@
 """Operators of the TRAINING step (BASELINE cfg 5; reference tools/train/train_reconstruct.py:421-535) on top of ops.py:
-weight / bias gradients, the 16 -> 16 layers and resampler under the bf16 autocast + storage policy, the ConvGRU fuser as one
-autograd node, the fused lift.  Reached through `ops.<name>` (ops.__getattr__) and through ops' dispatchers (conv3x3, conv1x1,
-resample_*, lift), which pick these forms when a gradient is wanted / the policy is on."""
+weight / bias gradients, the 16 -> 16 layers and resampler under the bf16 autocast + storage policy, the per-gate ConvGRU / LSTM
+functions, the fused lift (the ConvGRU fuser as one autograd node: gru_train.py).  Reached through `ops.<name>` (ops.__getattr__)
+and through ops' dispatchers (conv3x3, conv1x1, resample_*, lift), which pick these forms when a gradient is wanted / the policy is on."""
 import contextlib
-import functools
 import math  # noqa: F401
 
 import torch
@@ -27,17 +26,11 @@ def _env(name, default):
     return type(default)(int(_os.environ.get('LF_' + name, int(default))))
 
 
-# the ConvGRU recurrence on the ring kernels with fused epilogues (csrc/conv_gru.hip); False: round 5's one-output kernels + stage
-# kernels (kept: fp32 storage / no autocast take that path anyway)
+# the ConvGRU recurrence (gru_train.py) on the ring kernels with fused epilogues (csrc/conv_gru.hip); False: round 5's one-output
+# kernels + stage kernels (kept: fp32 storage / no autocast take that path anyway)
 GRU_RING = _env('GRU_RING', True)
-# 1: one-output launches on the sequential chain (two workgroups per CU overlap their phases), everything that does not depend
-# on the state batched over the views before / after the loop; 2: two outputs per staged halo (one 8-wave workgroup per CU --
-# measured slower: its waves run in lock-step, profiles/r06_gru_ring_probe.json)
-GRU_RING_GROUPS = _env('GRU_RING_GROUPS', 1)
 # steps per multi-volume weight-gradient launch of the recurrence on the side stream (0: one launch over all steps, after the chain)
 GRU_WGRAD_CHUNK = _env('GRU_WGRAD_CHUNK', 16)
-# a bf16 copy of the recurrent state for the staged operands: bit-identical, measured -0.2 ms for +1.9 GB: off
-GRU_STATE_BF16 = _env('GRU_STATE_BF16', False)
 RING_BLOCK_FWD = _env('RING_BLOCK_FWD', True)          # forward Block steps on ring_multi (LF_RING_EX_BLOCK, bit-identical)
 RING_DGRAD = _env('RING_DGRAD', True)                  # data gradients of the 16 -> 16 layers on ring_multi (bit-identical)
 CHAIN_EPILOGUE = _env('CHAIN_EPILOGUE', True)          # a Block's conv2 data gradient applies conv1's epilogue backward (LF_RING_EX_PREV)
@@ -46,14 +39,52 @@ PW16 = _env('PW16', True)                              # 1x1x1 16 -> 16 layers o
 WIDE_WGRAD = _env('WIDE_WGRAD', True)                  # weight gradients with Cin, Cout >= 64 on the LDS-staged MFMA kernel (csrc/wgrad_wide.hip)
 
 
-_SIDE = {}
+class _SideWgrad:
+    """Weight-gradient launches on the side stream beside the data-gradient chain of the current stream (`main`): the one place of
+    the training step that makes events, waits across streams and calls record_stream.  On when WGRAD_STREAM is set, work is
+    `wanted` and no KERNEL_TIMER runs (its events time the current stream); off, `run` launches inline and the rest does nothing.
+    The allocator recycles a tensor by main's order alone: every tensor a side launch touches must be named to `begin` or `run`."""
 
+    _streams = {}                                                 # device -> its side stream
 
-def side_stream(device):
-    st = _SIDE.get(device)
-    if st is None:
-        st = _SIDE[device] = torch.cuda.Stream(device=device)
-    return st
+    def __init__(self, device, wanted=True):
+        self.main = torch.cuda.current_stream()
+        self.on = bool(WGRAD_STREAM and wanted and ops.KERNEL_TIMER is None)
+        if self.on and device not in self._streams:
+            self._streams[device] = torch.cuda.Stream(device=device)
+        self.side = self._streams[device] if self.on else None
+
+    def begin(self, *long_lived):
+        """The side stream waits for what main has enqueued (the allocation and zero fill of `long_lived`: what several runs touch)."""
+        if self.on:
+            self.side.wait_stream(self.main)
+            for t in long_lived:
+                t.record_stream(self.side)
+
+    def run(self, fn, *keep, timed=None):
+        """fn() on the side stream once what main has enqueued so far is complete, `keep` (what it touches beyond `begin`'s tensors)
+        alive until it finishes; returns the completion event for `wait`.  Off: fn() here, inside _timed(*timed) if given; None."""
+        if not self.on:
+            with _timed(*timed) if timed else contextlib.nullcontext():
+                fn()
+            return None
+        self.side.wait_stream(self.main)
+        for t in keep:
+            t.record_stream(self.side)
+        with torch.cuda.stream(self.side):
+            fn()
+            done = torch.cuda.Event()
+            done.record(self.side)
+        return done
+
+    def wait(self, done):
+        """main waits for a `run`: before it reads what that wrote or rewrites what that read (None: nothing to wait for)."""
+        if done is not None:
+            self.main.wait_event(done)
+
+    def join(self):
+        if self.on:
+            self.main.wait_stream(self.side)
 
 
 class _SplitViews(torch.autograd.Function):
@@ -138,6 +169,11 @@ def _resample_ac_ok(vol, coef):
     return (vol.dim() == 5 and vol.shape[1] == 16 and vol.is_cuda and not coef.requires_grad and ops.DETERMINISTIC_SPLAT
             and (vol.dtype == torch.bfloat16 or storage_bf16()) and vol.shape[2] * vol.shape[3] * vol.shape[4] * 64 < 0xffffffff
             and max(vol.shape[2:]) < 0x7fff)
+
+
+def ring_multi_ok(D, H, W):
+    """lf_conv3d_c16_ring_multi takes this volume: 32-bit byte offsets within a sample of 64 B records."""
+    return D * H * W * 64 < 2 ** 31
 
 
 def _geom(t, dims):
@@ -342,7 +378,7 @@ class _Conv16AC(torch.autograd.Function):
             b_ = bias.detach() if bias is not None else None
             launch('lf_pw16_fwd', x, 1 if x.dtype == torch.bfloat16 else 0, wq, b_, he, flags, SLOPE, y, x.numel() // 16,
                    tag='pw16_fwd', detail=f'{x.shape[0]}:{x.dtype == torch.bfloat16}')
-        elif RING_BLOCK_FWD and flags == (LF_EPI_LRELU | LF_EPI_PIXELNORM) and x.shape[2] * x.shape[3] * x.shape[4] * 64 < 2 ** 31:
+        elif RING_BLOCK_FWD and flags == (LF_EPI_LRELU | LF_EPI_PIXELNORM) and ring_multi_ok(*x.shape[2:]):
             # the same arithmetic on the one-group ring kernel with its epilogue at compile time (LF_RING_EX_BLOCK): bit-identical
             pack = _pk(weight, 'a3f', lambda t: pack_conv3d_c16_ring_bf16(w3(t)))
             y = empty_cl16(tuple(x.shape), x.device, True)
@@ -363,7 +399,7 @@ class _Conv16AC(torch.autograd.Function):
             ctx.box = _chain_box()
             y._lf_link = (norm, ctx.box)
         ctx.link = None
-        if link is not None and x.dtype == torch.bfloat16 and need_w and not one and x.shape[2] * x.shape[3] * x.shape[4] * 64 < 2 ** 31:
+        if link is not None and x.dtype == torch.bfloat16 and need_w and not one and ring_multi_ok(*x.shape[2:]):
             ctx.link = link                                       # (norm of the producer, its box)
         return y
 
@@ -373,85 +409,91 @@ class _Conv16AC(torch.autograd.Function):
         gy = cl(gy)
         want_b = ctx.needs_input_grad[2]
         pw_bwd = ctx.pw and ctx.flags == 0 and gy.dtype == torch.bfloat16 and ctx.needs_input_grad[0]
-        if pw_bwd:
-            gp, gb = gy, None                                     # no activation: the pre-activation gradient IS gy; the bias sums ride in lf_pw16_bwd
-        elif ctx.box is not None and _chain_take(ctx.box) is not None:
-            gp, gb = _chain_epilogue_bwd(ctx, gy, y, norm, want_b)
-        elif ctx.flags == 0 and not want_b and gy.dtype == torch.bfloat16:
-            gp, gb = gy, None
-        else:
-            gp, gb = epilogue_bwd_c16(gy, y, norm, ctx.flags, want_b)
-        gx = gw = gwt = None
-        w3 = (lambda t: pack_center_tap(t)) if ctx.one else (lambda t: t)
+        gp, gb = _Conv16AC._preact_grad(ctx, gy, y, norm, want_b, pw_bwd)
+        gx = gw = None
         with autocast(True):
-            fast = ctx.needs_input_grad[1] and _wgrad_bf16_ok(gp, 3, 16, 16)
-            side = done = None
-            if fast:
-                # the weight gradient first, on the side stream (WGRAD_STREAM): it then runs beside the data gradient below
-                N, D, H, W, _ = _geom(gp, 3)
-                gwt = torch.empty(27, 16, 16, device=gp.device, dtype=torch.float32)
-                wg = _Wgrad(3, N, D, H, W, 16, 16, gp.device, ctx.he, bf16=True)
-                io = (1 if x_saved.dtype == torch.bfloat16 else 0) | 2
-                main = torch.cuda.current_stream()
-                if WGRAD_STREAM and ops.KERNEL_TIMER is None:
-                    side = side_stream(gp.device)
-                    side.wait_stream(main)                    # gp (and the allocations above) are ready
-                with torch.cuda.stream(side) if side is not None else _timed('wgrad3d_c16_bf16', f'{N}:io{io}'):
-                    wg(x_saved, gp, gwt)
-                    if side is not None:
-                        done = torch.cuda.Event()
-                        done.record(side)
-                        for t in (x_saved, gp, gwt, wg.scratch):
-                            t.record_stream(side)
-            if ctx.needs_input_grad[0] and ctx.pw and gp.dtype == torch.bfloat16:
-                # pointwise data gradient (+ this layer's bias gradient when nothing ran before it): one streamed pass
-                L = _lib.lib()
-                wtq = _pk(w, 'p1b', lambda t: t.detach().reshape(16, 16).t().to(torch.bfloat16).contiguous())
-                rows = gp.numel() // 16
-                out16 = ctx.xdtype == torch.bfloat16
-                gx = torch.empty_like(gp, dtype=torch.bfloat16 if out16 else torch.float32, memory_format=torch.preserve_format)
-                need_gb = pw_bwd and want_b
-                if need_gb:
-                    gb = torch.empty(16, device=gp.device, dtype=torch.float32)
-                    nb = L.lf_pw16_bwd_scratch_bytes(rows)
-                    scr = torch.empty(nb // 4 + 4, device=gp.device, dtype=torch.float32)
-                launch('lf_pw16_bwd', gp, wtq, ctx.he, gx, 1 if out16 else 0, gb if need_gb else None,
-                       scr.data_ptr() if need_gb else None, scr.numel() * 4 if need_gb else 0, rows, tag='pw16_bwd',
-                       detail=f'{gp.shape[0]}:{out16}')
-            elif ctx.needs_input_grad[0]:
-                pack_t = _pk(w, 'a3b', lambda t: pack_conv3d_c16_ring_bf16(w3(t), transpose=True))
-                if ctx.link is not None and gp.dtype == torch.bfloat16 and _chain_take(ctx.link[1]) is None:
-                    # this layer's data gradient + the PRODUCER's epilogue backward and bias sums in one launch: x_saved is the
-                    # producer's activation
-                    pnorm, pbox = ctx.link
-                    gx = torch.empty_like(gp)
-                    gbuf = torch.zeros(_ex_prev_scratch_floats(gp.device), device=gp.device, dtype=torch.float32)
-                    ring_multi(gp, pack_t.reshape(1, 14, 16, 32), ctx.he, [(gx, None, True)], extra=_lib.LF_RING_EX_PREV, e0=x_saved, e1=pnorm,
-                               o2=gbuf)
-                    _chain_arm(pbox, gx, gbuf[:16])
-                elif RING_DGRAD and gp.dtype == torch.bfloat16 and ctx.xdtype == torch.bfloat16:
-                    # the same sums and roundings on the one-group ring kernel with a compile-time epilogue (csrc/conv_gru.hip):
-                    # bit-identical, 32 instead of 53 us per 128^3 volume
-                    gx = torch.empty_like(gp)
-                    ring_multi(gp, pack_t.reshape(1, 14, 16, 32), ctx.he, [(gx, None, True)])
-                else:
-                    gx, _ = conv3d_c16_ring_bf16_io(gp, pack_t, None, ctx.he, 0, 1, out_bf16=ctx.xdtype == torch.bfloat16)
+            # the weight gradient first, on the side stream (WGRAD_STREAM): it then runs beside the data gradient below
+            wgrad = _Conv16AC._weight_grad_start(ctx, x_saved, gp) if ctx.needs_input_grad[1] else None
+            if ctx.needs_input_grad[0]:
+                gx, gb = _Conv16AC._data_grad(ctx, w, x_saved, gp, gb, pw_bwd and want_b)
             if ctx.needs_input_grad[1]:
-                if done is not None:
-                    torch.cuda.current_stream().wait_event(done)
-                if not fast:                                  # small volumes: the fp32-MFMA kernel on the same bf16 values
-                    xs = x_saved if x_saved.dtype == torch.bfloat16 else round_bf16(x_saved)
-                    gwt, _ = conv_bwd_weight(cl(xs.float()), cl(gp.float()), 3, 16, ctx.he, want_bias=False, bf16=False)
-                if ctx.one:
-                    gw = round_bf16(gwt[13].reshape(w.shape).contiguous())
-                else:
-                    gw = round_bf16(gwt.reshape(3, 3, 3, 16, 16).permute(3, 4, 0, 1, 2).contiguous())
+                gw = _Conv16AC._weight_grad_finish(ctx, w, x_saved, gp, wgrad)
         return gx, gw, gb if want_b else None, None, None
+
+    @staticmethod
+    def _preact_grad(ctx, gy, y, norm, want_b, pw_bwd):
+        """(pre-activation gradient in bf16, bias gradient or None)."""
+        if pw_bwd:                                                # no activation: it IS gy; the bias sums ride in lf_pw16_bwd
+            return gy, None
+        if ctx.box is not None and _chain_take(ctx.box) is not None:
+            return _chain_epilogue_bwd(ctx, gy, y, norm, want_b)  # the chained consumer ran this layer's epilogue backward
+        if ctx.flags == 0 and not want_b and gy.dtype == torch.bfloat16:
+            return gy, None
+        return epilogue_bwd_c16(gy, y, norm, ctx.flags, want_b)
+
+    @staticmethod
+    def _weight_grad_start(ctx, x_saved, gp):
+        """The bf16 weight gradient, launched: (side-stream helper, completion, gwt); None outside its domain (see _weight_grad_finish)."""
+        if not _wgrad_bf16_ok(gp, 3, 16, 16):
+            return None
+        N, D, H, W, _ = _geom(gp, 3)
+        gwt = torch.empty(27, 16, 16, device=gp.device, dtype=torch.float32)
+        wg = _Wgrad(3, N, D, H, W, 16, 16, gp.device, ctx.he, bf16=True)
+        io = (1 if x_saved.dtype == torch.bfloat16 else 0) | 2
+        sw = _SideWgrad(gp.device)
+        done = sw.run(lambda: wg(x_saved, gp, gwt), x_saved, gp, gwt, wg.scratch, timed=('wgrad3d_c16_bf16', f'{N}:io{io}'))
+        return sw, done, gwt
+
+    @staticmethod
+    def _weight_grad_finish(ctx, w, x_saved, gp, started):
+        if started is not None:
+            sw, done, gwt = started
+            sw.wait(done)
+        else:                                                     # small volumes: the fp32-MFMA kernel on the same bf16 values
+            xs = x_saved if x_saved.dtype == torch.bfloat16 else round_bf16(x_saved)
+            gwt, _ = conv_bwd_weight(cl(xs.float()), cl(gp.float()), 3, 16, ctx.he, want_bias=False, bf16=False)
+        if ctx.one:
+            return round_bf16(gwt[13].reshape(w.shape).contiguous())
+        return round_bf16(gwt.reshape(3, 3, 3, 16, 16).permute(3, 4, 0, 1, 2).contiguous())
+
+    @staticmethod
+    def _data_grad(ctx, w, x_saved, gp, gb, need_gb):
+        """(gx in the input's storage type, bias gradient): pointwise / chained-producer / ring-multi / ring-io."""
+        if ctx.pw and gp.dtype == torch.bfloat16:
+            # pointwise data gradient (+ this layer's bias gradient when nothing ran before it): one streamed pass
+            L = _lib.lib()
+            wtq = _pk(w, 'p1b', lambda t: t.detach().reshape(16, 16).t().to(torch.bfloat16).contiguous())
+            rows = gp.numel() // 16
+            out16 = ctx.xdtype == torch.bfloat16
+            gx = torch.empty_like(gp, dtype=torch.bfloat16 if out16 else torch.float32, memory_format=torch.preserve_format)
+            if need_gb:
+                gb = torch.empty(16, device=gp.device, dtype=torch.float32)
+                nb = L.lf_pw16_bwd_scratch_bytes(rows)
+                scr = torch.empty(nb // 4 + 4, device=gp.device, dtype=torch.float32)
+            launch('lf_pw16_bwd', gp, wtq, ctx.he, gx, 1 if out16 else 0, gb if need_gb else None, scr.data_ptr() if need_gb else None,
+                   scr.numel() * 4 if need_gb else 0, rows, tag='pw16_bwd', detail=f'{gp.shape[0]}:{out16}')
+            return gx, gb
+        w3 = (lambda t: pack_center_tap(t)) if ctx.one else (lambda t: t)
+        pack_t = _pk(w, 'a3b', lambda t: pack_conv3d_c16_ring_bf16(w3(t), transpose=True))
+        if ctx.link is not None and gp.dtype == torch.bfloat16 and _chain_take(ctx.link[1]) is None:
+            pnorm, pbox = ctx.link                                # + the PRODUCER's epilogue backward and bias sums: x_saved is its activation
+            gx = torch.empty_like(gp)
+            gbuf = torch.zeros(_ex_prev_scratch_floats(gp.device), device=gp.device, dtype=torch.float32)
+            ring_multi(gp, pack_t.reshape(1, 14, 16, 32), ctx.he, [(gx, None, True)], extra=_lib.LF_RING_EX_PREV, e0=x_saved, e1=pnorm,
+                       o2=gbuf)
+            _chain_arm(pbox, gx, gbuf[:16])
+        elif RING_DGRAD and gp.dtype == torch.bfloat16 and ctx.xdtype == torch.bfloat16:
+            # the same sums and roundings on the one-group ring kernel (csrc/conv_gru.hip): bit-identical, 32 instead of 53 us per 128^3
+            gx = torch.empty_like(gp)
+            ring_multi(gp, pack_t.reshape(1, 14, 16, 32), ctx.he, [(gx, None, True)])
+        else:
+            gx, _ = conv3d_c16_ring_bf16_io(gp, pack_t, None, ctx.he, 0, 1, out_bf16=ctx.xdtype == torch.bfloat16)
+        return gx, gb
 
 
 def _conv16_ac_ok(x, weight):
     return (storage_bf16() and x.dim() == 5 and weight.dim() == 5 and tuple(weight.shape[:2]) == (16, 16) and x.shape[1] == 16
-            and weight.shape[2] in (1, 3) and x.is_cuda and (x.shape[2] * x.shape[3] * x.shape[4]) * 64 < 2 ** 31)
+            and weight.shape[2] in (1, 3) and x.is_cuda and ring_multi_ok(*x.shape[2:]))
 
 
 class _Conv3x3Sum16(torch.autograd.Function):
@@ -625,341 +667,6 @@ class _LstmCell(torch.autograd.Function):
         gcc, gc = torch.empty_like(cc), torch.empty_like(c_cur)
         launch('lf_lstm_cell_bwd', cc, c_cur, gh, gcn, gcc, gc, c_cur.numel() // Ch, Ch)
         return gcc, gc
-
-
-def _gru_conv(ac, he, x, pack, addend=None, bias=None, out=None, out16=False, rnd=0):
-    """One 16 -> 16 convolution of the per-gate path of _GruFuse: the bf16 ring kernel under the autocast policy (`ac`), the
-    fp32 Winograd kernel otherwise; `addend` selects the addend form."""
-    if ac:
-        return conv3d_c16_ring_bf16_io(x, pack, bias, he, 0, rnd if addend is None else 0, addend=addend, out=out,
-                                       out_bf16=out16)[0]
-    prev = None if addend is None else (addend, None, _lib.LF_EPI_ADD)
-    return conv3d_c16_wino(x, pack, bias, he, 0, prev=prev, out=out)[0]
-
-
-def _gru_weight_grads(ctx, gwb, acc, c16, ws, he, ac):
-    """The (weight, bias) gradients of the three gates from the per-step / per-chunk blocks gwb [*][gate][z | state][27][16][16]
-    (summed in a fixed order) and the gate gradients' sums over the views acc[gate] (coordinate channels, bias)."""
-    outs = []
-    gsum = gwb.sum(dim=0)                                     # [gate][z | state][27][16][16]
-    for k, w in enumerate(ws):
-        gwt = torch.empty(27, 16, w.shape[1], device=gwb.device, dtype=torch.float32)
-        gwt[:, :, :16] = gsum[k, 0]
-        gwt[:, :, 19:] = gsum[k, 1]
-        gc_, _ = conv_bwd_weight(c16, acc[k], 3, 16, he, want_bias=False, bf16=ac)
-        gwt[:, :, 16:19] = gc_[:, :, :3]
-        gw = gwt.reshape(3, 3, 3, 16, w.shape[1]).permute(3, 4, 0, 1, 2).contiguous()
-        if ac:
-            gw = round_bf16(gw)
-        outs.append(gw if ctx.needs_input_grad[2 + 2 * k] else None)
-        outs.append(bias_grad(acc[k], 3) if (ctx.has_bias[k] and ctx.needs_input_grad[3 + 2 * k]) else None)
-    return outs
-
-
-class _GruFuse(torch.autograd.Function):
-    """GRUFuser.forward for 16-channel volumes as ONE autograd node (recon/fusion.py:188-197 over modules/gru.py:30-43): the
-    recurrence h_i = cell(cat(z_i, coords), h_{i-1}), h_0 = z_0, forward and backward sequenced explicitly.
-
-    Compared with the per-gate autograd functions (_Conv3x3Sum16 / _GruGates / _GruBlend) this removes every ATen gradient
-    accumulation over full volumes (the data gradients of a step chain through the addend form of the convolution, the
-    gate gradients' sums over the views are kept by the stage kernels), the sigmoid outputs are recomputed instead of stored,
-    and under the bf16 autocast policy the tensors that only half-precision convolutions produce / consume (gate
-    pre-activations, h*r, candidate, gate gradients) live in bf16 storage: 37 instead of ~90 volume passes per view.
-    z: (1,V,16,D,H,W) with dense channels-last views.  Returns h_V (1,16,D,H,W)."""
-
-    @staticmethod
-    def forward(ctx, z, c16, wu, bu, wr, br, wo, bo):
-        L = _lib.lib()
-        B, V = z.shape[0], z.shape[1]
-        assert B == 1 and z.shape[2] == 16 and z.is_cuda and z.dtype in (torch.float32, torch.bfloat16)
-        zz = _dense_views(z)                                      # (V,16,D,H,W) channels-last, fp32 or bf16 storage
-        D, H, W = zz.shape[2:]
-        ac = ops.AUTOCAST is not None
-        if not ac:
-            zz = _f32(zz)                                         # (a bf16-stored stack fused OUTSIDE the policy: the fp32 kernels read 64 B records)
-        T16 = ac                                                  # bf16 storage of the once-per-step tensors
-        he = he_constant(wu)
-        gates = ((wu, bu), (wr, br), (wo, bo))
-
-        def packs(w):
-            def make():
-                wd = _wsrc(w).detach()
-                wc = wd.new_zeros(16, 16, 3, 3, 3)
-                wc[:, :3] = wd[:, 16:19]
-                pk = pack_conv3d_c16_ring_bf16 if ac else pack_conv3d_c16_wino
-                return tuple((pk(t), pk(t, transpose=True)) for t in (wd[:, :16].contiguous(), wc, wd[:, 19:].contiguous()))
-            return _cached(w, 'gru_fuse' + ('@ac' if ac else ''), make)
-        pk = [packs(w) for w, _ in gates]                         # [gate][z | coords | state][fwd | transposed]
-
-        conv = functools.partial(_gru_conv, ac, he)
-        n = zz[0].numel()
-        base = [conv(c16, pk[k][1][0], bias=(b.detach() if b is not None else None)) for k, (_, b) in enumerate(gates)]
-        ctx.ring = bool(GRU_RING and ac and V >= 2 and D * H * W * 64 < 2 ** 31)
-        if ctx.ring:
-            ctx.z32 = zz.dtype != torch.bfloat16
-            z_in = zz
-            if ctx.z32:                                           # (the convolutions round x to bf16 while staging anyway: same numbers)
-                zz = zz.to(torch.bfloat16)
-            # ---- round 6: the multi-output ring kernels (csrc/conv_gru.hip).  The per-step tensors are STACKED blocks
-            # [V-1]: UP / RP / CA are first filled with the state-independent parts of the three gates (one launch over all
-            # views: x feeds three gates), then overwritten in place by the pre-activations / the candidate of their step;
-            # the backward overwrites them once more with the gate GRADIENTS, which the weight gradients then read as
-            # multi-volume launches -- no per-step allocation, no element-wise stage launch in the forward at all.
-            wz = (torch.stack((pk[0][0][0], pk[1][0][0])), pk[2][0][0].reshape(1, 14, 16, 32))     # packs back to back: [u | r], [o]
-            wh = (torch.stack((pk[0][2][0], pk[1][2][0])), pk[2][2][0].reshape(1, 14, 16, 32))
-            blk = lambda: empty_cl16((V - 1, 16, D, H, W), zz.device, True)      # noqa: E731
-            UP, RP, CA, RH = blk(), blk(), blk(), blk()
-            HS = empty_cl((V - 1, 16, D, H, W), zz.device)                       # h_0 .. h_{V-2} (fp32 state)
-            HS[0:1].copy_(z_in[0:1])                              # (h_0 = view 0, un-rounded when the stack is fp32)
-            # a bf16 copy of every state (round 6): what the gate convolutions and the weight gradients STAGE -- they round h to
-            # bf16 while staging anyway, so reading the rounded copy is the same arithmetic at half the bytes; the fp32 state
-            # stays what the element-wise stages (r h, the blend and their backward) use
-            H16 = blk() if GRU_STATE_BF16 else None
-            if H16 is not None:
-                H16[0:1].copy_(z_in[0:1])
-            if GRU_RING_GROUPS == 2:
-                ring_multi(zz[1:], wz[0], he, [(UP, base[0], False), (RP, base[1], False)], addend_per_sample=False)
-            else:
-                for k_, blk_ in enumerate((UP, RP)):
-                    ring_multi(zz[1:], pk[k_][0][0].reshape(1, 14, 16, 32), he, [(blk_, base[k_], False)], addend_per_sample=False)
-            ring_multi(zz[1:], wz[1], he, [(CA, base[2], False)], addend_per_sample=False)
-            out = empty_cl(HS[0:1].shape, zz.device)
-            whu, whr = pk[0][2][0].reshape(1, 14, 16, 32), pk[1][2][0].reshape(1, 14, 16, 32)
-            for i in range(1, V):
-                h, j = HS[i - 1:i], slice(i - 1, i)
-                hx = H16[j] if H16 is not None else h            # the staged operand
-                if GRU_RING_GROUPS == 2:
-                    ring_multi(h, wh[0], he, [(UP[j], UP[j], False), (RP[j], RP[j], False)], extra=_lib.LF_RING_EX_RH, o2=RH[j])
-                else:                                             # (two one-output launches: two workgroups per CU overlap their phases)
-                    ring_multi(hx, whu, he, [(UP[j], UP[j], False)])
-                    ring_multi(hx, whr, he, [(RP[j], RP[j], False)], extra=_lib.LF_RING_EX_RH, e0=h if H16 is not None else None, o2=RH[j])
-                hn = HS[i:i + 1] if i < V - 1 else out
-                launch('lf_conv3d_c16_ring_blend', RH[j], wh[1], CA[j], CA[j], h, UP[j], hn,
-                       H16[i:i + 1] if (H16 is not None and i < V - 1) else None, 1, D, H, W, he, tag='conv3d_c16_ring_multi',
-                       detail='1:2:1:11:2')
-            ctx.ac, ctx.T16, ctx.he, ctx.pk = ac, T16, he, pk
-            ctx.blocks = [UP, RP, CA, RH, HS, H16]
-            ctx.zshape = tuple(z.shape)
-            ctx.save_for_backward(zz, c16, wu, wr, wo)
-            ctx.has_bias = tuple(b is not None for _, b in gates)
-            return out
-        hs, saved = [_f32(zz[0:1])], []                            # (the state is fp32; view 0 seeds it)
-        for i in range(1, V):
-            zi, h = zz[i:i + 1], hs[-1]
-            pre = []
-            for k in (0, 1):
-                xk = conv(zi, pk[k][0][0], addend=base[k], out16=T16)
-                pre.append(conv(h, pk[k][2][0], addend=xk, out16=T16))
-                del xk
-            upre, rpre = pre
-            rh = empty_cl16(h.shape, h.device, T16)
-            launch('lf_gru_train_stage_a', rpre, h, rh, n, int(T16))
-            xo = conv(zi, pk[2][0][0], addend=base[2], out16=T16)
-            cand = conv(rh, pk[2][2][0], addend=xo, out16=T16)
-            del xo
-            hn = empty_cl(h.shape, h.device)
-            launch('lf_gru_train_stage_b', h, upre, cand, hn, n, int(T16))
-            saved.append((upre, rpre, rh, cand))
-            hs.append(hn)
-        ctx.ac, ctx.T16, ctx.he, ctx.pk = ac, T16, he, pk
-        ctx.steps = saved
-        ctx.hs = hs[1:-1]                                         # h_1 .. h_{V-2}
-        ctx.h0 = hs[0] if zz.dtype != torch.float32 else None     # (fp32 storage: h_0 is a view of z, saved below)
-        ctx.zshape = tuple(z.shape)
-        ctx.save_for_backward(zz, c16, wu, wr, wo)
-        ctx.has_bias = tuple(b is not None for _, b in gates)
-        return hs[-1].clone() if V == 1 else hs[-1]
-
-    @staticmethod
-    def backward(ctx, g):
-        zz, c16, wu, wr, wo = ctx.saved_tensors
-        V = zz.shape[0]
-        ac, T16, he, pk = ctx.ac, ctx.T16, ctx.he, ctx.pk
-        dev = zz.device
-        n = zz[0].numel()
-        shape1 = (1,) + tuple(zz.shape[1:])
-        D, H, W = zz.shape[2:]
-        need_z = ctx.needs_input_grad[0]
-        need_w = any(ctx.needs_input_grad[i] for i in (2, 3, 4, 5, 6, 7))
-        g = cl(g.reshape(shape1))
-        if ctx.ring:
-            return _gru_backward_ring(ctx, g, zz, c16, (wu, wr, wo), need_z, need_w)
-        conv = functools.partial(_gru_conv, ac, he)
-        gz = empty_cl16((V, 16, D, H, W), dev, zz.dtype == torch.bfloat16) if need_z else None
-        acc = [empty_cl(shape1, dev).zero_() for _ in range(3)] if need_w else [None] * 3
-        # weight-gradient blocks [step][gate][z | state][27][16][16], summed over the steps at the end (fixed order)
-        gwb = torch.zeros(max(V - 1, 1), 3, 2, 27, 16, 16, device=dev, dtype=torch.float32) if need_w else None
-        wg = _Wgrad(3, 1, D, H, W, 16, 16, dev, he, bf16=ac) if need_w else None      # (one scratch: the launches are in order)
-
-        def wgrad(x, gp, dst):
-            if ac and wg.entry != _Wgrad.BF16:                    # small volumes: the fp32-MFMA kernel on the same bf16 values
-                x, gp = round_bf16(x.float()), round_bf16(gp.float())
-            wg(x, gp, dst)
-        gh1 = empty_cl(shape1, dev)
-        gh12 = empty_cl(shape1, dev)
-        grh = empty_cl16(shape1, dev, T16)
-        # the six weight gradients of a step run on the side stream (WGRAD_STREAM) beside the data-gradient chain; the gate
-        # gradients they read are double-buffered, a buffer is rewritten only after the launches that read it have finished
-        main = torch.cuda.current_stream()
-        side = side_stream(dev) if (WGRAD_STREAM and need_w and ops.KERNEL_TIMER is None) else None
-        gbuf = [tuple(empty_cl16(shape1, dev, T16) for _ in range(3)) for _ in range(2 if side is not None else 1)]
-        gdone = [None, None]
-        if side is not None:
-            side.wait_stream(main)
-            for t in (gwb, wg.scratch, zz) + tuple(b for bb in gbuf for b in bb):
-                t.record_stream(side)
-        steps, hs = ctx.steps, ctx.hs
-        for i in range(V - 1, 0, -1):
-            gupre, gc, grpre = gbuf[i & 1 if side is not None else 0]
-            if gdone[i & 1] is not None:
-                main.wait_event(gdone[i & 1])
-            if steps[i - 1] is None:
-                raise RuntimeError('the fused GRU recurrence frees its activations during backward: a second backward through '
-                                   'the same graph is not supported')
-            upre, rpre, rh, cand = steps[i - 1]
-            h = (ctx.h0 if ctx.h0 is not None else zz[0:1]) if i == 1 else hs[i - 2]
-            zi = zz[i:i + 1]
-            launch('lf_gru_train_stage_b_bwd', g, h, upre, cand, gh1, gupre, gc, acc[0],
-                   acc[2], n, int(T16))
-            conv(gc, pk[2][2][1], out=grh, rnd=1)
-            launch('lf_gru_train_stage_a_bwd', grh, rpre, h, gh1, grpre, gh12, acc[1], n, int(T16))
-            if side is not None:
-                ready = torch.cuda.Event()
-                ready.record(main)                                # the three gate gradients of this step are complete
-                side.wait_event(ready)
-                h.record_stream(side)
-                rh.record_stream(side)
-                with torch.cuda.stream(side):
-                    for k, (xs, gp) in enumerate((((zi, h), gupre), ((zi, h), grpre), ((zi, rh), gc))):
-                        wgrad(xs[0], gp, gwb[i - 1, k, 0])
-                        wgrad(xs[1], gp, gwb[i - 1, k, 1])
-                    gdone[i & 1] = torch.cuda.Event()
-                    gdone[i & 1].record(side)
-            if need_z:
-                gzi = gz[i:i + 1]
-                conv(gc, pk[2][0][1], out=gzi, rnd=1)
-                conv(gupre, pk[0][0][1], addend=gzi, out=gzi)
-                conv(grpre, pk[1][0][1], addend=gzi, out=gzi)
-            gnext = empty_cl(shape1, dev)
-            conv(gupre, pk[0][2][1], addend=gh12, out=gnext)
-            conv(grpre, pk[1][2][1], addend=gnext, out=gnext)
-            if need_w and side is None:
-                for k, (xs, gp) in enumerate((((zi, h), gupre), ((zi, h), grpre), ((zi, rh), gc))):
-                    wgrad(xs[0], gp, gwb[i - 1, k, 0])
-                    wgrad(xs[1], gp, gwb[i - 1, k, 1])
-            g = gnext
-            steps[i - 1] = None                                   # the step's tensors are dead: free them as the walk goes
-            if i >= 2:
-                hs[i - 2] = None
-        if side is not None:
-            main.wait_stream(side)
-        if need_z:
-            gz[0:1].copy_(g)
-        outs = [gz.view(ctx.zshape) if need_z else None, None]
-        outs += _gru_weight_grads(ctx, gwb, acc, c16, (wu, wr, wo), he, ac) if need_w else [None] * 6
-        return tuple(outs)
-
-
-def _gru_backward_ring(ctx, g, zz, c16, ws, need_z, need_w):
-    """Backward of the recurrence on the multi-output ring kernels (see the forward): per step ONE element-wise launch
-    (lf_gru_train_stage_b_bwd, gate gradients written over the saved pre-activations) and three convolution launches --
-        gc    -> (g_rh with the reset gate's backward in its epilogue, g_x)
-        gupre -> (g_x +=, g_h = gh12 +)          grpre -> (g_x +=, g_h +=)
-    (was: two stage kernels + six convolutions + six weight-gradient launches).  The weight gradients run afterwards over the
-    STORED gate gradients as multi-volume launches, in chunks of GRU_WGRAD_CHUNK steps on the side stream beside the chain;
-    the sums over the steps that the bias / coordinate-channel gradients need come from lf_sum_views_bf16 over the same blocks."""
-    if ctx.blocks is None:
-        raise RuntimeError('the fused GRU recurrence overwrites its activations during backward: a second backward through '
-                           'the same graph is not supported')
-    UP, RP, CA, RH, HS, H16 = ctx.blocks
-    HX = H16 if H16 is not None else HS                          # the state as the weight gradients stage it
-    ctx.blocks = None
-    V = zz.shape[0]
-    he, pk = ctx.he, ctx.pk
-    dev = zz.device
-    D, H, W = zz.shape[2:]
-    shape1 = (1,) + tuple(zz.shape[1:])
-    n = zz[0].numel()
-    # transposed packs: [o: towards r h | towards x], [u: towards x | towards h], [r: towards x | towards h]
-    tp = tuple(torch.stack(p) for p in ((pk[2][2][1], pk[2][0][1]), (pk[0][0][1], pk[0][2][1]), (pk[1][0][1], pk[1][2][1])))
-    gz = empty_cl16((V, 16, D, H, W), dev, True)
-    gh1, gh12 = empty_cl(shape1, dev), empty_cl(shape1, dev)
-    gbuf = [empty_cl(shape1, dev), empty_cl(shape1, dev)]
-    main = torch.cuda.current_stream()
-    side = side_stream(dev) if (WGRAD_STREAM and need_w and ops.KERNEL_TIMER is None) else None
-    chunks = []                                                   # (first step, one past the last step) in launch order
-    hi = V
-    while hi > 1:
-        lo = max(1, hi - GRU_WGRAD_CHUNK) if GRU_WGRAD_CHUNK > 0 else 1
-        chunks.append((lo, hi))
-        hi = lo
-    gwb = torch.zeros(len(chunks), 3, 2, 27, 16, 16, device=dev, dtype=torch.float32) if need_w else None
-    acc = [empty_cl(shape1, dev) for _ in range(3)] if need_w else None
-    wg = _Wgrad(3, V, D, H, W, 16, 16, dev, he, bf16=True) if need_w else None     # (one scratch: the launches are in order)
-    if side is not None:
-        side.wait_stream(main)                                    # (the allocations above)
-        for t in [gwb, zz, UP, RP, CA, RH, HS, HX, wg.scratch] + acc:
-            t.record_stream(side)
-
-    def weight_grads(ci, lo, hi):
-        """The six weight gradients of steps lo .. hi-1 (their gate gradients are final) + this chunk's share of the sums."""
-        nv = hi - lo
-        j = slice(lo - 1, hi - 1)
-        for k, (gp, xh) in enumerate(((UP, HX), (RP, HX), (CA, RH))):
-            for q, x in enumerate((zz[lo:hi], xh[j])):
-                wg(x, gp[j], gwb[ci, k, q])
-            launch('lf_sum_views_bf16', gp[j], acc[k], n, nv, int(ci > 0))
-
-    def on_side(fn, *a):
-        if side is not None:
-            ready = torch.cuda.Event()
-            ready.record(main)                                    # the gate gradients the launches read are complete
-            side.wait_event(ready)
-            with torch.cuda.stream(side):
-                fn(*a)
-        else:
-            fn(*a)
-    two = GRU_RING_GROUPS == 2
-    one = lambda p: p.reshape(1, 14, 16, 32)                      # noqa: E731
-    for ci, (lo, hi) in enumerate(chunks):
-        for i in range(hi - 1, lo - 1, -1):
-            j = slice(i - 1, i)
-            h = HS[j]
-            gnext = gbuf[i & 1]
-            launch('lf_gru_train_stage_b_bwd', g, h, UP[j], CA[j], gh1, UP[j], CA[j], None, None, n, 1)
-            if two:
-                ring_multi(CA[j], tp[0], he, [(RP[j], RP[j], True), (gz[i:i + 1], None, True)], extra=_lib.LF_RING_EX_ABWD,
-                           e0=h, e1=gh1, o2=gh12)
-                ring_multi(UP[j], tp[1], he, [(gz[i:i + 1], gz[i:i + 1], False), (gnext, gh12, False)])
-                ring_multi(RP[j], tp[2], he, [(gz[i:i + 1], gz[i:i + 1], False), (gnext, gnext, False)])
-            else:
-                # one-output launches on the chain (the state's gradient only); the gradients of the views follow the loop
-                ring_multi(CA[j], one(tp[0][0]), he, [(RP[j], RP[j], True)], extra=_lib.LF_RING_EX_ABWD, e0=h, e1=gh1, o2=gh12)
-                ring_multi(UP[j], one(tp[1][1]), he, [(gnext, gh12, False)])
-                ring_multi(RP[j], one(tp[2][1]), he, [(gnext, gnext, False)])
-            g = gnext
-        if need_w:
-            on_side(weight_grads, ci, lo, hi)
-    if not two:
-        if need_z:                                                # the views' gradients, from the stored gate gradients of all steps
-            gzs = gz[1:]
-            ring_multi(CA, one(tp[0][1]), he, [(gzs, None, True)])
-            ring_multi(UP, one(tp[1][0]), he, [(gzs, gzs, False)])
-            ring_multi(RP, one(tp[2][0]), he, [(gzs, gzs, False)])
-    if side is not None:
-        main.wait_stream(side)
-    if ctx.z32:
-        gz = gz.float()
-    gz[0:1].copy_(g)
-    outs = [gz.view(ctx.zshape) if need_z else None, None]
-    outs += _gru_weight_grads(ctx, gwb, acc, c16, ws, he, True) if need_w else [None] * 6
-    return tuple(outs)
-
-
-def gru_fuse(z, c16, cell):
-    """See _GruFuse.  `cell`: the ConvGRUCell (three EqualizedConv3d gates over 16 + 3 + 16 input channels)."""
-    gs = (cell.update_gate, cell.reset_gate, cell.out_gate)
-    return _GruFuse.apply(z, c16, gs[0].module.weight, gs[0].bias, gs[1].module.weight, gs[1].bias, gs[2].module.weight, gs[2].bias)
 
 
 def lstm_cell(cc, c_cur):

@@ -95,7 +95,7 @@ def check(name, got, ref, bound, wrong=()):
 def switches():
     """Saves and restores every module switch the tests below flip."""
     from latentfusion_amd import ops, ops_train
-    names = ('RING_BLOCK_FWD', 'RING_DGRAD', 'CHAIN_EPILOGUE', 'PW16', 'GRU_RING')
+    names = ('RING_BLOCK_FWD', 'RING_DGRAD', 'CHAIN_EPILOGUE', 'PW16', 'GRU_RING', 'GRU_WGRAD_CHUNK', 'WGRAD_STREAM')
     saved = {n: getattr(ops_train, n) for n in names}
     storage = ops.BF16_STORAGE
     try:
@@ -527,15 +527,19 @@ def test_resample_vs_fp64(kind, shared, src, leave):
 
 
 # ---- _GruFuse through fusion.GRUFuser(16) ------------------------------------------------------------------------------
-@pytest.mark.parametrize('mode', ['autocast_ring', 'autocast', 'fp32'])
-@pytest.mark.parametrize('V', [2, 4])
+@pytest.mark.parametrize('V, mode', [(V, mode) for mode in ('autocast_ring', 'autocast', 'fp32') for V in (2, 4)]
+                         + [(4, 'autocast_ring_chunk2')])
 def test_gru_fuser_vs_fp64(V, mode, switches):
     """The fused ConvGRU recurrence (one autograd node; GRU_RING: the multi-output ring kernels) against nets.gru_step in
     fp64: output, gradient of the per-view volumes and of the six gate parameters.  The error grows with the number of
-    views (the state is carried through V - 1 steps), so the bounds are per V."""
+    views (the state is carried through V - 1 steps), so the bounds are per V.  autocast_ring_chunk2: the ring recurrence's
+    weight gradients in two chunks of GRU_WGRAD_CHUNK = 2 steps (steps 3, 2 and step 1), the second one accumulating the gate
+    gradients' sums (lf_sum_views_bf16 with `accumulate`) -- same bounds, same wrong references."""
     from latentfusion_amd import ops
     from latentfusion_amd.recon import fusion
-    switches.GRU_RING = mode == 'autocast_ring'
+    switches.GRU_RING = mode.startswith('autocast_ring')
+    if mode == 'autocast_ring_chunk2':
+        switches.GRU_WGRAD_CHUNK = 2
     ac = mode != 'fp32'
     torch.manual_seed(11)
     fu = fusion.GRUFuser(16).to(DEV)
@@ -578,3 +582,32 @@ def test_gru_fuser_vs_fp64(V, mode, switches):
         other = k.replace(gate, swap[gate])
         kind = 'gb' if k.endswith('bias') else 'gw'
         check(k, params[k].grad, rgp[k], bounds[kind], [(f'the gradient of {other}', rgp[other]), (f'{k} negated', -rgp[k])])
+
+
+def test_gru_fuser_small_volume_takes_the_step_recurrence(switches):
+    """A volume below the bf16 weight-gradient kernel's 8192 voxels (5 x 12 x 20, two views, autocast with bf16 storage,
+    trainable gates): the ring recurrence stores its gate gradients in bf16 and has no weight-gradient kernel for them there, so
+    GRU_RING leaves such a volume to the step recurrence -- output and every gradient are those of GRU_RING = False, bit for bit."""
+    from latentfusion_amd import ops
+    from latentfusion_amd.recon import fusion
+    torch.manual_seed(12)
+    fu = fusion.GRUFuser(16).to(DEV)
+    with torch.no_grad():
+        for gate in (fu.gru.update_gate, fu.gru.reset_gate, fu.gru.out_gate):
+            gate.bias.normal_(0.0, 0.3)
+    g = torch.Generator().manual_seed(_seed('gru-small'))
+    z0 = torch.randn(1, 2, 16, 5, 12, 20, generator=g).to(DEV).to(torch.bfloat16)
+    gout = torch.randn(1, 1, 16, 5, 12, 20, generator=g).to(DEV)
+
+    def run(ring):
+        switches.GRU_RING = ring
+        z = z0.clone().requires_grad_(True)
+        fu.zero_grad(set_to_none=True)
+        with ops.autocast(True):
+            out, _ = fu(z, None, None, None)
+        (out * gout).sum().backward()
+        return [out.detach(), z.grad] + [p.grad for p in fu.parameters()]
+    on, off = run(True), run(False)
+    assert len(on) == 8 and all(t is not None for t in on)
+    for a, b in zip(on, off):
+        assert a.dtype == b.dtype and torch.equal(a, b)
