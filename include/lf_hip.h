@@ -168,8 +168,12 @@ int lf_conv1x1_fwd_scaled(const float* x, const float* xscale, const float* wpac
  * weights (taps flipped / in-out swapped).  When prev_y != NULL the epilogue backward of the layer
  * that PRODUCED this convolution's input (whose saved output is prev_y, norm prev_norm, epilogue
  * prev_flags) is folded into the store, i.e. the result is already dL/d(pre-activation) of that
- * layer and no separate lf_epilogue_bwd pass over the volume is needed.  Requires 16-channel
- * records (Cout == 16 for 3x3; y_slice_channels == y_row_stride == 16 for 1x1). */
+ * layer and no separate lf_epilogue_bwd pass over the volume is needed.
+ *   3x3: Cout (the producer's channel count) in {16, 32, 64}; a voxel's whole row of Cout channels lies in one workgroup's
+ *        tiles, PixelNorm' takes its mean over all Cout channels and prev_norm is indexed by voxel, prev_norm[N*D*H*W].
+ *   1x1: 16-channel records, y_slice_channels == y_row_stride == 16, Cout and the two y strides multiples of 16; PixelNorm'
+ *        takes its mean over the record and prev_norm is indexed by record, prev_norm[offset of the record in gx / 16].
+ * prev_norm is required with LF_EPI_PIXELNORM in prev_flags; prev_y must be 16-byte aligned. */
 int lf_conv3x3_bwd_data(const float* gy, const float* wpack_t, float* gx, int dims, int N, int D, int H, int W,
                         int Cin, int Cout, float he, const float* prev_y, const float* prev_norm,
                         unsigned prev_flags, float slope, void* stream);
